@@ -12,7 +12,13 @@ one E+M iteration (one GPU: spk_em_iteration_start / _wait, a single launch; N G
 spk_em_histogram -> RCCL all-reduce -> spk_em_finalize) + the host M-step (Params update).  On one
 GPU the loop is software-pipelined: pass i is queued before the host M-step of iteration i - 1.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--records R] [--no-cpu-baseline]
+A plain run sets up, warms up, times the steps and prints the headline line.  `--dump-outputs DIR` also
+writes what the last timed step computed (dump_outputs).  Everything else the benchmark measures -- the
+scoring pass, the rooflines and committed counter records, the CPU baseline, the string rates, the E/M
+streaming row and the cfg5_columns sub-record -- runs only with `--full`.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--records R] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--em-scale S] [--cfg5-steps K]
 """
 from __future__ import annotations
 
@@ -160,6 +166,7 @@ def timed_run(config, records, shard, world, rank, local, steps, warmup):
     host = {"gammas_call": [], "em_wait": [], "m_step_host": [], "em_start": []}
     dev = {"gamma": [], "em_hist": [], "em_final": []}
     pending = [False]
+    last = {}
 
     def finish_m_step():
         """Statistics of the enqueued E+M iteration, then the host M-step (Params update)."""
@@ -169,6 +176,7 @@ def timed_run(config, records, shard, world, rank, local, steps, warmup):
         lam, rows = m_step_rows(stats, names, nlev)
         params._update_params(lam, rows)
         t2 = time.perf_counter()
+        last["stats"] = stats
         host["em_wait"].append((t1 - t0) * 1e3)
         host["m_step_host"].append((t2 - t1) * 1e3)
         pending[0] = False
@@ -223,7 +231,43 @@ def timed_run(config, records, shard, world, rank, local, steps, warmup):
     return argparse.Namespace(job=job, df=df, params=params, st=st, cols=cols, names=names, nlev=nlev,
                               n_records=n_records, gamma_ms=gamma_ms, hist_ms=hist_ms, fin_ms=fin_ms, host=host,
                               local_pairs=local_pairs, total_pairs=total_pairs, ms_per_step=ms_per_step,
+                              last_stats=last["stats"],
                               block_s=block_s, block_kernel_ms=block_kernel_ms, first_gammas_s=first_gammas_s)
+
+
+DUMP_RUNS, DUMP_RUN_ROWS = 256, 4096  # --dump-outputs: the sample of comparison vectors (1 Mi pairs)
+
+
+def dump_outputs(path, R):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as DIR/<name>.npy.
+
+    em_stats (float64): the E+M iteration's sufficient statistics as Job.em_wait returned them (summed over
+    the ranks).  lambda, m_probabilities, u_probabilities (float64): the parameters after the host M-step on
+    those statistics, the level tables flattened in column order as the next iteration would receive them.
+    gammas_sample (float32, pairs x columns) and gammas_sample_rows (float64): the last pass's comparison
+    vectors at a fixed, seeded sample of rank 0's pair ordinals -- DUMP_RUNS runs of DUMP_RUN_ROWS consecutive
+    pairs, or every pair when there are no more than that -- and those ordinals.  The records and the sample
+    are seeded and the pairs come in ordinal order: the same arguments give the same arrays, 29 MB at cfg2."""
+    from splink_amd.engine import Job
+    job, params, K, P = R.job, R.params, len(R.names), R.job.n_pairs
+    os.makedirs(path, exist_ok=True)
+    if P <= DUMP_RUNS * DUMP_RUN_ROWS:
+        starts, rows_per = np.zeros(1, np.int64), P
+    else:
+        rng = np.random.Generator(np.random.PCG64(11))
+        starts = np.sort(rng.choice(P // DUMP_RUN_ROWS, size=DUMP_RUNS, replace=False)).astype(np.int64) * DUMP_RUN_ROWS
+        rows_per = DUMP_RUN_ROWS
+    g = np.concatenate([job.ctx.gammas_copy(K, int(s), rows_per) for s in starts])
+    rows = (starts[:, None] + np.arange(rows_per, dtype=np.int64)[None, :]).reshape(-1)
+    lam = params.params["λ"]
+    m, u = Job.flat_tables(params._level_probabilities())
+    arrays = {"em_stats": np.asarray(R.last_stats, dtype=np.float64),
+              "lambda": np.array([lam], dtype=np.float64),
+              "m_probabilities": m, "u_probabilities": u,
+              "gammas_sample": g.astype(np.float32), "gammas_sample_rows": rows.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"dumped {', '.join(arrays)} ({sum(a.nbytes for a in arrays.values()) / 1e6:.1f} MB) to {path}")
 
 
 def main():
@@ -244,17 +288,25 @@ def main():
                          "ranks (strong scaling); 5: + free-text address Levenshtein-4 (cfg5's columns at cfg2's size)")
     ap.add_argument("--share", type=str, default=None,
                     help="k/n: run rank k's share of an n-rank job on this one GPU (e.g. --config 4 --share 0/8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run and report the scoring pass, the rooflines and counter "
+                         "records, the CPU baseline, the string rates, the E/M streaming row and cfg5_columns")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cfg5-steps", type=int, default=10,
-                    help="the cfg5_columns sub-record of a one-GPU cfg2 run: steps timed (0 = off)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
+                    help="with --full: the cfg5_columns sub-record of a one-GPU cfg2 run: steps timed (0 = off)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full: time budget of the CPU baseline")
     ap.add_argument("--gamma-graph", action="store_true",
                     help="replay unchanged comparison passes from a captured HIP graph (measured slower; A/B only)")
     ap.add_argument("--gamma-streams", type=int, default=2, choices=[1, 2],
                     help="comparison pass as two concurrent half windows on two streams (2, default) or one (1)")
     ap.add_argument("--em-scale", type=int, default=8,
-                    help="separate E/M streaming row: the run's comparison vectors tiled this many times (0 = off)")
+                    help="with --full: separate E/M streaming row, the run's comparison vectors tiled this many "
+                         "times (0 = off)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least one timed step, --warmup none or more")
     global GAMMA_STREAMS
     GAMMA_STREAMS = args.gamma_streams
     global GAMMA_GRAPH
@@ -321,16 +373,20 @@ def main():
         assert world == 1 and 0 <= k < n, "--share runs one rank's share on one GPU"
         shard = (k, n)
     R = timed_run(args.config, args.records, shard, world, rank, local, args.steps, args.warmup)
-    job, df, params, st, cols, names, nlev = R.job, R.df, R.params, R.st, R.cols, R.names, R.nlev
+    job, params, cols = R.job, R.params, R.cols
     n_records, gamma_ms, hist_ms, fin_ms, host = R.n_records, R.gamma_ms, R.hist_ms, R.fin_ms, R.host
-    local_pairs, total_pairs, ms_per_step = R.local_pairs, R.total_pairs, R.ms_per_step
+    total_pairs, ms_per_step = R.total_pairs, R.ms_per_step
     block_s, block_kernel_ms, first_gammas_s = R.block_s, R.block_kernel_ms, R.first_gammas_s
 
-    # ---- full job (blocking excluded from the metric): score pass for the record
-    t0 = time.perf_counter()
-    job.score(params.params["λ"], params._level_probabilities(), want_host=False)
-    torch.cuda.synchronize()
-    score_ms = job.ctx.kernel_ms()["score"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, R)
+
+    score_ms = None
+    if args.full:
+        # ---- full job (blocking excluded from the metric): score pass for the record
+        job.score(params.params["λ"], params._level_probabilities(), want_host=False)
+        torch.cuda.synchronize()
+        score_ms = job.ctx.kernel_ms()["score"]
 
     if rank != 0:
         if world > 1:
@@ -339,6 +395,57 @@ def main():
             dist.destroy_process_group()
         return
 
+    out = {
+        "metric": "candidate pairs scored/sec (gammas+E+M per iter)",
+        "value": total_pairs / (ms_per_step / 1e3),
+        "unit": "pairs/s",
+        "n_gpus": world,
+        "ranks_seen": ranks_seen,
+        "backend": args.backend if world > 1 else None,
+        "devices_used": min(world, n_dev),
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong" if args.config == 4 else "weak",
+        "vs_baseline": None,
+        "dtype": "fp64",
+        "data": "synthetic",
+        "full": args.full,
+        "config": {"workload": WORKLOADS[args.config],
+                   "records": n_records, "candidate_pairs": total_pairs, "comparison_columns": len(cols),
+                   "candidate_ordinals_total": job.n_candidates, "shard": list(shard),
+                   "comparison_windows": job.ctx.gammas_windows(),
+                   "parallelism": f"pair-ordinal shards x{world}, " + (
+                       "RCCL all-reduce of pattern histogram" if args.backend == "nccl" or world == 1 else
+                       "gloo all-reduce of pattern histogram (host-staged rehearsal, ranks sharing GPUs)")},
+        "breakdown_ms": {"gamma": float(np.mean(gamma_ms)), "em_hist": float(np.mean(hist_ms)),
+                         "em_final": float(np.mean(fin_ms)),
+                         "block_device": block_kernel_ms, "block_wall": block_s * 1e3,
+                         "block_keys_wall": job.timings.get("block_keys_s", 0.0) * 1e3,
+                         "first_gammas_call_incl_column_decode": first_gammas_s * 1e3,
+                         **{f"host_wall_{k}": float(np.mean(v)) for k, v in host.items()}},
+        "input": "Arrow-backed string columns (pd.ArrowDtype(large_string)); keys, ids, ranks, clustering on the device",
+    }
+    if args.full:
+        out["breakdown_ms"]["score"] = score_ms
+        out.update(full_record(args, R, score_ms, world))
+        if world == 1 and args.config == 2 and args.cfg5_steps > 0 and not args.share:
+            # cfg5's columns in the same run, after the headline (never the headline): the free-text address
+            # column's Levenshtein passes are the other workload the comparison kernels are tuned on
+            del job, R
+            out["cfg5_columns"] = cfg5_record(args, local)
+    emit(out)
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_record(args, R, score_ms, world):
+    """What `--full` adds to the line for the headline's job (runs of their own, after the timed steps)."""
+    job, df, params, st, cols, names, nlev = R.job, R.df, R.params, R.st, R.cols, R.names, R.nlev
+    gamma_ms, hist_ms, fin_ms, local_pairs = R.gamma_ms, R.hist_ms, R.fin_ms, R.local_pairs
     # ---- roofline of the dominant kernel (comparison-vector pass) -------------------------
     # SURVEY §8(d) algorithmic bytes: 8 + K bytes per pair (read the int32 pair, write the γ vector)
     # plus every record's field bytes once (UTF-8).  The pass writes a packed 2-byte code instead of
@@ -401,40 +508,12 @@ def main():
     if world == 1 and args.em_scale > 0 and args.config != 4:
         em_scale = em_streaming(job, names, nlev, params, args.em_scale)
 
-    out = {
-        "metric": "candidate pairs scored/sec (gammas+E+M per iter)",
-        "value": total_pairs / (ms_per_step / 1e3),
-        "unit": "pairs/s",
-        "n_gpus": world,
-        "ranks_seen": ranks_seen,
-        "backend": args.backend if world > 1 else None,
-        "devices_used": min(world, n_dev),
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong" if args.config == 4 else "weak",
-        "vs_baseline": None,
-        "dtype": "fp64",
-        "data": "synthetic",
-        "config": {"workload": WORKLOADS[args.config],
-                   "records": n_records, "candidate_pairs": total_pairs, "comparison_columns": len(cols),
-                   "candidate_ordinals_total": job.n_candidates, "shard": list(shard),
-                   "comparison_windows": job.ctx.gammas_windows(),
-                   "parallelism": f"pair-ordinal shards x{world}, " + (
-                       "RCCL all-reduce of pattern histogram" if args.backend == "nccl" or world == 1 else
-                       "gloo all-reduce of pattern histogram (host-staged rehearsal, ranks sharing GPUs)")},
+    return {
         "roofline": roofline,
         "roofline_em": em_roofline,
         "issue_gamma_kernels": issue,
         "hbm_headline_contract": headline,
-        "breakdown_ms": {"gamma": g_ms, "em_hist": h_ms, "em_final": f_ms, "score": score_ms,
-                         "block_device": block_kernel_ms, "block_wall": block_s * 1e3,
-                         "block_keys_wall": job.timings.get("block_keys_s", 0.0) * 1e3,
-                         "first_gammas_call_incl_column_decode": first_gammas_s * 1e3,
-                         **{f"host_wall_{k}": float(np.mean(v)) for k, v in host.items()}},
         "device_lds_per_block": job.ctx.lds_per_block(),
-        "input": "Arrow-backed string columns (pd.ArrowDtype(large_string)); keys, ids, ranks, clustering on the device",
         "deferred_pairs": job.ctx.gammas_deferred(),
         "exact_cells_per_column": dict(zip(names, job.ctx.gammas_exact_counts(len(names)))),
         # pairs whose level the blocking key implies (the filter reads nothing for that column there)
@@ -443,16 +522,6 @@ def main():
         "string_rates": rates,
         "em_at_scale": em_scale,
     }
-    if world == 1 and args.config == 2 and args.cfg5_steps > 0 and not args.share:
-        # cfg5's columns in the same run, after the headline (never the headline): the free-text address
-        # column's Levenshtein passes are the other workload the comparison kernels are tuned on
-        del job, R
-        out["cfg5_columns"] = cfg5_record(args, local)
-    emit(out)
-    if world > 1:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 def issue_counters(config):
