@@ -229,6 +229,34 @@ int spk_gammas(spk_ctx *ctx, int n_cols, const spk_column_program *cols, int n_w
                const int32_t *when_first_instr, const int32_t *when_n_instr, const int32_t *when_level,
                int n_instr, const spk_instr *instr, int n_operands, const spk_operand *operands,
                int n_lits, const int64_t *lit_offsets, const uint8_t *lit_utf8);
+/* spk_block for rules with residual predicates: the reference splices any join condition into
+ * `on {rule} {not_previous_rules}` (blocking.py:59-68, 145-154), so a rule may AND further conjuncts
+ * (`abs(l.age - r.age) < 5`, `levenshtein(l.a, r.a) <= 2`, `l.a != r.a`, `l.age < r.age` ...) onto its key equalities.
+ * rule_program[r] = index of rule r's predicate among the column programs given here (spk_gammas' argument
+ * format; a 2-level program with ELSE 0 whose level 1 means "the whole rule text is TRUE", i.e.
+ * ifnull(rule, false)), or -1 for a rule that is only its key equalities.  At most SPK_MAX_RESIDUAL_RULES
+ * programs (3^8 code patterns, inside the 2-byte code); the columns they read must be in the tables.
+ * A pair is emitted by rule r iff the link-type predicate holds, rule r is TRUE and every earlier rule is not
+ * TRUE (NULL does not emit and does not exclude).  Three steps: (a) spk_block's enumeration of the key candidates,
+ * where an earlier rule with a program does not exclude on its key; (b) the programs evaluated over those
+ * candidates by the comparison pass; (c) a stable device compaction of the pairs (and the second rule's view
+ * positions) by the codes, rule range by rule range, into fresh buffers.  The pair set becomes visible after
+ * (c); a failure before leaves none.  The codes of (b) are dropped: spk_gammas must follow as after spk_block.
+ * out_n_candidates_total: the key-candidate ordinals, the space the shards are cut on, as spk_block.
+ * With every rule_program[r] = -1 the result is spk_block's. */
+#define SPK_MAX_RESIDUAL_RULES 8
+int spk_block_residual(spk_ctx *ctx, int link_type, int n_rules, const int32_t *rule_symmetric,
+                       const int32_t *rule_program, int shard, int n_shards, int n_cols,
+                       const spk_column_program *cols, int n_when, const int32_t *when_first_instr,
+                       const int32_t *when_n_instr, const int32_t *when_level, int n_instr,
+                       const spk_instr *instr, int n_operands, const spk_operand *operands, int n_lits,
+                       const int64_t *lit_offsets, const uint8_t *lit_utf8, int64_t *out_n_pairs,
+                       int64_t *out_n_candidates_total);
+/* The last spk_block_residual: pairs its enumeration produced on this shard before the filter (-1: none yet),
+ * and, with timing on, the device milliseconds of its compaction (-1 = none): the sum over HIP event pairs around
+ * each rule's count kernel and scan and around the emit kernels; the host round trips between them (survivor
+ * counts, buffer allocation) are not in it. */
+int spk_block_residual_info(spk_ctx *ctx, int64_t *out_enumerated, double *out_filter_ms);
 /* Decode codes to int8 gamma columns, [count x K] row-major. */
 int spk_gammas_copy(spk_ctx *ctx, int64_t start, int64_t count, int8_t *out);
 /* Use a caller-provided gamma matrix (int8 [n x K], values -1..L_k-1). */

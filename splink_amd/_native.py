@@ -55,6 +55,7 @@ EXPORTS = [
     "spk_em_finalize_start", "spk_gammas_exact_ms", "spk_gammas_set_window", "spk_gammas_windows", "spk_gammas_set_streams", "spk_gammas_set_graph",
     "spk_gammas_graph_launches",
     "spk_gammas_set_lev_kernel",
+    "spk_block_residual", "spk_block_residual_info",
 ]
 TF_LIMBS = 14  # SPK_TF_LIMBS
 
@@ -280,6 +281,26 @@ class Context:
                                   ctypes.c_int(shard), ctypes.c_int(n_shards), ctypes.byref(n_pairs),
                                   ctypes.byref(n_total)), "spk_block")
         return n_pairs.value, n_total.value
+
+    def block_residual(self, link_type: int, symmetric, rule_program, args, shard: int = 0, n_shards: int = 1):
+        """spk_block_residual: rules with residual predicates.  rule_program[r]: index of rule r's hidden program
+        in `args` (gammas_args of the rules' predicates), -1 for a rule that is only its key equalities."""
+        sym = np.ascontiguousarray(symmetric, dtype=np.int32)
+        prog = np.ascontiguousarray(rule_program, dtype=np.int32)
+        assert len(prog) == len(sym)
+        n_pairs = ctypes.c_int64(0)
+        n_total = ctypes.c_int64(0)
+        check(self._lib.spk_block_residual(self._h, ctypes.c_int(link_type), ctypes.c_int(len(sym)), _ptr(sym),
+                                           _ptr(prog), ctypes.c_int(shard), ctypes.c_int(n_shards), *args[1],
+                                           ctypes.byref(n_pairs), ctypes.byref(n_total)), "spk_block_residual")
+        return n_pairs.value, n_total.value
+
+    def block_residual_info(self):
+        """(pairs the last block_residual enumerated before its filter, ms of its compaction kernels or -1)."""
+        n = ctypes.c_int64(0)
+        ms = ctypes.c_double(-1.0)
+        check(self._lib.spk_block_residual_info(self._h, ctypes.byref(n), ctypes.byref(ms)), "spk_block_residual_info")
+        return n.value, ms.value
 
     def pairs_count(self) -> int:
         n = ctypes.c_int64(0)

@@ -3,7 +3,9 @@
 `block_using_rules` keeps the reference's signature and semantics: one equi-join per rule,
 each excluding pairs an earlier rule produced, the link-type predicate (`l.uid < r.uid` for
 dedupe_only, source-table ordering for link_and_dedupe), and a cartesian product when there
-are no rules.  The pairs are generated on the GPU (spk_block) and stay there.
+are no rules.  A rule may AND a residual predicate onto its equalities (`l.a = r.a and abs(l.x - r.x) < 5`,
+compiler.compile_rules).  The pairs are generated on the GPU (spk_block; spk_block_residual when a rule has
+a residual) and stay there.
 """
 import pandas as pd
 

@@ -7,8 +7,13 @@
   substr / ifnull operands) combined with Kleene AND / OR / NOT.  An operand may be a Spark built-in
   over ONE record's columns (lower / upper / trim / ltrim / rtrim / concat / concat_ws / cast, nested,
   with substr / ifnull inside): a derived column (derived.py) evaluated once per row at ingest.
-* Blocking rules (blocking.py:95-160): conjunctions of equalities between an l-side and an
-  r-side key expression (a column, optionally under substr / lower / upper / trim).
+* Blocking rules (blocking.py:59-68, 95-160): a conjunction with at least one key term -- an equality
+  between an l-side and an r-side key expression (a column, optionally under substr / lower / upper /
+  trim) -- and, optionally, further conjuncts of any shape the predicate grammar above knows
+  (`abs(l.age - r.age) < 5`, `levenshtein(l.a, r.a) <= 2`, `l.a != r.a`, `l.age < r.age`, OR / NOT ...): the
+  rule's residual.  The key terms drive the device join; a rule with a residual is also compiled, whole, to a
+  hidden 2-level column program (`CASE WHEN <rule> THEN 1 ELSE 0 END` over `<col>_l` / `<col>_r`) that the
+  device evaluates per key candidate and filters on (compile_rules; at most MAX_RESIDUAL_RULES such rules a job).
 
 Anything else raises ValueError naming the unsupported construct, rather than guessing.
 """
@@ -438,6 +443,21 @@ def _guard_on_derived(tree: Case) -> Case:
     return Case(((guard, val),) + tuple(tree.whens[1:]), tree.else_)
 
 
+def _add_program(b: _ProgramBuilder, name: str, L: int, tree: Case):
+    """Compile one CASE into the builder; returns its spk_column_program tuple."""
+    first_when = len(b.whens)
+    for cond, val in tree.whens:
+        start = len(b.instrs)
+        b.predicate(cond)
+        n = len(b.instrs) - start
+        if n > 16:
+            raise ValueError(f"a WHEN condition of {name} is too long for the device (max 16 terms)")
+        b.whens.append((start, n, _level(val, L, "THEN value")))
+    if tree.else_ is None:
+        raise ValueError(f"case_expression for {name} has no ELSE branch")
+    return (L, _level(tree.else_, L, "ELSE value"), len(tree.whens), first_when)
+
+
 def compile_comparisons(settings: dict, schema: Schema) -> CompiledComparisons:
     b = _ProgramBuilder(schema)
     programs, names, n_levels = [], [], []
@@ -448,19 +468,13 @@ def compile_comparisons(settings: dict, schema: Schema) -> CompiledComparisons:
         if not isinstance(tree, Case):
             raise ValueError(f"case_expression for {name} is not a CASE expression")
         tree = _guard_on_derived(tree)
-        first_when = len(b.whens)
-        for cond, val in tree.whens:
-            start = len(b.instrs)
-            b.predicate(cond)
-            n = len(b.instrs) - start
-            if n > 16:
-                raise ValueError(f"a WHEN condition of {name} is too long for the device (max 16 terms)")
-            b.whens.append((start, n, _level(val, L, "THEN value")))
-        if tree.else_ is None:
-            raise ValueError(f"case_expression for {name} has no ELSE branch")
-        programs.append((L, _level(tree.else_, L, "ELSE value"), len(tree.whens), first_when))
+        programs.append(_add_program(b, name, L, tree))
         names.append(f"gamma_{name}")
         n_levels.append(L)
+    return _finish(b, programs, names, n_levels)
+
+
+def _finish(b: _ProgramBuilder, programs, names, n_levels) -> CompiledComparisons:
     prog = np.array(programs, dtype=N.PROGRAM_DTYPE)
     instrs = np.array(b.instrs, dtype=N.INSTR_DTYPE) if b.instrs else np.zeros(0, dtype=N.INSTR_DTYPE)
     wf = np.array([w[0] for w in b.whens], dtype=np.int32)
@@ -479,10 +493,16 @@ class KeyExpr:
     transforms: Tuple[tuple, ...] = ()   # ("substr", pos, len) | ("lower",) | ("upper",) | ("trim",)
 
 
+MAX_RESIDUAL_RULES = 8  # SPK_MAX_RESIDUAL_RULES: 3^8 patterns of the hidden programs, inside the 2-byte code
+
+
 @dataclass
 class RuleSpec:
     text: str
     terms: List[Tuple[KeyExpr, KeyExpr]]
+    # the conjuncts that are not key terms, AND-ed (an AST over l.<col> / r.<col>), or None
+    residual: Optional[object] = None
+    tree: Optional[object] = None   # the whole rule text, parsed
 
     @property
     def symmetric(self) -> bool:
@@ -511,15 +531,93 @@ def _key_expr(node, schema: Schema):
     return node.qualifier, KeyExpr(canon, tuple(reversed(transforms)))
 
 
+def _key_term(term, schema: Schema):
+    """(l KeyExpr, r KeyExpr) when the conjunct is a key term `l.<key expr> = r.<key expr>`, else None."""
+    if not (isinstance(term, Bin) and term.op == "="):
+        return None
+    sa, ka = _key_expr(term.a, schema)  # ValueError: not a key expression
+    sb, kb = _key_expr(term.b, schema)
+    if sa == sb:
+        return None
+    return (ka, kb) if sa == "l" else (kb, ka)
+
+
 def compile_rule(text: str, schema: Schema) -> RuleSpec:
-    terms = []
-    for term in conjuncts(parse(text)):
-        if not (isinstance(term, Bin) and term.op == "="):
-            raise ValueError(f"blocking rule {text!r}: only conjunctions of equalities are supported on the device "
-                             f"(found {term})")
-        sa, ka = _key_expr(term.a, schema)
-        sb, kb = _key_expr(term.b, schema)
-        if sa == sb:
-            raise ValueError(f"blocking rule {text!r}: each equality must compare an l.* with an r.* expression")
-        terms.append((ka, kb) if sa == "l" else (kb, ka))
-    return RuleSpec(text, terms)
+    tree = parse(text)
+    terms, rest, why = [], [], None
+    for term in conjuncts(tree):
+        try:
+            kt = _key_term(term, schema)
+        except ValueError as e:  # an equality of something else: part of the residual
+            kt, why = None, why or e
+        if kt is not None:
+            terms.append(kt)
+        else:
+            rest.append(term)
+    if not terms:
+        if why is not None and len(rest) == 1:
+            raise why
+        raise ValueError(f"blocking rule {text!r}: a rule needs at least one equality between an l.* and an r.* key "
+                         f"expression (a column, optionally under substr / lower / upper / trim) to join on; found "
+                         f"{', '.join(str(t) for t in rest)}")
+    residual = None
+    for term in rest:
+        residual = term if residual is None else Bin("and", residual, term)
+    return RuleSpec(text, terms, residual, tree)
+
+
+def _unqualify(node, text: str):
+    """A rule's AST in the comparison grammar: l.x -> x_l, r.x -> x_r."""
+    if isinstance(node, Col):
+        if node.qualifier not in ("l", "r"):
+            raise ValueError(f"blocking rule {text!r}: column {node.name!r} must be qualified as l.{node.name} or "
+                             f"r.{node.name}")
+        return Col(f"{node.name}_{node.qualifier}", "")
+    if isinstance(node, Func):
+        return Func(node.name, tuple(_unqualify(a, text) for a in node.args))
+    if isinstance(node, Bin):
+        return Bin(node.op, _unqualify(node.a, text), _unqualify(node.b, text))
+    if isinstance(node, Un):
+        return Un(node.op, _unqualify(node.a, text))
+    if isinstance(node, IsNull):
+        return IsNull(_unqualify(node.a, text), node.negated)
+    if isinstance(node, Case):
+        return Case(tuple((_unqualify(c, text), _unqualify(v, text)) for c, v in node.whens),
+                    None if node.else_ is None else _unqualify(node.else_, text))
+    return node
+
+
+def compile_rules(texts: List[str], schema: Schema):
+    """The rules of one job: (specs, rule_program, hidden).  `hidden` holds one 2-level program per rule with a
+    residual -- the whole rule text as `CASE WHEN <rule> THEN 1 ELSE 0 END`, so level 1 is ifnull(rule, false) --
+    and rule_program[r] is rule r's index among them, -1 for a rule that is only key terms; hidden is None when no
+    rule has a residual.  A pair key-matching an earlier rule with a residual is excluded only if that whole rule
+    is TRUE for it (blocking.py:59-68), which is why the program is the whole rule and not the residual alone."""
+    specs = [compile_rule(t, schema) for t in texts]
+    rule_program = [-1] * len(specs)
+    if not any(s.residual is not None for s in specs):
+        return specs, rule_program, None
+    if sum(s.residual is not None for s in specs) > MAX_RESIDUAL_RULES:
+        raise ValueError(f"at most {MAX_RESIDUAL_RULES} blocking rules of one job may carry a residual predicate "
+                         f"(conjuncts beyond l.x = r.y equalities)")
+    b = _ProgramBuilder(schema)
+    programs, names = [], []
+    for r, spec in enumerate(specs):
+        if spec.residual is None:
+            continue
+        for lexpr, rexpr in spec.terms:
+            # the predicate evaluates the key equality by the comparison grammar's rules; the join by the key's.
+            # They agree for same-form columns; a number column under string functions or a string compared with a
+            # number is keyed on the host by rules the grammar does not restate
+            fl, fr = schema.form(lexpr.column), schema.form(rexpr.column)
+            if fl != fr or (fl == "num" and (lexpr.transforms or rexpr.transforms)):
+                raise ValueError(f"blocking rule {spec.text!r}: the key term on {lexpr.column} / {rexpr.column} "
+                                 f"(mixed types or a transformed number) cannot be combined with a residual predicate")
+        try:
+            case = Case(((_unqualify(spec.tree, spec.text), Lit(1)),), Lit(0))
+            programs.append(_add_program(b, f"blocking rule {spec.text!r}", 2, case))
+        except ValueError as e:
+            raise ValueError(f"blocking rule {spec.text!r}: {e}") from None
+        rule_program[r] = len(programs) - 1
+        names.append(f"rule_{r}")
+    return specs, rule_program, _finish(b, programs, names, [2] * len(programs))

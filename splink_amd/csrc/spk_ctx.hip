@@ -439,6 +439,8 @@ void spk_ctx_destroy(spk_ctx *ctx) {
     }
     if (ctx->gexec) (void)hipGraphExecDestroy(ctx->gexec);
     if (ctx->graph) (void)hipGraphDestroy(ctx->graph);
+    if (ctx->res_ev0) (void)hipEventDestroy(ctx->res_ev0);
+    if (ctx->res_ev1) (void)hipEventDestroy(ctx->res_ev1);
     if (ctx->ev_info) (void)hipEventDestroy(ctx->ev_info);
     if (ctx->ev_stats) (void)hipEventDestroy(ctx->ev_stats);
     if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);

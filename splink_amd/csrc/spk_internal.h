@@ -238,6 +238,12 @@ struct spk_ctx {
     int n_views = 0;
     spk::DevBuf<int32_t> pvl, pvr;     // view positions of pairs [pv_base, n_pairs)
     int64_t pv_base = 0;
+    // the last spk_block_residual: key candidates it enumerated on this shard (after the link-type predicate and
+    // the exclusion by earlier key-only rules), -1 = none yet; device milliseconds of its compaction (timing on:
+    // the sum over HIP event pairs around each rule's count kernel + scan and around the emit kernels), -1 = none
+    int64_t res_enumerated = -1;
+    hipEvent_t res_ev0 = nullptr, res_ev1 = nullptr;
+    double res_filter_ms = -1.0;
 
     // packed comparison-vector codes
     spk::DevBuf<uint8_t> codes;

@@ -21,7 +21,7 @@ import pandas as pd
 from . import _native as N
 from . import distributed as D
 from . import table as T
-from .compiler import CompiledComparisons, Schema, compile_comparisons, compile_rule
+from .compiler import CompiledComparisons, Schema, compile_comparisons, compile_rules
 
 
 N_HEAD = 5  # spk_em_finalize statistics header: [Σmp, rows, non-null rows, Σ ln(..), non-null ln rows]
@@ -437,8 +437,10 @@ class Job:
             self.ctx.table_set_key(0, 0, 0, np.zeros(n0, dtype=np.int64))
             self.ctx.table_set_key(self.r_side(), 0, 1, np.zeros(nr, dtype=np.int64))
             symmetric = [1]
-        for r, text in enumerate(rules):
-            spec = compile_rule(text, self.schema)
+        # rules with a residual predicate (`l.a = r.a and abs(l.x - r.x) < 5`): the whole rule as a hidden device
+        # program per such rule (compiler.compile_rules); none: today's spk_block path
+        specs, rule_program, hidden = compile_rules(list(rules), self.schema)
+        for r, spec in enumerate(specs):
             terms = [self._term(r, i, lexpr, rexpr, lexpr == rexpr) for i, (lexpr, rexpr) in enumerate(spec.terms)]
             self.ctx.key_build(r, terms)
             symmetric.append(1 if spec.symmetric else 0)
@@ -449,10 +451,27 @@ class Job:
             self.perm = [p0] + ([p1] if p1 is not None else [])
             self._views, self._host_cols, self._col_index, self._prog_cache = {}, {}, {}, {}
         t_keys = time.perf_counter()
-        self.n_pairs, self.n_candidates = self.ctx.block(N.LINK_TYPES[self.link_type], symmetric, self.shard,
-                                                         self.n_shards)
+        if hidden is None:
+            self.n_pairs, self.n_candidates = self.ctx.block(N.LINK_TYPES[self.link_type], symmetric, self.shard,
+                                                             self.n_shards)
+        else:
+            # the columns the predicates read go to the device now (after the clustering, which reset the column
+            # registry) and stay registered: a later gammas() reuses them
+            for name, node in hidden.derived.items():
+                self.add_derived(name, node)
+            index = {k: self.column_index(*k) for k in hidden.columns}
+            lit_off, lit_bytes = hidden.literal_buffers()
+            args = N.Context.gammas_args(hidden.programs, hidden.when_first, hidden.when_n, hidden.when_level,
+                                         hidden.instrs, hidden.native_operands(index), lit_off, lit_bytes)
+            t_cols = time.perf_counter()
+            self.n_pairs, self.n_candidates = self.ctx.block_residual(
+                N.LINK_TYPES[self.link_type], symmetric, rule_program, args, self.shard, self.n_shards)
+            # the predicates' columns are uploaded here only because no gammas() has done it yet: their time is kept
+            # apart, so that block_pairs_s stays the device blocking call alone (enumerate + evaluate + filter)
+            self.timings["block_residual_cols_s"] = t_cols - t_keys
+            t_keys_end = t_cols
         self.timings["block_keys_s"] = t_keys - t_start
-        self.timings["block_pairs_s"] = time.perf_counter() - t_keys
+        self.timings["block_pairs_s"] = time.perf_counter() - (t_keys if hidden is None else t_keys_end)
         self._pairs_host = None
         self.codes_token = None
         return self.n_pairs
