@@ -7,15 +7,12 @@
 // Each ordinal decodes to one (l, r) row pair; the earlier-rule exclusion and the link-type
 // predicate are applied per pair.  Two passes (count, emit) keep the output in ordinal order,
 // so pair order is deterministic and independent of the grid.
-#include <cstring>
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 #include "spk_internal.h"
+#include "spk_prim.h"
 
 namespace spk {
 
@@ -282,12 +279,7 @@ static int sort_view(spk_ctx *ctx, int64_t n, const int64_t *d_key, const int64_
     k_make_sort_keys<<<(unsigned)std::min<int64_t>((n + 255) / 256, 4 * (int64_t)ctx->n_cu), 256, 0, ctx->stream>>>(
         n, d_key, d_rank, k_in.p, r_in.p, cnt.p);
     SPK_HIP(hipGetLastError());
-    size_t bytes = 0;
-    SPK_HIP(rocprim::radix_sort_pairs(nullptr, bytes, k_in.p, v.keys.p, r_in.p, v.rows.p, (size_t)n, 0, 64,
-                                      ctx->stream));
-    SPK_TRY(tmp.alloc(bytes + 1));
-    SPK_HIP(rocprim::radix_sort_pairs(tmp.p, bytes, k_in.p, v.keys.p, r_in.p, v.rows.p, (size_t)n, 0, 64,
-                                      ctx->stream));
+    SPK_TRY(sort_pairs_u64(ctx->stream, tmp, k_in.p, v.keys.p, r_in.p, v.rows.p, n));
     unsigned long long h = 0;
     SPK_HIP(hipMemcpyAsync(&h, cnt.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     SPK_HIP(hipStreamSynchronize(ctx->stream));
@@ -295,24 +287,42 @@ static int sort_view(spk_ctx *ctx, int64_t n, const int64_t *d_key, const int64_
     return SPK_OK;
 }
 
-template <typename T>
-static int exclusive_scan(spk_ctx *ctx, const T *in, T *out, int64_t n, DevBuf<uint8_t> &tmp) {
-    if (n == 0) return SPK_OK;
-    size_t bytes = 0;
-    SPK_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, (T)0, (size_t)n, rocprim::plus<T>(), ctx->stream));
-    SPK_TRY(tmp.alloc(bytes + 1));
-    SPK_HIP(rocprim::exclusive_scan(tmp.p, bytes, in, out, (T)0, (size_t)n, rocprim::plus<T>(), ctx->stream));
+// Counts, their exclusive prefix sums and their total.  Three things here have this shape: the head flags of a
+// sorted view (prefix: the block of every position, total: the number of blocks), a rule's candidates per block
+// (prefix: the first ordinal of every block), and the pairs a compaction pass keeps per chunk (prefix: where the
+// emit pass writes every chunk's pairs).
+struct CountScan {
+    DevBuf<int64_t> count, off;  // [n + 1]: count[n] is a zero that is scanned with the rest, so off[n] is the total
+    int64_t n = 0, total = 0;
+    int alloc(spk_ctx *ctx, int64_t n_counts) {
+        n = n_counts;
+        SPK_TRY(count.alloc((size_t)n + 1));
+        SPK_TRY(off.alloc((size_t)n + 1));
+        SPK_HIP(hipMemsetAsync(count.p + n, 0, sizeof(int64_t), ctx->stream));
+        return SPK_OK;
+    }
+};
+
+// Enqueued behind the kernel that writes S.count[0 .. n): the scan, then the read-back of the total.  Returns with
+// the stream synchronised; `scanned` (optional) is recorded between the scan and the read-back.
+static int scan_total(spk_ctx *ctx, CountScan &S, DevBuf<uint8_t> &tmp, hipEvent_t scanned = nullptr) {
+    SPK_TRY(exclusive_scan(ctx->stream, tmp, S.count.p, S.off.p, S.n + 1));
+    if (scanned) SPK_HIP(hipEventRecord(scanned, ctx->stream));
+    SPK_HIP(hipMemcpyAsync(&S.total, S.off.p + S.n, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    SPK_HIP(hipStreamSynchronize(ctx->stream));
     return SPK_OK;
 }
 
 struct RulePlan {
     SortedView L, R;
-    DevBuf<int64_t> bstart, bstartR, bnR, cand, cand_off;
+    DevBuf<int64_t> bstart, bstartR, bnR;
+    CountScan cand;  // candidates per block; cand.total: the rule's candidate ordinals
     // by view position: rank (l, r), then the keys of the earlier rules (l then r per rule)
     DevBuf<int64_t> bypos;
     const int64_t *rankL = nullptr, *rankR = nullptr;
     const int64_t *keyL[MAX_RULES] = {}, *keyR[MAX_RULES] = {};
-    int64_t B = 0, T = 0;
+    int n_excl = 0;  // earlier rules whose keys are in keyL / keyR
+    int64_t B = 0;
     int tri = 1;
 };
 
@@ -325,39 +335,24 @@ static int plan_rule(spk_ctx *ctx, int rule, bool symmetric, RulePlan &P, DevBuf
     SPK_TRY(sort_view(ctx, tl.n, tl.key[0][rule]->p, link_only ? nullptr : rankL, P.L, tmp));
     if (!P.tri) SPK_TRY(sort_view(ctx, tr.n, tr.key[1][rule]->p, nullptr, P.R, tmp));
     int64_t n = P.L.n_valid;
-    P.B = 0;
-    P.T = 0;
     if (n == 0) return SPK_OK;
-    DevBuf<int64_t> flag, pos;
-    SPK_TRY(flag.alloc((size_t)n));
-    SPK_TRY(pos.alloc((size_t)n));
+    CountScan heads;
+    SPK_TRY(heads.alloc(ctx, n));
     unsigned g = (unsigned)((n + 255) / 256);
-    k_heads<<<g, 256, 0, ctx->stream>>>(n, P.L.keys.p, flag.p);
-    SPK_TRY(exclusive_scan<int64_t>(ctx, flag.p, pos.p, n, tmp));
-    int64_t last[2];
-    SPK_HIP(hipMemcpyAsync(&last[0], pos.p + n - 1, 8, hipMemcpyDeviceToHost, ctx->stream));
-    SPK_HIP(hipMemcpyAsync(&last[1], flag.p + n - 1, 8, hipMemcpyDeviceToHost, ctx->stream));
-    SPK_HIP(hipStreamSynchronize(ctx->stream));
-    int64_t B = last[0] + last[1];
-    P.B = B;
+    k_heads<<<g, 256, 0, ctx->stream>>>(n, P.L.keys.p, heads.count.p);
+    SPK_TRY(scan_total(ctx, heads, tmp));
+    const int64_t B = P.B = heads.total;
     SPK_TRY(P.bstart.alloc((size_t)B + 1));
     SPK_TRY(P.bstartR.alloc((size_t)B + 1));
     SPK_TRY(P.bnR.alloc((size_t)B + 1));
-    SPK_TRY(P.cand.alloc((size_t)B + 1));
-    SPK_TRY(P.cand_off.alloc((size_t)B + 1));
-    k_starts<<<g, 256, 0, ctx->stream>>>(n, flag.p, pos.p, P.bstart.p);
+    SPK_TRY(P.cand.alloc(ctx, B));
+    k_starts<<<g, 256, 0, ctx->stream>>>(n, heads.count.p, heads.off.p, P.bstart.p);
     SPK_HIP(hipMemcpyAsync(P.bstart.p + B, &n, 8, hipMemcpyHostToDevice, ctx->stream));
     k_cand<<<(unsigned)((B + 255) / 256), 256, 0, ctx->stream>>>(B, P.bstart.p, P.tri, P.L.keys.p,
                                                                  P.tri ? nullptr : P.R.keys.p, P.R.n_valid,
-                                                                 P.bstartR.p, P.bnR.p, P.cand.p);
+                                                                 P.bstartR.p, P.bnR.p, P.cand.count.p);
     SPK_HIP(hipGetLastError());
-    SPK_TRY(exclusive_scan<int64_t>(ctx, P.cand.p, P.cand_off.p, B, tmp));
-    int64_t lc[2];
-    SPK_HIP(hipMemcpyAsync(&lc[0], P.cand_off.p + B - 1, 8, hipMemcpyDeviceToHost, ctx->stream));
-    SPK_HIP(hipMemcpyAsync(&lc[1], P.cand.p + B - 1, 8, hipMemcpyDeviceToHost, ctx->stream));
-    SPK_HIP(hipStreamSynchronize(ctx->stream));
-    P.T = lc[0] + lc[1];
-    return SPK_OK;
+    return scan_total(ctx, P.cand, tmp);
 }
 
 // Position-ordered copies of what k_enum reads per candidate pair: ranks (dedupe / link_and_dedupe) and
@@ -389,6 +384,7 @@ static int build_by_position(spk_ctx *ctx, const std::vector<int> &excl, RulePla
         P.keyL[j] = by_pos(nL, P.L.rows.p, tl.key[0][excl[j]]->p);
         P.keyR[j] = by_pos(nR, rowsR, tr.key[1][excl[j]]->p);
     }
+    P.n_excl = rule;
     SPK_HIP(hipGetLastError());
     return SPK_OK;
 }
@@ -397,6 +393,33 @@ static void release_by_position(RulePlan &P) {
     P.bypos.release();
     P.rankL = P.rankR = nullptr;
     for (int j = 0; j < MAX_RULES; ++j) P.keyL[j] = P.keyR[j] = nullptr;
+    P.n_excl = 0;
+}
+
+// k_enum's arguments for the ordinals [q0, q1) of a rule whose by-position copies are built.  The count pass
+// adds chunk_count, the emit pass chunk_off and the outputs: everything both passes must agree on is set here.
+static EnumArgs enum_args(spk_ctx *ctx, const RulePlan &P, int64_t q0, int64_t q1) {
+    EnumArgs A{};
+    A.q0 = q0;
+    A.q1 = q1;
+    A.B = P.B;
+    A.cand_off = P.cand.off.p;
+    A.bstart = P.bstart.p;
+    A.bstartR = P.bstartR.p;
+    A.bnR = P.bnR.p;
+    A.rowsL = P.L.rows.p;
+    A.rowsR = P.tri ? P.L.rows.p : P.R.rows.p;
+    A.rankL = P.rankL;
+    A.rankR = P.rankR;
+    A.tri = P.tri;
+    A.rank_filter = ctx->link_type == SPK_LINK_ONLY ? 0 : 1;
+    A.null_div = ctx->table[0].null_div;
+    A.rule = P.n_excl;
+    for (int j = 0; j < P.n_excl; ++j) {
+        A.keys.keyL[j] = P.keyL[j];
+        A.keys.keyR[j] = P.keyR[j];
+    }
+    return A;
 }
 
 // ---- residual predicates: stable compaction of one rule's pair range by the hidden programs' codes -------
@@ -508,18 +531,11 @@ static int block_rules(spk_ctx *ctx, int link_type, int n_rules, const int32_t *
     }
     SPK_TRY(ctx->begin(K_BLOCK));
     DevBuf<uint8_t> tmp;
-    std::vector<RulePlan *> plans;
-    struct Guard {
-        std::vector<RulePlan *> &v;
-        ~Guard() {
-            for (RulePlan *p : v) delete p;
-        }
-    } guard{plans};
+    std::vector<RulePlan> plans(n_rules);
     int64_t total = 0;
     for (int r = 0; r < n_rules; ++r) {
-        plans.push_back(new RulePlan());
-        SPK_TRY(plan_rule(ctx, r, rule_symmetric[r] != 0, *plans.back(), tmp));
-        total += plans.back()->T;
+        SPK_TRY(plan_rule(ctx, r, rule_symmetric[r] != 0, plans[r], tmp));
+        total += plans[r].cand.total;
     }
     int64_t g_lo = (int64_t)((__int128)total * shard / n_shards);
     int64_t g_hi = (int64_t)((__int128)total * (shard + 1) / n_shards);
@@ -528,107 +544,56 @@ static int block_rules(spk_ctx *ctx, int link_type, int n_rules, const int32_t *
     for (int r = 0; r < n_rules; ++r)
         for (int j = 0; j < r; ++j)
             if (!rule_program || rule_program[j] < 0) excl[r].push_back(j);
-    EnumArgs base{};
     // count pass
-    std::vector<DevBuf<int64_t> *> counts(n_rules, nullptr), offs(n_rules, nullptr);
-    struct G2 {
-        std::vector<DevBuf<int64_t> *> &a, &b;
-        ~G2() {
-            for (auto *x : a) delete x;
-            for (auto *x : b) delete x;
-        }
-    } g2{counts, offs};
-    std::vector<int64_t> rule_lo(n_rules), rule_hi(n_rules), rule_base(n_rules), n_chunks(n_rules);
+    struct Pass {
+        int64_t lo = 0, hi = 0;  // this shard's ordinals of the rule (rule-local)
+        CountScan chunks;        // pairs kept per EN_CHUNK ordinals; n = 0: the shard has none of the rule
+    };
+    std::vector<Pass> pass(n_rules);
+    std::vector<int64_t> rule_base(n_rules);
     int64_t acc = 0, n_out = 0;
     for (int r = 0; r < n_rules; ++r) {
-        RulePlan &P = *plans[r];
-        int64_t lo = std::max<int64_t>(g_lo - acc, 0), hi = std::min<int64_t>(g_hi - acc, P.T);
-        acc += P.T;
-        rule_lo[r] = lo;
-        rule_hi[r] = hi;
-        n_chunks[r] = hi > lo ? (hi - lo + EN_CHUNK - 1) / EN_CHUNK : 0;
+        RulePlan &P = plans[r];
+        Pass &Q = pass[r];
+        Q.lo = std::max<int64_t>(g_lo - acc, 0);
+        Q.hi = std::min<int64_t>(g_hi - acc, P.cand.total);
+        acc += P.cand.total;
         rule_base[r] = n_out;
-        if (!n_chunks[r]) continue;
-        counts[r] = new DevBuf<int64_t>();
-        offs[r] = new DevBuf<int64_t>();
+        if (Q.hi <= Q.lo) continue;
         SPK_TRY(build_by_position(ctx, excl[r], P));
-        SPK_TRY(counts[r]->alloc((size_t)n_chunks[r]));
-        SPK_TRY(offs[r]->alloc((size_t)n_chunks[r]));
-        EnumArgs A = base;
-        A.q0 = lo;
-        A.q1 = hi;
-        A.B = P.B;
-        A.cand_off = P.cand_off.p;
-        A.bstart = P.bstart.p;
-        A.bstartR = P.bstartR.p;
-        A.bnR = P.bnR.p;
-        A.rowsL = P.L.rows.p;
-        A.rowsR = P.tri ? P.L.rows.p : P.R.rows.p;
-        A.rankL = P.rankL;
-        A.rankR = P.rankR;
-        for (int j = 0; j < (int)excl[r].size(); ++j) {
-            A.keys.keyL[j] = P.keyL[j];
-            A.keys.keyR[j] = P.keyR[j];
-        }
-        A.tri = P.tri;
-        A.rank_filter = link_only ? 0 : 1;
-        A.null_div = tl.null_div;
-        A.rule = (int)excl[r].size();
-        A.chunk_count = counts[r]->p;
-        k_enum<false><<<(unsigned)n_chunks[r], EN_THREADS, 0, ctx->stream>>>(A);
+        SPK_TRY(Q.chunks.alloc(ctx, (Q.hi - Q.lo + EN_CHUNK - 1) / EN_CHUNK));
+        EnumArgs A = enum_args(ctx, P, Q.lo, Q.hi);
+        A.chunk_count = Q.chunks.count.p;
+        k_enum<false><<<(unsigned)Q.chunks.n, EN_THREADS, 0, ctx->stream>>>(A);
         SPK_HIP(hipGetLastError());
-        SPK_TRY(exclusive_scan<int64_t>(ctx, counts[r]->p, offs[r]->p, n_chunks[r], tmp));
-        SPK_HIP(hipStreamSynchronize(ctx->stream));  // the copies are freed next: the pass must be done
+        SPK_TRY(scan_total(ctx, Q.chunks, tmp));  // synchronises: the pass is done, its copies can be freed
         release_by_position(P);
-        int64_t lc[2];
-        SPK_HIP(hipMemcpyAsync(&lc[0], offs[r]->p + n_chunks[r] - 1, 8, hipMemcpyDeviceToHost, ctx->stream));
-        SPK_HIP(hipMemcpyAsync(&lc[1], counts[r]->p + n_chunks[r] - 1, 8, hipMemcpyDeviceToHost, ctx->stream));
-        SPK_HIP(hipStreamSynchronize(ctx->stream));
-        n_out += lc[0] + lc[1];
+        n_out += Q.chunks.total;
     }
     SPK_REQUIRE(n_out < (int64_t)1 << 40, SPK_E_LIMIT, "spk_block: pair count too large");
     SPK_TRY(ctx->pl.alloc((size_t)n_out + 1));
     SPK_TRY(ctx->pr.alloc((size_t)n_out + 1));
     // rules 1 .. MAX_VIEWS-1 keep their row order (view) and emit their pairs' view positions
     const int n_views = std::min(n_rules, MAX_VIEWS) - 1;
-    const int64_t pv_base = n_views > 0 ? rule_base[1] : n_out;
-    ctx->n_views = 0;
-    ctx->pv_base = pv_base;
+    const int64_t pv_base = view_pair_base(rule_base, n_out);
+    ctx->n_views = 0;  // no view until this call's are in place (set_rule_ranges)
     if (n_views > 0 && n_out > pv_base) {
         SPK_TRY(ctx->pvl.alloc((size_t)(n_out - pv_base) + 1));
         SPK_TRY(ctx->pvr.alloc((size_t)(n_out - pv_base) + 1));
     }
     for (int r = 0; r < n_rules; ++r) {
-        if (!n_chunks[r]) continue;
-        RulePlan &P = *plans[r];
+        Pass &Q = pass[r];
+        if (!Q.chunks.n) continue;
+        RulePlan &P = plans[r];
         SPK_TRY(build_by_position(ctx, excl[r], P));
-        EnumArgs A = base;
-        A.q0 = rule_lo[r];
-        A.q1 = rule_hi[r];
-        A.B = P.B;
-        A.cand_off = P.cand_off.p;
-        A.bstart = P.bstart.p;
-        A.bstartR = P.bstartR.p;
-        A.bnR = P.bnR.p;
-        A.rowsL = P.L.rows.p;
-        A.rowsR = P.tri ? P.L.rows.p : P.R.rows.p;
-        A.rankL = P.rankL;
-        A.rankR = P.rankR;
-        for (int j = 0; j < (int)excl[r].size(); ++j) {
-            A.keys.keyL[j] = P.keyL[j];
-            A.keys.keyR[j] = P.keyR[j];
-        }
-        A.tri = P.tri;
-        A.rank_filter = link_only ? 0 : 1;
-        A.null_div = tl.null_div;
-        A.rule = (int)excl[r].size();
-        A.chunk_off = offs[r]->p;
+        EnumArgs A = enum_args(ctx, P, Q.lo, Q.hi);
+        A.chunk_off = Q.chunks.off.p;
         A.out_l = ctx->pl.p + rule_base[r];
         A.out_r = ctx->pr.p + rule_base[r];
         const bool view = r >= 1 && r <= n_views;
         A.out_vl = view ? ctx->pvl.p + (rule_base[r] - pv_base) : nullptr;
         A.out_vr = view ? ctx->pvr.p + (rule_base[r] - pv_base) : nullptr;
-        k_enum<true><<<(unsigned)n_chunks[r], EN_THREADS, 0, ctx->stream>>>(A);
+        k_enum<true><<<(unsigned)Q.chunks.n, EN_THREADS, 0, ctx->stream>>>(A);
         SPK_HIP(hipGetLastError());
         SPK_HIP(hipStreamSynchronize(ctx->stream));
         release_by_position(P);
@@ -637,27 +602,17 @@ static int block_rules(spk_ctx *ctx, int link_type, int n_rules, const int32_t *
     SPK_HIP(hipStreamSynchronize(ctx->stream));
     for (int r = 1; r <= n_views; ++r) {
         RuleView &v = ctx->views[r];
-        RulePlan &P = *plans[r];
-        take_buf(v.rowsL, P.L.rows);
+        RulePlan &P = plans[r];
+        v.rowsL = std::move(P.L.rows);
         v.nL = P.L.n_valid;
         v.tri = P.tri != 0;
-        if (!v.tri) take_buf(v.rowsR, P.R.rows);
+        if (!v.tri) v.rowsR = std::move(P.R.rows);
         else v.rowsR.release();
         v.nR = v.tri ? v.nL : P.R.n_valid;
-        v.pair_lo = rule_base[r];
-        v.pair_hi = r + 1 < n_rules ? rule_base[r + 1] : n_out;
     }
-    ctx->n_views = n_views;
     ctx->pair_terms.assign(ctx->rule_terms, ctx->rule_terms + n_rules);
-    ctx->pair_rule_lo.assign(rule_base.begin(), rule_base.end());
-    ctx->pair_rule_hi.resize(n_rules);
-    for (int r = 0; r < n_rules; ++r) ctx->pair_rule_hi[r] = r + 1 < n_rules ? rule_base[r + 1] : n_out;
-    ctx->n_pairs = n_out;
-    ctx->pairs_valid = true;
-    ctx->pairs_epoch++;
-    ctx->tf_mp.release();  // a kept tf result describes the old pair set (spk_tf_copy refuses it)
-    ctx->tf_count = -1;
-    ctx->codes_valid = false;
+    ctx->pairs_replaced(n_out);
+    ctx->set_rule_ranges(rule_base, n_out);
     if (out_n_pairs) *out_n_pairs = n_out;
     if (out_n_candidates_total) *out_n_candidates_total = total;
     return SPK_OK;
@@ -675,9 +630,7 @@ struct PairsCommit {
     spk_ctx *ctx;
     bool done = false;
     ~PairsCommit() {
-        if (done) return;
-        ctx->pairs_valid = false;
-        ctx->codes_valid = false;
+        if (!done) ctx->pairs_dropped();
     }
 };
 }  // namespace
@@ -707,7 +660,7 @@ extern "C" int spk_block_residual(spk_ctx *ctx, int link_type, int n_rules, cons
     for (int k = 0; any && k < n_cols; ++k)
         SPK_REQUIRE(cols[k].n_levels == 2 && cols[k].else_level == 0, SPK_E_INVALID,
                     "spk_block_residual: a rule's predicate is a 2-level program (level 1: the rule is TRUE)");
-    ctx->pairs_valid = false;
+    ctx->pairs_dropped();  // (the codes go with the first stage's pair set at the latest)
     PairsCommit commit{ctx};
     // ---- a. enumerate: the key candidates, excluded only by earlier rules without a predicate
     int64_t n_enum = 0, total = 0;
@@ -756,16 +709,9 @@ extern "C" int spk_block_residual(spk_ctx *ctx, int link_type, int n_rules, cons
     };
     const int64_t old_pv_base = ctx->pv_base;
     const int n_views = ctx->n_views;
-    std::vector<DevBuf<int64_t> *> counts(n_rules, nullptr), offs(n_rules, nullptr);
-    struct G2 {
-        std::vector<DevBuf<int64_t> *> &a, &b;
-        ~G2() {
-            for (auto *x : a) delete x;
-            for (auto *x : b) delete x;
-        }
-    } g2{counts, offs};
-    std::vector<int64_t> new_base(n_rules), n_chunks(n_rules);
-    auto args_of = [&](int r) {
+    // k_residual_filter's arguments for rule r's enumerated range: what both passes must agree on.  The count pass
+    // adds chunk_count, the emit pass chunk_off, the outputs and the view positions.
+    auto filter_args = [&](int r) {
         ResidualFilterArgs A{};
         A.lo = ctx->pair_rule_lo[r];
         A.hi = ctx->pair_rule_hi[r];
@@ -776,45 +722,38 @@ extern "C" int spk_block_residual(spk_ctx *ctx, int link_type, int n_rules, cons
         A.in_r = ctx->pr.p;
         return A;
     };
+    std::vector<CountScan> chunks(n_rules);  // survivors per RF_CHUNK ordinals; n = 0: the rule enumerated nothing
+    std::vector<int64_t> new_base(n_rules);
     int64_t n_out = 0;
     for (int r = 0; r < n_rules; ++r) {
         const int64_t lo = ctx->pair_rule_lo[r], hi = ctx->pair_rule_hi[r];
-        n_chunks[r] = hi > lo ? (hi - lo + RF_CHUNK - 1) / RF_CHUNK : 0;
         new_base[r] = n_out;
-        if (!n_chunks[r]) continue;
-        counts[r] = new DevBuf<int64_t>();
-        offs[r] = new DevBuf<int64_t>();
-        SPK_TRY(counts[r]->alloc((size_t)n_chunks[r]));
-        SPK_TRY(offs[r]->alloc((size_t)n_chunks[r]));
-        ResidualFilterArgs A = args_of(r);
-        A.chunk_count = counts[r]->p;
+        if (hi <= lo) continue;
+        SPK_TRY(chunks[r].alloc(ctx, (hi - lo + RF_CHUNK - 1) / RF_CHUNK));
+        ResidualFilterArgs A = filter_args(r);
+        A.chunk_count = chunks[r].count.p;
         if (ctx->timing) SPK_HIP(hipEventRecord(ctx->res_ev0, ctx->stream));
-        k_residual_filter<false><<<(unsigned)n_chunks[r], RF_THREADS, 0, ctx->stream>>>(A);
+        k_residual_filter<false><<<(unsigned)chunks[r].n, RF_THREADS, 0, ctx->stream>>>(A);
         SPK_HIP(hipGetLastError());
-        SPK_TRY(exclusive_scan<int64_t>(ctx, counts[r]->p, offs[r]->p, n_chunks[r], tmp));
-        if (ctx->timing) SPK_HIP(hipEventRecord(ctx->res_ev1, ctx->stream));
-        int64_t lc[2];
-        SPK_HIP(hipMemcpyAsync(&lc[0], offs[r]->p + n_chunks[r] - 1, 8, hipMemcpyDeviceToHost, ctx->stream));
-        SPK_HIP(hipMemcpyAsync(&lc[1], counts[r]->p + n_chunks[r] - 1, 8, hipMemcpyDeviceToHost, ctx->stream));
-        SPK_HIP(hipStreamSynchronize(ctx->stream));
+        SPK_TRY(scan_total(ctx, chunks[r], tmp, ctx->timing ? ctx->res_ev1 : nullptr));
         SPK_TRY(lap());
-        n_out += lc[0] + lc[1];
+        n_out += chunks[r].total;
     }
     SPK_REQUIRE(n_out <= n_enum, SPK_E_STATE, "spk_block_residual: survivor count");
     // fresh buffers (both pair sets are held until the swap), rule 1's view positions with the same offsets
     DevBuf<int32_t> npl, npr, npvl, npvr;
     SPK_TRY(npl.alloc((size_t)n_out + 1));
     SPK_TRY(npr.alloc((size_t)n_out + 1));
-    const int64_t pv_base = n_views > 0 ? new_base[1] : n_out;
+    const int64_t pv_base = view_pair_base(new_base, n_out);
     if (n_views > 0 && n_out > pv_base) {
         SPK_TRY(npvl.alloc((size_t)(n_out - pv_base) + 1));
         SPK_TRY(npvr.alloc((size_t)(n_out - pv_base) + 1));
     }
     if (ctx->timing) SPK_HIP(hipEventRecord(ctx->res_ev0, ctx->stream));
     for (int r = 0; r < n_rules; ++r) {
-        if (!n_chunks[r]) continue;
-        ResidualFilterArgs A = args_of(r);
-        A.chunk_off = offs[r]->p;
+        if (!chunks[r].n) continue;
+        ResidualFilterArgs A = filter_args(r);
+        A.chunk_off = chunks[r].off.p;
         A.out_l = npl.p + new_base[r];
         A.out_r = npr.p + new_base[r];
         const bool view = r >= 1 && r <= n_views && npvl.p && ctx->pvl.p;
@@ -825,38 +764,21 @@ extern "C" int spk_block_residual(spk_ctx *ctx, int link_type, int n_rules, cons
             A.out_vl = npvl.p + (new_base[r] - pv_base);
             A.out_vr = npvr.p + (new_base[r] - pv_base);
         }
-        k_residual_filter<true><<<(unsigned)n_chunks[r], RF_THREADS, 0, ctx->stream>>>(A);
+        k_residual_filter<true><<<(unsigned)chunks[r].n, RF_THREADS, 0, ctx->stream>>>(A);
         SPK_HIP(hipGetLastError());
     }
     if (ctx->timing) SPK_HIP(hipEventRecord(ctx->res_ev1, ctx->stream));
     SPK_HIP(hipStreamSynchronize(ctx->stream));
     SPK_TRY(lap());
     if (ctx->timing) ctx->res_filter_ms = filter_ms;
-    take_buf(ctx->pl, npl);
-    take_buf(ctx->pr, npr);
-    take_buf(ctx->pvl, npvl);
-    take_buf(ctx->pvr, npvr);
-    ctx->pv_base = pv_base;
-    for (int r = 0; r < n_rules; ++r) {
-        ctx->pair_rule_lo[r] = new_base[r];
-        ctx->pair_rule_hi[r] = r + 1 < n_rules ? new_base[r + 1] : n_out;
-    }
-    for (int r = 1; r <= n_views; ++r) {
-        ctx->views[r].pair_lo = ctx->pair_rule_lo[r];
-        ctx->views[r].pair_hi = ctx->pair_rule_hi[r];
-    }
+    ctx->pl = std::move(npl);
+    ctx->pr = std::move(npr);
+    ctx->pvl = std::move(npvl);
+    ctx->pvr = std::move(npvr);
     // pair_terms stays: every survivor still satisfies its rule's key terms.  The hidden pass leaves nothing a
     // later call could take for the caller's comparison vectors.
-    ctx->n_pairs = n_out;
-    ctx->pairs_epoch++;
-    ctx->codes_valid = false;
-    ctx->gamma_pending = false;
-    ctx->alt.gamma_pending = false;
-    ctx->slow_seen_valid = false;
-    ctx->mpat_valid = false;
-    ctx->tf_mp.release();
-    ctx->tf_count = -1;
-    ctx->pairs_valid = true;
+    ctx->pairs_replaced(n_out);
+    ctx->set_rule_ranges(new_base, n_out);
     commit.done = true;
     if (out_n_pairs) *out_n_pairs = n_out;
     return SPK_OK;

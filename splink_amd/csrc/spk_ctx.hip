@@ -362,6 +362,48 @@ int spk_ctx::xend(int k) {
     return SPK_OK;
 }
 
+// ---- the pair set's bookkeeping: the only writers of pairs_valid, pairs_epoch, the rule ranges and pv_base ------
+void spk_ctx::pairs_dropped() {
+    pairs_valid = false;
+    codes_valid = false;
+}
+
+// Called with the stream synchronised, once pl / pr hold the n pairs of the new set.  Everything that describes
+// the old set goes, on every path (spk_block, spk_block_residual, spk_pairs_load); where a path did not clear a
+// field before, the line says why clearing it changes nothing a caller can see.
+void spk_ctx::pairs_replaced(int64_t n) {
+    n_pairs = n;
+    pairs_valid = true;
+    pairs_epoch++;      // keys slow_seen, the view images, the EM hot pattern, the graph and the tf results
+    codes_valid = false;
+    tf_mp.release();    // a kept tf result describes the old pair set (spk_tf_copy refuses it by tf_epoch as well)
+    tf_count = -1;
+    // the next three were cleared by spk_block_residual alone:
+    // gamma_pending: with codes_valid false, settle_slot only waits for the read-back event and returns; the
+    //   stream is synchronised here, and the alternate slot's flag is dropped without a wait there too
+    gamma_pending = false;
+    alt.gamma_pending = false;
+    // slow_seen_valid: read by spk_gammas after it has compared slow_key_pairs with pairs_epoch, bumped above
+    slow_seen_valid = false;
+    // mpat_valid: read behind codes_valid (tf_ready); codes come back only through spk_gammas or
+    //   set_pattern_space, which clear it themselves
+    mpat_valid = false;
+}
+
+void spk_ctx::set_rule_ranges(const std::vector<int64_t> &rule_base, int64_t n_out) {
+    const int n_rules = (int)rule_base.size();
+    pair_rule_lo = rule_base;
+    pair_rule_hi.resize(rule_base.size());
+    for (int r = 0; r < n_rules; ++r) pair_rule_hi[r] = r + 1 < n_rules ? rule_base[r + 1] : n_out;
+    // rules 1 .. MAX_VIEWS-1 keep their row order (view); their pairs carry view positions
+    n_views = std::max(std::min(n_rules, MAX_VIEWS) - 1, 0);
+    pv_base = view_pair_base(rule_base, n_out);
+    for (int r = 1; r <= n_views; ++r) {
+        views[r].pair_lo = pair_rule_lo[r];
+        views[r].pair_hi = pair_rule_hi[r];
+    }
+}
+
 extern "C" {
 
 const char *spk_last_error(void) { return g_last_error.c_str(); }
@@ -517,8 +559,7 @@ int spk_table_create(spk_ctx *ctx, int side, int64_t n_rows, int n_cols) {
     t.n = n_rows;
     t.desc_dirty = true;
     t.version = ++ctx->table_epoch;
-    ctx->pairs_valid = false;
-    ctx->codes_valid = false;
+    ctx->pairs_dropped();
     return SPK_OK;
 }
 
@@ -693,17 +734,9 @@ int spk_pairs_load(spk_ctx *ctx, int64_t n, const int32_t *rows_l, const int32_t
         SPK_HIP(hipMemcpyAsync(ctx->pr.p, rows_r, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
     }
     SPK_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->n_pairs = n;
-    ctx->pairs_valid = true;
-    ctx->pairs_epoch++;
-    ctx->tf_mp.release();  // a kept tf result describes the old pair set (spk_tf_copy refuses it)
-    ctx->tf_count = -1;
-    ctx->n_views = 0;
-    ctx->pv_base = n;
-    ctx->pair_terms.clear();
-    ctx->pair_rule_lo.clear();
-    ctx->pair_rule_hi.clear();
-    ctx->codes_valid = false;
+    ctx->pairs_replaced(n);
+    ctx->pair_terms.clear();  // a loaded list has no rules: no key terms, no rule ranges, no views
+    ctx->set_rule_ranges({}, n);
     return SPK_OK;
 }
 

@@ -14,14 +14,11 @@
 //   * comparison columns (spk_table_add_raw_utf8): UTF-8 -> UTF-16 decode through the permutation,
 //     with dictionary ids computed like the keys (string equality = one integer compare).
 // Every kernel here is a streaming pass or a gather over the rows; the sorts are rocPRIM radix sorts.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_reduce.hpp>
-#include <rocprim/device/device_scan.hpp>
-
 #include <algorithm>
 #include <cstring>
 
 #include "spk_internal.h"
+#include "spk_prim.h"
 
 namespace spk {
 
@@ -240,22 +237,12 @@ static int sorted_ids(spk_ctx *ctx, int64_t n, IdWork &w, const HashSeg &s0, con
     *n_runs = 0;
     *collision = false;
     if (n == 0) return SPK_OK;
-    size_t bytes = 0;
-    SPK_HIP(rocprim::radix_sort_pairs(nullptr, bytes, w.k_in.p, w.k_out.p, w.i_in.p, w.i_out.p, (size_t)n, 0, 64,
-                                      ctx->stream));
-    SPK_TRY(w.tmp.alloc(bytes + 1));
-    SPK_HIP(rocprim::radix_sort_pairs(w.tmp.p, bytes, w.k_in.p, w.k_out.p, w.i_in.p, w.i_out.p, (size_t)n, 0, 64,
-                                      ctx->stream));
+    SPK_TRY(sort_pairs_u64(ctx->stream, w.tmp, w.k_in.p, w.k_out.p, w.i_in.p, w.i_out.p, n));
     SPK_HIP(hipMemsetAsync(w.flag.p, 0, sizeof(unsigned int), ctx->stream));
     k_heads_verify<<<grid(n), 256, 0, ctx->stream>>>(n, w.k_out.p, w.i_out.p, s0, s1, verify ? 1 : 0, w.heads.p,
                                                      w.flag.p);
     SPK_HIP(hipGetLastError());
-    bytes = 0;
-    SPK_HIP(rocprim::inclusive_scan(nullptr, bytes, w.heads.p, w.incl.p, (size_t)n, rocprim::plus<int64_t>(),
-                                    ctx->stream));
-    SPK_TRY(w.tmp.alloc(bytes + 1));
-    SPK_HIP(rocprim::inclusive_scan(w.tmp.p, bytes, w.heads.p, w.incl.p, (size_t)n, rocprim::plus<int64_t>(),
-                                    ctx->stream));
+    SPK_TRY(inclusive_scan(ctx->stream, w.tmp, w.heads.p, w.incl.p, n));
     k_scatter_ids<<<grid(n), 256, 0, ctx->stream>>>(n, w.k_out.p, w.i_out.p, w.incl.p, null_flag, ids);
     SPK_HIP(hipGetLastError());
     int64_t runs = 0;
@@ -708,10 +695,7 @@ int spk_rank_from_raw(spk_ctx *ctx, int raw_uid, int64_t right_from) {
     // NULL ids present?  (the rank layout then marks them for the link predicate)
     DevBuf<unsigned long long> cnt;
     SPK_TRY(cnt.alloc(1));
-    size_t bytes = 0;
-    SPK_HIP(rocprim::reduce(nullptr, bytes, nul.p, cnt.p, (size_t)n, rocprim::plus<unsigned long long>(), ctx->stream));
-    SPK_TRY(w.tmp.alloc(bytes + 1));
-    SPK_HIP(rocprim::reduce(w.tmp.p, bytes, nul.p, cnt.p, (size_t)n, rocprim::plus<unsigned long long>(), ctx->stream));
+    SPK_TRY(reduce_sum(ctx->stream, w.tmp, nul.p, cnt.p, n));
     unsigned long long n_null = 0;
     SPK_HIP(hipMemcpyAsync(&n_null, cnt.p, 8, hipMemcpyDeviceToHost, ctx->stream));
     SPK_HIP(hipStreamSynchronize(ctx->stream));
@@ -737,12 +721,7 @@ int spk_cluster(spk_ctx *ctx, int32_t *out_perm0, int32_t *out_perm1) {
         k_cluster_keys<<<grid(n), 256, 0, ctx->stream>>>(n, t.key[which][0]->p, use_rank ? t.rank.p : nullptr,
                                                          w.k_in.p, w.i_in.p);
         SPK_HIP(hipGetLastError());
-        size_t bytes = 0;
-        SPK_HIP(rocprim::radix_sort_pairs(nullptr, bytes, w.k_in.p, w.k_out.p, w.i_in.p, w.i_out.p, (size_t)n, 0, 64,
-                                          ctx->stream));
-        SPK_TRY(w.tmp.alloc(bytes + 1));
-        SPK_HIP(rocprim::radix_sort_pairs(w.tmp.p, bytes, w.k_in.p, w.k_out.p, w.i_in.p, w.i_out.p, (size_t)n, 0, 64,
-                                          ctx->stream));
+        SPK_TRY(sort_pairs_u64(ctx->stream, w.tmp, w.k_in.p, w.k_out.p, w.i_in.p, w.i_out.p, n));
         const int32_t *perm = w.i_out.p;
         DevBuf<int64_t> tmp64;
         SPK_TRY(tmp64.alloc((size_t)n + 1));
@@ -777,8 +756,7 @@ int spk_cluster(spk_ctx *ctx, int32_t *out_perm0, int32_t *out_perm1) {
         t.version = ++ctx->table_epoch;
         SPK_HIP(hipStreamSynchronize(ctx->stream));
     }
-    ctx->pairs_valid = false;
-    ctx->codes_valid = false;
+    ctx->pairs_dropped();
     return SPK_OK;
 }
 
@@ -820,12 +798,7 @@ int spk_table_add_raw_utf8(spk_ctx *ctx, int col, int raw0, int raw1) {
         k_perm_lengths<<<grid(n + 1), 256, 0, ctx->stream>>>(n, r->off.p, perm, len.p);
         SPK_HIP(hipGetLastError());
         DevBuf<uint8_t> tmp;
-        size_t bytes = 0;
-        SPK_HIP(rocprim::exclusive_scan(nullptr, bytes, len.p, off8.p, (int64_t)0, (size_t)n + 1,
-                                        rocprim::plus<int64_t>(), ctx->stream));
-        SPK_TRY(tmp.alloc(bytes + 1));
-        SPK_HIP(rocprim::exclusive_scan(tmp.p, bytes, len.p, off8.p, (int64_t)0, (size_t)n + 1,
-                                        rocprim::plus<int64_t>(), ctx->stream));
+        SPK_TRY(exclusive_scan(ctx->stream, tmp, len.p, off8.p, n + 1));
         int64_t nbytes = 0;
         SPK_HIP(hipMemcpyAsync(&nbytes, off8.p + n, 8, hipMemcpyDeviceToHost, ctx->stream));
         SPK_HIP(hipStreamSynchronize(ctx->stream));

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/splink_hip.h"
@@ -131,6 +132,18 @@ struct DevBuf {
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) {
+        o.p = nullptr;
+        o.n = 0;
+    }
+    DevBuf &operator=(DevBuf &&o) noexcept {  // frees what this buffer held
+        if (this != &o) {
+            release();
+            std::swap(p, o.p);
+            std::swap(n, o.n);
+        }
+        return *this;
+    }
 };
 
 struct Column {
@@ -191,15 +204,6 @@ struct Table {
     ~Table();
 };
 
-template <typename T>
-inline void take_buf(DevBuf<T> &dst, DevBuf<T> &src) {  // move src's allocation into dst
-    dst.release();
-    dst.p = src.p;
-    dst.n = src.n;
-    src.p = nullptr;
-    src.n = 0;
-}
-
 // Blocking rule r >= 1 as its own row order ("view"): the rows with a non-NULL key r sorted by
 // (key r, rank), so a block of rule r is contiguous in it.  Pairs of rule r also carry their view
 // positions (spk_ctx::pvl / pvr), and the comparison filter reads a copy of the row image laid out
@@ -212,6 +216,12 @@ struct RuleView {
     bool tri = true;               // symmetric self-join: both sides index rowsL
     int64_t pair_lo = 0, pair_hi = 0;  // this rule's pair ordinals (local shard)
 };
+
+// First pair ordinal that carries view positions, given the first ordinal of every rule and the pair count:
+// rule 1's first pair, or none when there is one rule (MAX_VIEWS = 2: only rule 1 has a view).
+inline int64_t view_pair_base(const std::vector<int64_t> &rule_base, int64_t n_pairs) {
+    return rule_base.size() > 1 ? rule_base[1] : n_pairs;
+}
 
 struct GammaPlan;
 enum Kern { K_BLOCK = 0, K_GAMMA = 1, K_EMHIST = 2, K_EMFIN = 3, K_SCORE = 4, K_COUNT = 5 };
@@ -238,6 +248,12 @@ struct spk_ctx {
     int n_views = 0;
     spk::DevBuf<int32_t> pvl, pvr;     // view positions of pairs [pv_base, n_pairs)
     int64_t pv_base = 0;
+    // Every change of the pair set goes through these three (spk_ctx.hip), so that each path invalidates the same
+    // things: there is no pair set (and so no codes); pl / pr now hold n pairs of a new set; the new set's rules
+    // start at the ordinals rule_base and it has n_out pairs (no rules: a loaded pair list).
+    void pairs_dropped();
+    void pairs_replaced(int64_t n);
+    void set_rule_ranges(const std::vector<int64_t> &rule_base, int64_t n_out);
     // the last spk_block_residual: key candidates it enumerated on this shard (after the link-type predicate and
     // the exclusion by earlier key-only rules), -1 = none yet; device milliseconds of its compaction (timing on:
     // the sum over HIP event pairs around each rule's count kernel + scan and around the emit kernels), -1 = none

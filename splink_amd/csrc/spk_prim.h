@@ -1,0 +1,71 @@
+// Device-wide primitives (rocprim) behind the project's error codes.  Included only by the translation units
+// that sort or scan, so the others do not compile rocprim.
+//
+// Every rocprim call comes in two: with a null scratch pointer it reports the scratch size, with the scratch it
+// runs.  Each wrapper takes the stream and a scratch buffer that grows as needed and can be handed from call
+// to call; n == 0 does nothing.  Inputs are plain (non-const) pointers: rocprim instantiates its kernels per
+// iterator type, and one type per primitive keeps one set of them in the library.
+#pragma once
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_reduce.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include "spk_internal.h"
+
+namespace spk {
+
+// call(scratch, bytes) -> hipError_t: once for the size, once to run.
+template <typename Call>
+inline int prim_two_calls(const char *what, DevBuf<uint8_t> &tmp, Call call) {
+    size_t bytes = 0;
+    hipError_t e = call(static_cast<void *>(nullptr), bytes);
+    if (e == hipSuccess) {
+        SPK_TRY(tmp.alloc(bytes + 1));
+        e = call(static_cast<void *>(tmp.p), bytes);
+    }
+    if (e != hipSuccess) {
+        set_error(std::string(what) + ": " + hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? SPK_E_OOM : SPK_E_HIP;
+    }
+    return SPK_OK;
+}
+
+// Stable sort of (key, value) pairs by all 64 bits of the key.
+template <typename V>
+inline int sort_pairs_u64(hipStream_t stream, DevBuf<uint8_t> &tmp, uint64_t *keys_in, uint64_t *keys_out, V *vals_in,
+                          V *vals_out, int64_t n) {
+    if (n <= 0) return SPK_OK;
+    return prim_two_calls("rocprim::radix_sort_pairs", tmp, [&](void *scratch, size_t &bytes) {
+        return rocprim::radix_sort_pairs(scratch, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, 64, stream);
+    });
+}
+
+// out[i] = in[0] + .. + in[i - 1]
+template <typename T>
+inline int exclusive_scan(hipStream_t stream, DevBuf<uint8_t> &tmp, T *in, T *out, int64_t n) {
+    if (n <= 0) return SPK_OK;
+    return prim_two_calls("rocprim::exclusive_scan", tmp, [&](void *scratch, size_t &bytes) {
+        return rocprim::exclusive_scan(scratch, bytes, in, out, (T)0, (size_t)n, rocprim::plus<T>(), stream);
+    });
+}
+
+// out[i] = in[0] + .. + in[i]
+template <typename T>
+inline int inclusive_scan(hipStream_t stream, DevBuf<uint8_t> &tmp, T *in, T *out, int64_t n) {
+    if (n <= 0) return SPK_OK;
+    return prim_two_calls("rocprim::inclusive_scan", tmp, [&](void *scratch, size_t &bytes) {
+        return rocprim::inclusive_scan(scratch, bytes, in, out, (size_t)n, rocprim::plus<T>(), stream);
+    });
+}
+
+// *out = in[0] + .. + in[n - 1], summed as Out
+template <typename In, typename Out>
+inline int reduce_sum(hipStream_t stream, DevBuf<uint8_t> &tmp, In *in, Out *out, int64_t n) {
+    if (n <= 0) return SPK_OK;
+    return prim_two_calls("rocprim::reduce", tmp, [&](void *scratch, size_t &bytes) {
+        return rocprim::reduce(scratch, bytes, in, out, (size_t)n, rocprim::plus<Out>(), stream);
+    });
+}
+
+}  // namespace spk

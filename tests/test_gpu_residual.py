@@ -2,7 +2,6 @@
 tests/golden/residual_rules.json, a medium-sized sharded job against a pandas restatement, the state the
 filter leaves for the comparison pass, the link-type edges, and the unchanged path of plain rules."""
 import copy
-import math
 import warnings
 
 import numpy as np
@@ -11,6 +10,7 @@ import pytest
 
 import residual_common as rc
 from conftest import load_golden
+from parity_common import check_history, compare_frames, frame
 
 pytestmark = pytest.mark.gpu
 warnings.filterwarnings("ignore")
@@ -24,53 +24,6 @@ def amd():
     if _native.device_count() == 0:
         pytest.fail("no HIP device visible: the -m gpu tests need an MI355X")
     return AmdSession(0)
-
-
-# ---- the comparison of tests/test_gpu_parity.py (compare_frames / check_history), copied -------------------
-def frame(d):
-    return pd.DataFrame(d) if d else None
-
-
-def rel_close(a, b, tol=1e-9):
-    """Relative closeness; NULL (None) and NaN are the same missing value."""
-    a = None if (isinstance(a, float) and math.isnan(a)) else a
-    b = None if (isinstance(b, float) and math.isnan(b)) else b
-    if a is None or b is None:
-        return a is None and b is None
-    return abs(a - b) <= tol * max(abs(a), abs(b), 1e-300)
-
-
-def sort_like_golden(df):
-    keys = [k for k in ("_source_table_l", "unique_id_l", "_source_table_r", "unique_id_r") if k in df.columns]
-    rest = [c for c in df.columns if c.startswith("gamma_")]
-    return df.sort_values(keys + rest, kind="mergesort").reset_index(drop=True)
-
-
-def compare_frames(got: pd.DataFrame, exp: dict, columns):
-    assert list(got.columns) == list(columns)
-    got = sort_like_golden(got)
-    for c in columns:
-        gv, ev = got[c].tolist(), exp[c]
-        assert len(gv) == len(ev), c
-        for a, b in zip(gv, ev):
-            if isinstance(b, float) or (isinstance(a, float) and not isinstance(b, str)):
-                a = None if a is None else float(a)
-                assert rel_close(a, b), (c, a, b)
-            else:
-                if isinstance(a, float) and math.isnan(a):
-                    a = None
-                assert a == b, (c, a, b)
-
-
-def check_history(params, g):
-    hist = params.param_history[1:] + [params.params]
-    assert len(hist) == len(g["iterations"])
-    for p, it in zip(hist, g["iterations"]):
-        assert rel_close(p["λ"], it["lambda"])
-        for gname, d in it["pi"].items():
-            for i, (m, u) in enumerate(zip(d["m"], d["u"])):
-                assert rel_close(p["π"][gname]["prob_dist_match"][f"level_{i}"]["probability"], m), (gname, i)
-                assert rel_close(p["π"][gname]["prob_dist_non_match"][f"level_{i}"]["probability"], u), (gname, i)
 
 
 # ---- 1. golden pipeline parity ------------------------------------------------------------------------------
@@ -279,3 +232,83 @@ def test_plain_rules_take_spk_block(amd, medium, monkeypatch):
     job2 = Job("dedupe_only", [medium["df"]], "unique_id", 0)
     job2.block(MEDIUM_RULES[:1])
     assert calls == ["block", "residual"]
+
+
+# ---- 6. the compaction's chunk edges at small size -------------------------------------------------------------
+SMALL_N = 65  # one key: rule 0 enumerates 65 * 64 / 2 = 2080 candidates -- two compaction workgroups, nine slabs
+SMALL_RULES = ["l.k = r.k and l.v < r.v", "l.k2 = r.k2"]  # rule 1 is key-only and carries view positions
+SMALL_FNS = [(rc.eq("k"), lambda l, r: rc.cmp("<", l["v"], r["v"])), (rc.eq("k2"), None)]
+RF_SLAB = 256  # pairs per slab of a compaction workgroup (spk_block.hip RF_THREADS)
+
+
+def small_frame(keep):
+    """65 records in unique-id order under one key, so rule 0's candidate ordinals are the pairs (i, j), i < j,
+    i-major; `v` decides which of them `l.v < r.v` keeps."""
+    from splink_amd.synthetic import make_records
+    df = make_records(SMALL_N, seed=41, surname_vocab=6, first_vocab=6, city_vocab=4)[
+        ["unique_id", "first_name", "surname", "dob", "city", "email"]]
+    i = np.arange(SMALL_N)
+    df["unique_id"] = i
+    df["k"] = "a"
+    df["k2"] = [f"g{x % 5}" for x in i]
+    if keep == "none":
+        v = np.zeros(SMALL_N)
+    elif keep == "all":
+        v = i.astype(np.float64)
+    elif keep == "one":  # descending but for rows 60, 61: the pair (60, 61), ordinal 2070 of 2080
+        v = -i.astype(np.float64)
+        v[[60, 61]] = v[[61, 60]]
+    else:
+        v = np.random.default_rng(7).integers(0, 4, SMALL_N).astype(np.float64)
+    df["v"] = v
+    return df
+
+
+@pytest.mark.parametrize("keep", ["none", "one", "all", "mix"])
+def test_small_rule_at_the_chunk_edges(amd, keep):
+    from splink_amd.engine import Job
+    from splink_amd.settings import complete_settings_dict
+    from splink_amd.synthetic import cfg_settings
+    df = small_frame(keep)
+    L = [dict(zip(df.columns, v), _id=i) for i, v in enumerate(df.itertuples(index=False, name=None))]
+    emitted, stats = rc.brute_force("dedupe_only", L, L, SMALL_FNS)
+    n_cand = SMALL_N * (SMALL_N - 1) // 2
+    assert n_cand == 2080 and stats[0]["candidates"] == n_cand and stats[1]["candidates"] == 5 * 13 * 12 // 2
+    want0 = [(i, j) for k, i, j in emitted if k == 0]
+    assert len(want0) == {"none": 0, "one": 1, "all": n_cand}.get(keep, len(want0))
+    assert (stats[1]["emitted"] == 0) == (keep == "all")
+    if keep == "one":
+        assert want0 == [(60, 61)]
+    if keep == "mix":  # kept and rejected candidates in the first slab, between ordinals 256 and 2048, and past 2048
+        kept = np.zeros(n_cand, dtype=bool)
+        kept[[i * (2 * SMALL_N - i - 1) // 2 + j - i - 1 for i, j in want0]] = True
+        for part in (kept[:RF_SLAB], kept[RF_SLAB:RF_CHUNK], kept[RF_CHUNK:]):
+            assert part.any() and not part.all()
+    job = Job("dedupe_only", [df], "unique_id", 0)
+    job.block(SMALL_RULES)
+    assert job.n_pairs == len(emitted) and job.n_candidates == n_cand + stats[1]["candidates"]
+    assert job.ctx.block_residual_info()[0] == n_cand + stats[1]["candidates"]  # rule 0 does not exclude on its key
+    l, r = job.pair_rows()
+    perm = job.perm[0] if job.perm[0] is not None else np.arange(SMALL_N)
+    got = list(zip(perm[l].tolist(), perm[r].tolist()))
+    # rule 0: the survivors in ordinal order
+    assert got[:len(want0)] == want0
+    # rule 1: block after block (their order is the device's key ids'), l-major inside a block
+    got1 = got[len(want0):]
+    groups = list(dict.fromkeys(i % 5 for i, _ in got1))
+    want1 = sorted(((i, j) for k, i, j in emitted if k == 1), key=lambda p: (groups.index(p[0] % 5), p))
+    assert got1 == want1
+    if keep != "mix":
+        return
+    # the state after the filter, as test_state_after_the_filter: rule ranges and rule 1's view positions
+    st = complete_settings_dict(cfg_settings(2), amd)
+    other = Job("dedupe_only", [job.tables[0][list(df.columns)]], "unique_id", 0, cluster=False)
+    other.load_pairs(l, r)
+    other.gammas(st)
+    want = other.gammas_host()
+    job.ctx.gammas_set_simple(21)
+    job.gammas(st)
+    codes = job.gammas_host()
+    job.ctx.gammas_set_simple(1)
+    assert codes.shape == want.shape and (codes == want).all(), np.nonzero((codes != want).any(axis=1))[0][:10]
+    assert job.ctx.gammas_view_regions() > 0
