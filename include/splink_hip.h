@@ -67,7 +67,8 @@ int spk_ctx_lds_per_block(spk_ctx *ctx, int *out);
  * buffers as handed over), [1] record encodings (decoded columns: units, metadata, bit-planes, bag rows,
  * numeric values; row permutations, ranks, blocking keys), [2] filter row images, [3] candidate pairs (row
  * indices, rule-view positions and rows), [4] comparison codes, [5] comparison work lists (filter lists,
- * exact / slow lists, region counts), [6] EM, scoring and tf state and the last selection (spk_select), [7] the sum.  For sizing a share of a
+ * exact / slow lists, region counts), [6] EM, scoring and tf state, the last selection (spk_select) and the last
+ * components' labels (spk_components*), [7] the sum.  For sizing a share of a
  * job against a device's memory (there is no reference counterpart: Spark spills). */
 int spk_ctx_memory(spk_ctx *ctx, int64_t *out8);
 
@@ -423,6 +424,34 @@ int spk_select_copy(spk_ctx *ctx, int64_t start, int64_t count, int64_t *out_ord
  * emit pass; the host round trip between them is not in it), -1 otherwise. */
 int spk_select_info(spk_ctx *ctx, int64_t *out_n_selected, double *out_ms);
 int spk_select_release(spk_ctx *ctx);
+
+/* ---- connected components of the kept pairs (replaces handing df_e.filter(...) to GraphFrames'
+ *      connectedComponents; later reference releases: cluster_pairwise_predictions_at_threshold) ---- */
+/* label[v] = the smallest node id of v's component in the graph whose edges are the survivors of the last spk_select;
+ * a node without edges keeps label[v] = v.  Node ids are INPUT positions, not device rows (spk_cluster permutes
+ * those): dedupe_only and link_and_dedupe have the n0 rows of table 0 as nodes (the latter: the vertical
+ * concatenation, left rows first); link_only has n0 + n1 nodes, a right row r being node n0 + its input position.
+ * Min-label hooking with pointer jumping, one host-read "changed" word per round; the result does not depend on
+ * edge order, launch shape or the arrival order of the atomics.  out_n_clusters counts the nodes with label[v] == v
+ * (singletons included); out_rounds the rounds run, the last quiet one included (0 without edges).  SPK_E_STATE
+ * without a selection, with a stale one, or with one that has no pair rows (a loaded gamma table); SPK_E_LIMIT past
+ * 2^32 - 1 nodes or when the round cap (256) is reached.  The labels stay on the device until the next
+ * spk_components*, spk_components_release, or a change of the tables (spk_table_create, spk_cluster); they do not
+ * depend on the selection, the codes or the pairs once built, and a failing call leaves none.  Reads the selection
+ * and the tables' permutations only: scores, tf and EM state are not touched. */
+int spk_components(spk_ctx *ctx, int64_t *out_n_nodes, int64_t *out_n_clusters, int *out_rounds);
+/* The same over host edges u[i] -- v[i] with ids in [0, n_nodes): any graph, no tables needed (the building block
+ * for merging the clusters of several shards).  Self-loops, repeated edges and both orientations are legal; an id
+ * >= n_nodes is SPK_E_INVALID (found on the device in the first pass, no label is read or written for that edge). */
+int spk_components_edges(spk_ctx *ctx, int64_t n_nodes, int64_t n_edges, const uint32_t *u, const uint32_t *v,
+                         int64_t *out_n_clusters, int *out_rounds);
+/* Labels of nodes [start, start + count) of the last spk_components* (SPK_E_STATE: none). */
+int spk_components_copy(spk_ctx *ctx, int64_t start, int64_t count, uint32_t *out_label);
+/* The last spk_components*: nodes and edges (-1: none, released or replaced by a failed call), rounds, and with
+ * timing on (spk_ctx_enable_timing) the device milliseconds of its kernels (edge build, every round's hook and jump
+ * launches, the cluster count; the host round trip after each round is not in it), -1 otherwise. */
+int spk_components_info(spk_ctx *ctx, int64_t *out_n_nodes, int64_t *out_n_edges, int *out_rounds, double *out_ms);
+int spk_components_release(spk_ctx *ctx);
 
 /* ---- term-frequency adjustment (term_frequencies.py:122-168) ------------------- */
 /* For value ids of one column (per row, -1 NULL; both sides in one id space) accumulate, over

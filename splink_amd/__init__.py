@@ -6,6 +6,7 @@ Drop-in for the reference's public API (splink 0.1.7, splink/__init__.py):
     linker = Splink(settings, AmdSession(), df=records)      # pandas / pyarrow / Spark input
     df_e = linker.get_scored_comparisons()                   # device-resident frame
     df_e.toPandas()
+    df_e.clusters(0.95).toPandas()                           # one cluster_id per input record
 
 Blocking, comparison vectors, EM and scoring run as hand-written HIP kernels in
 libsplink_hip.so (C ABI: include/splink_hip.h); there is no CPU fallback.
@@ -16,7 +17,7 @@ from .blocking import block_using_rules
 from .case_statements import _check_jaro_registered
 from .check_types import check_types
 from .expectation_step import run_expectation_step
-from .frames import SplinkDataFrame
+from .frames import ClusterFrame, FilteredFrame, SplinkDataFrame
 from .gammas import add_gammas
 from .iterate import iterate
 from .params import Params, load_params_from_json
@@ -26,7 +27,8 @@ from .term_frequencies import make_adjustment_for_term_frequencies
 from .validate import validate_settings
 
 __all__ = ["Splink", "load_from_json", "AmdSession", "session", "Params", "block_using_rules", "add_gammas",
-           "iterate", "run_expectation_step", "make_adjustment_for_term_frequencies", "complete_settings_dict"]
+           "iterate", "run_expectation_step", "make_adjustment_for_term_frequencies", "complete_settings_dict",
+           "ClusterFrame", "FilteredFrame"]
 
 
 def _is_frame(x):

@@ -43,6 +43,9 @@ SELECT_MAX_TERMS = 8  # SPK_SELECT_MAX_TERMS
 # Pair ordinals per count of the selection's compaction.  Mirrored from SEL_CHUNK in csrc/spk_select.hip (the
 # library exports no call for it); only the tests' edge sizes depend on it.
 SELECT_CHUNK = 2048
+# Edges per workgroup step of the components' hooking kernel.  Mirrored from CC_CHUNK in csrc/spk_components.hip
+# (256 threads x one 16-byte vector of ids each); only the tests' edge sizes depend on it.
+COMPONENTS_CHUNK = 1024
 assert OPERAND_DTYPE.itemsize == 40 and INSTR_DTYPE.itemsize == 32 and PROGRAM_DTYPE.itemsize == 16
 
 OP = {"ISNULL": 1, "NOTNULL": 2, "STR_CMP": 3, "NUM_CMP": 4, "JW": 5, "LEV": 6, "LEVRATIO": 7, "ABSDIFF": 8,
@@ -67,6 +70,7 @@ EXPORTS = [
     "spk_gammas_set_lev_kernel",
     "spk_block_residual", "spk_block_residual_info",
     "spk_select", "spk_select_copy", "spk_select_info", "spk_select_release",
+    "spk_components", "spk_components_edges", "spk_components_copy", "spk_components_info", "spk_components_release",
 ]
 TF_LIMBS = 14  # SPK_TF_LIMBS
 
@@ -567,6 +571,51 @@ class Context:
 
     def select_release(self):
         check(self._lib.spk_select_release(self._h), "spk_select_release")
+
+    # ---- connected components of the kept pairs -----------------------------------------------
+    def components(self):
+        """spk_components over the last select's survivors: (n_nodes, n_clusters, rounds).  Node ids are input
+        positions (link_only: the right table's follow the left's)."""
+        n = ctypes.c_int64(0)
+        c = ctypes.c_int64(0)
+        r = ctypes.c_int(0)
+        check(self._lib.spk_components(self._h, ctypes.byref(n), ctypes.byref(c), ctypes.byref(r)), "spk_components")
+        return n.value, c.value, r.value
+
+    def components_edges(self, n_nodes: int, u, v):
+        """spk_components_edges: the same over host edges u[i] -- v[i] with ids in [0, n_nodes); returns
+        (n_clusters, rounds).  An id >= n_nodes raises ValueError."""
+        u = np.ascontiguousarray(u, dtype=np.uint32)
+        v = np.ascontiguousarray(v, dtype=np.uint32)
+        if u.shape != v.shape or u.ndim != 1:
+            raise ValueError("components_edges: u and v must be one-dimensional and of one length")
+        c = ctypes.c_int64(0)
+        r = ctypes.c_int(0)
+        check(self._lib.spk_components_edges(self._h, ctypes.c_int64(n_nodes), ctypes.c_int64(len(u)),
+                                             _ptr(u) if len(u) else ctypes.c_void_p(0),
+                                             _ptr(v) if len(v) else ctypes.c_void_p(0), ctypes.byref(c), ctypes.byref(r)),
+              "spk_components_edges")
+        return c.value, r.value
+
+    def components_copy(self, start: int, count: int) -> np.ndarray:
+        """Labels (uint32, the smallest node id of the component) of nodes [start, start + count)."""
+        out = np.empty(count, dtype=np.uint32)
+        check(self._lib.spk_components_copy(self._h, ctypes.c_int64(start), ctypes.c_int64(count),
+                                            _ptr(out) if count else ctypes.c_void_p(0)), "spk_components_copy")
+        return out
+
+    def components_info(self):
+        """(nodes, edges, rounds of the last components or -1 each, ms of its kernels with timing on or -1)."""
+        n = ctypes.c_int64(-1)
+        e = ctypes.c_int64(-1)
+        r = ctypes.c_int(-1)
+        ms = ctypes.c_double(-1.0)
+        check(self._lib.spk_components_info(self._h, ctypes.byref(n), ctypes.byref(e), ctypes.byref(r), ctypes.byref(ms)),
+              "spk_components_info")
+        return n.value, e.value, r.value, ms.value
+
+    def components_release(self):
+        check(self._lib.spk_components_release(self._h), "spk_components_release")
 
     def _udf(self, fn, left, right):
         from .table import encode_utf8

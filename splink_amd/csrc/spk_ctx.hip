@@ -486,6 +486,8 @@ void spk_ctx_destroy(spk_ctx *ctx) {
     if (ctx->res_ev1) (void)hipEventDestroy(ctx->res_ev1);
     if (ctx->sel_ev0) (void)hipEventDestroy(ctx->sel_ev0);
     if (ctx->sel_ev1) (void)hipEventDestroy(ctx->sel_ev1);
+    if (ctx->cc_ev0) (void)hipEventDestroy(ctx->cc_ev0);
+    if (ctx->cc_ev1) (void)hipEventDestroy(ctx->cc_ev1);
     if (ctx->ev_info) (void)hipEventDestroy(ctx->ev_info);
     if (ctx->ev_stats) (void)hipEventDestroy(ctx->ev_stats);
     if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);
@@ -563,6 +565,7 @@ int spk_table_create(spk_ctx *ctx, int side, int64_t n_rows, int n_cols) {
     t.desc_dirty = true;
     t.version = ++ctx->table_epoch;
     ctx->pairs_dropped();
+    ctx->comp.clear();  // its node ids named the old tables' rows
     return SPK_OK;
 }
 

@@ -3441,7 +3441,8 @@ extern "C" int spk_ctx_memory(spk_ctx *ctx, int64_t *out8) {
            b(ctx->em_row) + b(ctx->em_hot) + b(ctx->mp) + b(ctx->mpat_score) + b(ctx->tf_uniq) + b(ctx->tf_runs) +
            b(ctx->tf_nruns) + b(ctx->tf_mp) + b(ctx->tf_hist) +
            b(ctx->tf_sort) +
-           b(ctx->sel.ord) + b(ctx->sel.l) + b(ctx->sel.r) + b(ctx->sel.code) + b(ctx->sel.mpat);
+           b(ctx->sel.ord) + b(ctx->sel.l) + b(ctx->sel.r) + b(ctx->sel.code) + b(ctx->sel.mpat) +
+           b(ctx->comp.label);
     for (int i = 0; i < 7; ++i) m[7] += m[i];
     for (int i = 0; i < 8; ++i) out8[i] = m[i];
     return SPK_OK;

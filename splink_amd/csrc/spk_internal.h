@@ -242,6 +242,18 @@ struct Selection {
     void clear() { *this = Selection(); }
 };
 
+// The labels of the last spk_components* (spk_components.hip): label[v] = the smallest node id of v's component, by
+// node id (input position).  Built in a local and moved into the context, so a failing call leaves none; once built
+// it needs neither the selection nor the codes nor the pairs, only that the tables (whose rows the ids name) stay.
+struct Components {
+    bool valid = false;
+    int64_t n_nodes = 0, n_edges = 0, n_clusters = 0;
+    int rounds = 0;
+    DevBuf<uint32_t> label;  // [n_nodes]
+    double ms = -1.0;        // device milliseconds of its kernels (timing on), -1 = none
+    void clear() { *this = Components(); }
+};
+
 struct GammaPlan;
 enum Kern { K_BLOCK = 0, K_GAMMA = 1, K_EMHIST = 2, K_EMFIN = 3, K_SCORE = 4, K_COUNT = 5 };
 
@@ -436,6 +448,9 @@ struct spk_ctx {
     spk::Selection sel;
     hipEvent_t sel_ev0 = nullptr, sel_ev1 = nullptr;
     uint64_t codes_fix_seq = 0;
+    // spk_components*: the last labels and the HIP events around its launches (created on first use with timing on)
+    spk::Components comp;
+    hipEvent_t cc_ev0 = nullptr, cc_ev1 = nullptr;
     // the (value, pattern) runs of the last tf scale pass over a device-id column, reused by its sum pass
     spk::DevBuf<unsigned long long> tf_uniq;
     spk::DevBuf<unsigned int> tf_runs, tf_nruns;

@@ -6,7 +6,8 @@ pipeline and its users need: `toPandas()`, `count()`, `columns`, `persist()` / `
 `unpersist()`, `createOrReplaceTempView()`.  Pairs, comparison codes and scores stay on the
 GPU; `toPandas()` copies them back and gathers the retained input columns with the
 reference's column names and order.  `filter(condition)` / `where` (Spark's DataFrame.filter on the
-scored frame) select on the device instead: a `FilteredFrame` copies back the survivors only.
+scored frame) select on the device instead: a `FilteredFrame` copies back the survivors only, and its
+`clusters()` (GraphFrames' connectedComponents over the kept pairs) leaves the device with one label per record.
 """
 from __future__ import annotations
 
@@ -283,6 +284,10 @@ class ExpectationFrame(SplinkDataFrame):
 
     where = filter
 
+    def clusters(self, threshold):
+        """Shorthand for filter(f"match_probability > {threshold!r}").clusters()."""
+        return self.filter(f"match_probability > {threshold!r}").clusters()
+
 
 class FilteredFrame(SplinkDataFrame):
     """`parent.filter(condition)`: lazily selected on the device.  count() runs the selection and returns the
@@ -373,9 +378,88 @@ class FilteredFrame(SplinkDataFrame):
                 data[c] = job.host_values(s, base)[rows_l if side == "_l" else rows_r]
         return pd.DataFrame(data)
 
+    def clusters(self):
+        """The connected components of the graph whose edges are this frame's pairs (GraphFrames'
+        connectedComponents on the reference's filtered frame), computed on the device: a `ClusterFrame`."""
+        return ClusterFrame(self)
+
+
+COPY_NODES = 1 << 26  # labels per spk_components_copy
+
+
+class ClusterFrame(SplinkDataFrame):
+    """`filtered.clusters()`: one row per input record, in input order (two input tables: left rows, then right).
+
+    cluster_id (int64) is the smallest input position among the records of the cluster, so
+    `inputs.iloc[cluster_id]` is its representative; then the unique id, and for the two-table link types
+    _source_table ('left' / 'right').  A record no kept pair touches is a cluster of its own."""
+
+    def __init__(self, filtered: FilteredFrame):
+        job = filtered.job
+        if getattr(job, "passthrough", None) is not None:
+            raise ValueError("clusters() needs the records: a job made from a gamma table has pairs without rows")
+        if job.n_shards > 1:
+            raise ValueError("clusters() on a sharded job: a record's cluster spans the shards' pairs (merge the "
+                             "shards' (node, label) pairs with spk_components_edges, DESIGN.md)")
+        self.filtered = filtered
+        self.job = job
+        self.settings = filtered.settings
+        self._labels = None
+        self._info = None  # (n_nodes, n_clusters, rounds)
+
+    def _column_order(self):
+        cols = ["cluster_id", self.settings["unique_id_column_name"]]
+        if self.job.link_type in ("link_only", "link_and_dedupe"):
+            cols.append("_source_table")
+        return cols
+
+    def _run(self):
+        """Select (the frame's re-select rules), then label: the labels are copied at once, so a later selection or
+        components call of the job does not reach this frame."""
+        if self._labels is None:
+            ctx = self.job.ctx
+            self.filtered._select()
+            n_nodes, n_clusters, rounds = ctx.components()
+            parts = [ctx.components_copy(s, min(COPY_NODES, n_nodes - s)) for s in range(0, n_nodes, COPY_NODES)]
+            self._labels = np.concatenate(parts) if parts else np.empty(0, dtype=np.uint32)
+            self._info = (int(n_nodes), int(n_clusters), int(rounds))
+        return self._labels
+
+    def count(self) -> int:
+        return int(sum(len(t) for t in self.job.inputs))
+
+    @property
+    def n_clusters(self) -> int:
+        self._run()
+        return self._info[1]
+
+    @property
+    def rounds(self) -> int:
+        self._run()
+        return self._info[2]
+
+    def toPandas(self, singletons=True):
+        job = self.job
+        uid = self.settings["unique_id_column_name"]
+        data = OrderedDict()
+        data["cluster_id"] = self._run().astype(np.int64)
+        data[uid] = pd.concat([t[uid] for t in job.inputs], ignore_index=True)
+        if job.link_type == "link_only":
+            data["_source_table"] = np.repeat(np.array(["left", "right"], dtype=object), [len(t) for t in job.inputs])
+        elif job.link_type == "link_and_dedupe":
+            data["_source_table"] = job.inputs[0]["_source_table"].to_numpy()
+        out = pd.DataFrame(data)
+        if not singletons:
+            size = np.bincount(data["cluster_id"], minlength=len(out))
+            out = out[size[data["cluster_id"]] > 1].reset_index(drop=True)
+        return out
+
 
 def reject_filtered(frame, what):
     """The stage functions run over every pair of a job: a filtered frame must not slip into them."""
     if isinstance(frame, FilteredFrame):
         raise ValueError(f"{what} does not take a filtered frame (it would run over all of the job's pairs, not the "
                          "survivors): pass the frame filter() was called on")
+    if isinstance(frame, ClusterFrame):
+        raise ValueError(f"{what} does not take a cluster frame (it holds records, not pairs): pass the frame "
+                         "filter() was called on")
