@@ -320,6 +320,14 @@ int spk_gammas_graph_launches(spk_ctx *ctx, int64_t *out);
  * refill pass over a free-text column (k_compact_lev: cells whose bag distance exceeds the cut take their level
  * there).  Modes 1 and 2 make those decisions too. */
 int spk_gammas_set_lev_kernel(spk_ctx *ctx, int mode);
+/* Filter field of a template Levenshtein column without free-text rows (same codes in both modes; for A/B tests):
+ * 1 = the positional sketch (default) -- an 8-bit length and, for each half of the row, 30 buckets of 2-bit
+ * saturating counts; the filter bounds the distance by the length gap, the whole-string bag distance of the summed
+ * halves and a two-segment bag distance (a's first half against a prefix of b, its second against the rest), and
+ * lists rows with equal fields for the exact pass (the field has no key); 0 = key, lengths and the whole-string
+ * sketch.  A change of mode lays the row image out again at the next spk_gammas.  Free-text columns (rows past 64
+ * units on both sides) keep the mode-0 field either way. */
+int spk_gammas_set_lev_bound(spk_ctx *ctx, int mode);
 /* Filter regions (workgroups) the last spk_gammas ran over the second rule's view-ordered image. */
 int spk_gammas_view_regions(spk_ctx *ctx, int64_t *out);
 

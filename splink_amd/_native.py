@@ -67,7 +67,7 @@ EXPORTS = [
     "spk_em_iteration_start", "spk_em_iteration_wait", "spk_ctx_kernel_ms_done", "spk_em_histogram_async",
     "spk_em_finalize_start", "spk_gammas_exact_ms", "spk_gammas_set_window", "spk_gammas_windows", "spk_gammas_set_streams", "spk_gammas_set_graph",
     "spk_gammas_graph_launches",
-    "spk_gammas_set_lev_kernel",
+    "spk_gammas_set_lev_kernel", "spk_gammas_set_lev_bound",
     "spk_block_residual", "spk_block_residual_info",
     "spk_select", "spk_select_copy", "spk_select_info", "spk_select_release",
     "spk_components", "spk_components_edges", "spk_components_copy", "spk_components_info", "spk_components_release",
@@ -446,6 +446,11 @@ class Context:
         elsewhere (default); 1 lane refill everywhere; 0 one cell per lane everywhere; 3 as 2 without the
         character-bag decisions before the refill pass."""
         check(self._lib.spk_gammas_set_lev_kernel(self._h, ctypes.c_int(int(mode))), "spk_gammas_set_lev_kernel")
+
+    def gammas_set_lev_bound(self, mode: int):
+        """Filter field of template Levenshtein columns without free-text rows (same codes; A/B tests): 1 the
+        positional sketch and its two-segment bound (default), 0 key, lengths and the whole-string sketch."""
+        check(self._lib.spk_gammas_set_lev_bound(self._h, ctypes.c_int(int(mode))), "spk_gammas_set_lev_bound")
 
     def lds_per_block(self) -> int:
         n = ctypes.c_int(0)

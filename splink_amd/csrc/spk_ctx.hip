@@ -28,6 +28,7 @@ int ensure_desc(spk_ctx *ctx, Table &t) {
             d.planes = c->planes.p;
             d.planes_hi = c->planes_hi.n ? c->planes_hi.p : nullptr;
             d.bag = c->bag.n ? c->bag.p : nullptr;
+            d.pos = c->pos.n ? c->pos.p : nullptr;
         } else if (c && c->kind == COL_NUM) {
             d.val = c->val.p;
             d.valid = c->valid.p;
@@ -278,9 +279,50 @@ int build_bag_rows(spk_ctx *ctx, int64_t n, Column *c) {
     return SPK_OK;
 }
 
+// Positional sketch rows (spk_internal.h: pos_bucket and the row layout), one thread per row, the four planes in
+// registers.  Built on first use (spk_gammas), dropped when the column is decoded again.
+__global__ void k_pos_rows(int64_t n, const RecMeta *__restrict__ meta, const uint16_t *__restrict__ units,
+                           uint4 *__restrict__ pos) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= n) return;
+    const RecMeta m = meta[row];
+    const int len = m.len16;
+    if (len < 0 || len >= (int)POS_NONE || meta_cplen(m) != len) {
+        pos[row] = make_uint4(len < 0 ? POS_NULL : POS_NONE, 0u, 0u, 0u);
+        return;
+    }
+    const uint16_t *u = units + meta_off(m);
+    const int half = (len + 1) >> 1;
+    uint32_t lo[2] = {0u, 0u}, hi[2] = {0u, 0u};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        uint32_t l = 0u, g = 0u;
+        for (int i = h ? half : 0; i < (h ? len : half); ++i) {
+            const uint32_t bit = 1u << pos_bucket(u[i]);
+            if (l & g & bit) continue;  // saturated at 3
+            g |= l & bit;               // 1 -> 2 carries into the high plane
+            l ^= bit;                   // 0 -> 1, 1 -> 2, 2 -> 3
+        }
+        lo[h] = l;
+        hi[h] = g;
+    }
+    pos[row] = make_uint4((uint32_t)len | (lo[0] << 8), (lo[0] >> 24) | (hi[0] << 6), (hi[0] >> 26) | (lo[1] << 4),
+                          (lo[1] >> 28) | (hi[1] << 2));
+}
+
+int build_pos_rows(spk_ctx *ctx, int64_t n, Column *c) {
+    SPK_TRY(c->pos.alloc((size_t)(n + 1)));
+    if (n > 0) {
+        k_pos_rows<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(n, c->meta.p, c->units.p, c->pos.p);
+        SPK_HIP(hipGetLastError());
+    }
+    return SPK_OK;
+}
+
 int launch_unit_bits(spk_ctx *ctx, int64_t n, Column *c) {
     c->unit_bits = false;
     c->bag.release();  // the rows changed: built again on first use
+    c->pos.release();
     if (n <= 0) return SPK_OK;
     DevBuf<unsigned int> d;
     SPK_TRY(d.alloc(2));

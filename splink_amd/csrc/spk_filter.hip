@@ -11,7 +11,9 @@
 //              against the smallest threshold: lv_bound) or leaves the cell to the exact pass;
 //   Levenshtein  the distance lies in [max(length gap, bag distance), max length]; the tests that can
 //              still hold for unequal strings are a short chain of integer compares (threshold tables
-//              of the ratio tests in LDS).
+//              of the ratio tests in LDS).  A column without free-text rows carries the positional sketch
+//              instead (FLev.pos): the lower bound is then the largest of the length gap, the bag distance
+//              of the summed halves and the two-segment bag distance (pos_side), which sees character order.
 // The class loops are unrolled to a fixed maximum with wave-uniform guards, so the kernel has no
 // per-column dispatch and keeps every column's parameters in scalar registers.  Cells a bound does
 // not settle go to the column's work list for the exact pass (spk_gamma.hip).
@@ -59,6 +61,7 @@ struct FLev {
     FCommon c;
     int32_t lv_same, lv_same_empty, lv_else;
     int32_t n;  // the chain of tests that can hold for unequal strings
+    int32_t pos;  // the field is a positional sketch row (SimpleCol.pos): lv_same / lv_same_empty are not used
     int32_t kind[MAX_TESTS], a[MAX_TESTS], cmp[MAX_TESTS], level[MAX_TESTS];
     double t[MAX_TESTS];
 };
@@ -257,6 +260,56 @@ template <int FP>
 struct Data16 {
     uint4 a[FP], b[FP];
 };
+
+// The positional sketch field (spk_internal.h): length and the two bit-planes of each half.
+struct PosRow {
+    int n;
+    uint32_t l1, h1, l2, h2;
+};
+__device__ __attribute__((always_inline)) inline PosRow pos_unpack(const uint4 &v) {
+    PosRow r;
+    r.n = (int)(v.x & 0xFFu);
+    r.l1 = __builtin_amdgcn_alignbit(v.y, v.x, 8) & POS_MASK;
+    r.h1 = __builtin_amdgcn_alignbit(v.z, v.y, 6) & POS_MASK;
+    r.l2 = __builtin_amdgcn_alignbit(v.w, v.z, 4) & POS_MASK;
+    r.h2 = v.w >> 2;
+    return r;
+}
+__device__ __attribute__((always_inline)) inline int pos_sum(uint32_t l, uint32_t h) {
+    return __builtin_popcount(l) + 2 * __builtin_popcount(h);
+}
+// Upper bound of the multiset intersection of two strings of la / lb units from their saturating counts, without a
+// case for saturated buckets: the units of a that b cannot match number at least Σ max(0, ca - cb) over the stored
+// counts (a bucket saturated in b hides three or more units, above any unsaturated count of a; one saturated in a
+// holds at least its three; one saturated in both adds 0), so the intersection is at most la - Σ (ca - min(ca, cb))
+// = Σ min + (la - Σ ca), and likewise from b's side.  The result never exceeds la or lb.
+__device__ __attribute__((always_inline)) inline int pos_inter(uint32_t aL, uint32_t aH, uint32_t bL, uint32_t bH,
+                                                               int la, int lb) {
+    const uint32_t gt = (aH & ~bH) | (~(aH ^ bH) & aL & ~bL);
+    const uint32_t mL = (aL & ~gt) | (bL & gt), mH = (aH & ~gt) | (bH & gt);
+    const int ea = la - pos_sum(aL, aH), eb = lb - pos_sum(bL, bH);
+    return pos_sum(mL, mH) + (ea < eb ? ea : eb);
+}
+// The whole row's counts from its halves', saturating at 3 again: a sum below 3 is exact (neither half saturated).
+__device__ __attribute__((always_inline)) inline void pos_whole(const PosRow &r, uint32_t &wL, uint32_t &wH) {
+    const uint32_t hh = r.h1 | r.h2, ll = r.l1 | r.l2;
+    wH = hh | (r.l1 & r.l2);
+    wL = ((r.l1 ^ r.l2) & ~hh) | (r.h1 & r.h2) | (hh & ll);
+}
+// Two-segment bound.  An optimal edit script aligns a's first half a1 with a prefix b[0, j) and its second half a2
+// with b[j, |b|); with j = |b1| + d, d >= 0, the prefix holds b1 and d units of b2, the rest is part of b2, so by the
+// bag bound of each part  lev >= max(Ax, Bx + d) - min(Ix + d, Ax) + max(Ay, By - d) - min(Iy, By - d)  (x = first
+// halves, y = second; A, B lengths, I intersection bounds <= both lengths).  The summands are
+// max(Ax - Ix - d, Bx - Ix, d - (Ax - Bx)) and max(By - Iy - d, Ay - Iy, d - (By - Ay)): each falls, is flat on
+// [Ax - Bx, Ax - Ix] / [By - Ay, By - Iy], then rises, all at slope one, so the sum is convex and smallest where the
+// flats overlap or at the nearer end of the gap between them, clamped to [0, By].  d < 0 is the same with the halves'
+// roles exchanged; the bound is the smaller of the two sides.
+__device__ __attribute__((always_inline)) inline int pos_side(int Ax, int Bx, int Ix, int Ay, int By, int Iy) {
+    const int d1 = Ax - Bx, d2 = By - Ay, d3 = Ax - Ix, d4 = By - Iy;
+    int d = min(max(d1, d2), min(d3, d4));
+    d = min(max(d, 0), By);
+    return max(max(d3 - d, Bx - Ix), d - d1) + max(max(d4 - d, Ay - Iy), d - d2);
+}
 template <int FP>
 __device__ __attribute__((always_inline)) inline void ev_lev(const FLev &L, const int16_t *s_thr, const Data16<FP> &d,
                                                              const bool (&act)[FP], uint32_t (&acc)[FP], bool (&und)[FP]) {
@@ -265,17 +318,41 @@ __device__ __attribute__((always_inline)) inline void ev_lev(const FLev &L, cons
     bool same[FP], nul[FP], bmp[FP], u0[FP];
     int lo[FP], hi[FP], S[FP];
     bool need = false;
+    if (L.pos) {  // kernel-argument (wave-uniform) branch: positional sketch fields
 #pragma unroll
-    for (int u = 0; u < FP; ++u) {
-        same[u] = a[u].x == b[u].x && a[u].y == b[u].y;
-        nul[u] = a[u].y == LENS_NULL || b[u].y == LENS_NULL;
-        const int la = lens_u16(a[u].y), lb = lens_u16(b[u].y), na = lens_cp(a[u].y), nb = lens_cp(b[u].y);
-        u0[u] = (same[u] && L.c.und_same) || la >= LEN_SAT || lb >= LEN_SAT || na >= LEN_SAT || nb >= LEN_SAT;
-        bmp[u] = na == la && nb == lb && !same[u] && !nul[u];  // BMP rows: units are code points (bag bound)
-        need = need || bmp[u];
-        lo[u] = na > nb ? na - nb : nb - na;
-        hi[u] = na > nb ? na : nb;
-        S[u] = na + nb;
+        for (int u = 0; u < FP; ++u) {
+            const PosRow x = pos_unpack(a[u]), y = pos_unpack(b[u]);
+            const int na = x.n, nb = y.n;
+            nul[u] = na == (int)POS_NULL || nb == (int)POS_NULL;
+            const bool none = na >= (int)POS_NONE || nb >= (int)POS_NONE;  // no sketch (or NULL)
+            same[u] = false;  // no key: rows that may be equal are listed (u0)
+            bmp[u] = false;
+            hi[u] = na > nb ? na : nb;
+            S[u] = none ? 0 : na + nb;
+            const int A1 = (na + 1) >> 1, A2 = na >> 1, B1 = (nb + 1) >> 1, B2 = nb >> 1;
+            const int I1 = pos_inter(x.l1, x.h1, y.l1, y.h1, A1, B1), I2 = pos_inter(x.l2, x.h2, y.l2, y.h2, A2, B2);
+            uint32_t awL, awH, bwL, bwH;
+            pos_whole(x, awL, awH);
+            pos_whole(y, bwL, bwH);
+            const int bag = hi[u] - pos_inter(awL, awH, bwL, bwH, na, nb);
+            const int seg = min(pos_side(A1, B1, I1, A2, B2, I2), pos_side(A2, B2, I2, A1, B1, I1));
+            const int gap = na > nb ? na - nb : nb - na;
+            lo[u] = max(max(gap, bag), seg);
+            u0[u] = none || lo[u] == 0;  // every bound 0: equal fields among them
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < FP; ++u) {
+            same[u] = a[u].x == b[u].x && a[u].y == b[u].y;
+            nul[u] = a[u].y == LENS_NULL || b[u].y == LENS_NULL;
+            const int la = lens_u16(a[u].y), lb = lens_u16(b[u].y), na = lens_cp(a[u].y), nb = lens_cp(b[u].y);
+            u0[u] = (same[u] && L.c.und_same) || la >= LEN_SAT || lb >= LEN_SAT || na >= LEN_SAT || nb >= LEN_SAT;
+            bmp[u] = na == la && nb == lb && !same[u] && !nul[u];  // BMP rows: units are code points (bag bound)
+            need = need || bmp[u];
+            lo[u] = na > nb ? na - nb : nb - na;
+            hi[u] = na > nb ? na : nb;
+            S[u] = na + nb;
+        }
     }
     if (__any(need)) {
 #pragma unroll
@@ -651,6 +728,7 @@ static void make_jw(const SimpleCol &s, const GammaArgs &A, FJw &J) {
 
 static void make_lev(const SimpleCol &s, const GammaArgs &A, FLev &L) {
     common(s, A, s.off, L.c);
+    L.pos = s.pos;
     // equal strings: `=` holds, the distance is 0 and its ratio 0.0 (NULL when both are empty: den = 0)
     auto same_level = [&](bool empty) {
         for (int i = 0; i < s.n_tests; ++i) {

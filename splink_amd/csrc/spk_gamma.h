@@ -59,6 +59,9 @@ struct SimpleCol {
     // Bit-planes the Levenshtein scans need: bits np..7 of every plane-row unit of the column (both
     // sides) are the same (Column.unit_or / unit_and), so those planes' match-mask terms are no-ops.
     int32_t np;
+    // SC_LEV: the field is the column's positional sketch row (spk_internal.h: no key, so equal rows go to the
+    // exact pass) instead of {key, lens, sketch}: spk_gammas_set_lev_bound 1 and no free-text rows
+    int32_t pos;
 };
 constexpr int THR_S = 256;
 constexpr int32_t TF_ZERO = 1;     // the value 0.0 passes the test (JW of strings without a common unit; lev ratio 0)
@@ -73,7 +76,8 @@ constexpr int32_t TF_EQ = 16;      // `=` (else `<>`)
 // and the pairs of a second blocking rule land on random rows.  So before the filter pass the
 // fields of every simple column are packed, per row, into one row of a row image (<= IMG_MAX
 // bytes, 16-byte aligned): a pair then reads two rows' lines whatever the number of columns.
-//   SC_EQ   8 B {key u32, lens u32}            SC_LEV 16 B {key, lens, sketch u64}
+//   SC_EQ   8 B {key u32, lens u32}            SC_LEV 16 B {key, lens, sketch u64}, or the positional sketch row
+//                                              (SimpleCol.pos: 8-bit length, two halves x 30 buckets x 2 bits)
 //   SC_JW  16 B {key, lens, sketch} + 8 B head units at off2
 //   SC_NUM 16 B {value f64, valid u32, pad}
 // lens = UTF-16 length | code points << 16, each saturating at LEN_SAT; LENS_NULL = NULL.

@@ -398,6 +398,10 @@ __global__ void k_build_image(int64_t n, const ColDesc *__restrict__ cols, const
             *reinterpret_cast<uint2 *>(img + img_at(rows_img, row, sc.off + 8)) = make_uint2(ok ? 1u : 0u, 0u);
             continue;
         }
+        if (sc.cls == SC_LEV && sc.pos) {
+            *reinterpret_cast<uint4 *>(img + img_at(rows_img, row, sc.off)) = c.pos[row];
+            continue;
+        }
         const RecMeta m = c.meta[row];
         uint32_t lens = LENS_NULL;
         if (m.len16 >= 0) {
@@ -2188,6 +2192,7 @@ static int build_images(spk_ctx *ctx, Table &t0, Table &t1, GammaArgs &A, int64_
             key.push_back(sc.off);
             key.push_back(sc.off2);
             key.push_back(sc.eq4);
+            key.push_back(sc.pos);
         }
         const bool fresh = ctx->img[s].p && ctx->img_key[s] == key;
         SPK_TRY(ctx->img[s].alloc((size_t)(t.n + 1) * (size_t)stride));
@@ -2723,6 +2728,26 @@ extern "C" int spk_gammas(spk_ctx *ctx, int n_cols, const spk_column_program *co
         if (built[0]) SPK_TRY(ensure_desc(ctx, t0));
         if (built[1]) SPK_TRY(ensure_desc(ctx, t1));
     }
+    // positional sketch rows of the other template Levenshtein columns' strings (the filter's two-segment bound),
+    // built on first use
+    {
+        bool built[2] = {false, false};
+        for (SimpleCol &sc : simple) {
+            const bool free_text = sc.kind == SK_STR && t0.cols[sc.col]->planes_hi.n && t1.cols[sc.col]->planes_hi.n;
+            sc.pos = (sc.cls == SC_LEV && sc.kind == SK_STR && ctx->lev_bound == 1 && !free_text) ? 1 : 0;
+            if (!sc.pos) continue;
+            for (int s = 0; s < 2; ++s) {
+                Table &t = s ? t1 : t0;
+                Column *c = t.cols[sc.col];
+                if (c->kind != COL_STR || c->pos.n || t.n <= 0) continue;
+                SPK_TRY(build_pos_rows(ctx, t.n, c));
+                t.desc_dirty = true;
+                built[s] = true;
+            }
+        }
+        if (built[0]) SPK_TRY(ensure_desc(ctx, t0));
+        if (built[1]) SPK_TRY(ensure_desc(ctx, t1));
+    }
     // threshold tables of the Levenshtein-ratio tests (SimpleCol.thr_off)
     std::vector<int16_t> thr_tab;
     for (SimpleCol &sc : simple) {
@@ -2950,7 +2975,7 @@ extern "C" int spk_gammas(spk_ctx *ctx, int n_cols, const spk_column_program *co
         auto ptr = [](const void *q) { return (int64_t)(uintptr_t)q; };
         gkey = {P, n_win, split ? 1 : 0, W, K, ctx->code_bytes, (int64_t)ctx->pairs_epoch, (int64_t)ctx->table_epoch,
                 (int64_t)std::hash<std::string>()(std::string(blob.begin(), blob.end())), ctx->lev_kernel,
-                ctx->lev_bag ? 1 : 0, ctx->filter_mode, ctx->use_views, ctx->slow_force_skip ? 1 : 0,
+                ctx->lev_bag ? 1 : 0, ctx->lev_bound, ctx->filter_mode, ctx->use_views, ctx->slow_force_skip ? 1 : 0,
                 have_view ? 1 : 0, ptr(ctx->stream), ptr(ctx->codes.p), ptr(ctx->pl.p), ptr(ctx->pr.p), ptr(ctx->pvl.p),
                 ptr(ctx->prog_blob.p), ptr(ctx->img[0].p), ptr(ctx->img[1].p), ptr(ctx->work.p), ptr(ctx->xlist.p),
                 ptr(ctx->xinfo.p), ptr(ctx->xpref.p), ptr(ctx->region_count.p), ctx->xcap, ptr(ctx->alt.work.p),
@@ -3426,7 +3451,9 @@ extern "C" int spk_ctx_memory(spk_ctx *ctx, int64_t *out8) {
             for (const DevBuf<int64_t> *k : t.key[w])
                 if (k) m[1] += b(*k);
         for (const Column *c : t.cols)
-            if (c) m[1] += b(c->units) + b(c->meta) + b(c->planes) + b(c->planes_hi) + b(c->bag) + b(c->val) + b(c->valid);
+            if (c)
+                m[1] += b(c->units) + b(c->meta) + b(c->planes) + b(c->planes_hi) + b(c->bag) + b(c->pos) + b(c->val) +
+                        b(c->valid);
     }
     for (int s = 0; s < 2; ++s) {
         m[2] += b(ctx->img[s]);
@@ -3504,6 +3531,12 @@ extern "C" int spk_gammas_set_lev_kernel(spk_ctx *ctx, int mode) {
     SPK_REQUIRE(ctx && mode >= 0 && mode <= 3, SPK_E_INVALID, "spk_gammas_set_lev_kernel: mode 0 .. 3");
     ctx->lev_kernel = mode == 3 ? 2 : mode;
     ctx->lev_bag = mode != 3;
+    return SPK_OK;
+}
+
+extern "C" int spk_gammas_set_lev_bound(spk_ctx *ctx, int mode) {
+    SPK_REQUIRE(ctx && (mode == 0 || mode == 1), SPK_E_INVALID, "spk_gammas_set_lev_bound: mode 0 or 1");
+    ctx->lev_bound = mode;  // SimpleCol.pos follows it: the next spk_gammas lays the row image out again
     return SPK_OK;
 }
 

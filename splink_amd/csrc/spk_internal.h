@@ -94,6 +94,23 @@ __host__ __device__ inline void sketch_add(uint64_t &sk, uint32_t unit) {
     else sk |= lo;                       // 0 -> 1, 2 -> 3
 }
 
+// Positional sketch of a row that a template Levenshtein comparison reads (k_pos_rows, spk_ctx.hip; the filter's
+// bound is in spk_filter.hip): the row's n code points split into the halves [0, ceil(n/2)) and [ceil(n/2), n),
+// each with 30 buckets of saturating 2-bit counts as two bit-planes -- a bucket per ASCII letter (case folded), two
+// for the digits, two for every other unit.  The 16-byte row, as one 128-bit value:
+//   length (8 bits) | half-1 low plane << 8 | half-1 high plane << 38 | half-2 low plane << 68 | half-2 high << 98
+// with length 255 = NULL and 254 = no sketch (254 code points or more, or a surrogate pair: its units are not its
+// code points), which leaves the cell to the exact pass.
+constexpr int POS_BUCKETS = 30;
+constexpr uint32_t POS_MASK = (1u << POS_BUCKETS) - 1u;
+constexpr uint32_t POS_NULL = 255u, POS_NONE = 254u;
+__host__ __device__ inline uint32_t pos_bucket(uint32_t u) {
+    if (u >= 'a' && u <= 'z') return u - 'a';
+    if (u >= 'A' && u <= 'Z') return u - 'A';
+    if (u >= '0' && u <= '9') return 26u + (u & 1u);
+    return 28u + ((u >> 1) & 1u);
+}
+
 struct ColDesc {
     int32_t kind;
     int32_t pad;
@@ -102,6 +119,7 @@ struct ColDesc {
     const uint64_t *planes;  // COL_STR, [n][N_PLANES]
     const uint64_t *planes_hi;  // COL_STR, [n][N_PLANES] units 64..127 (CPF_PLANES2 rows), or null
     const uint4 *bag;        // COL_STR: [n][2] character-bag rows (k_bag_rows), or null (not built)
+    const uint4 *pos;        // COL_STR: [n] positional sketch rows (k_pos_rows), or null (not built)
     const double *val;       // COL_NUM
     const uint8_t *valid;   // COL_NUM
 };
@@ -155,6 +173,8 @@ struct Column {
     DevBuf<uint64_t> planes_hi;  // allocated only when some row has more than 64 UTF-8 bytes
     DevBuf<uint4> bag;           // 32-byte character-bag row per row (k_bag_rows; built when a Levenshtein
                                  // comparison reads the column)
+    DevBuf<uint4> pos;           // 16-byte positional sketch per row (k_pos_rows; built when a template Levenshtein
+                                 // comparison reads a column without free-text rows)
     DevBuf<double> val;
     DevBuf<uint8_t> valid;
     bool has_ids = false;  // COL_STR: RecMeta.key is a dictionary id
@@ -359,6 +379,8 @@ struct spk_ctx {
     bool lev_bag = true;           // k_compact_lev's bag-distance decisions before a refill pass (mode 3: off)
     int lev_kernel = 2;            // Levenshtein exact pass: 0 k_gamma_exact_simple<X_LEV>, 1 k_lev_refill, 2 refill in
                                    // free-text columns (rows past 64 units), one cell per lane elsewhere
+    int lev_bound = 1;             // filter field of template Levenshtein columns without free-text rows: 1 the positional
+                                   // sketch (two-segment bound), 0 key, lengths and whole-string sketch (spk_gammas_set_lev_bound)
     bool slow_force_skip = false;  // tests: leave every slow-list launch to settle_gammas
     uint64_t slow_key_pairs = 0, slow_key_tables = 0;
     spk::DevBuf<unsigned int> region_count;  // [K][regions] filter work-list lengths
@@ -510,6 +532,7 @@ int pattern_mp_table(spk_ctx *ctx, double lambda, double one_minus, const double
 int new_column(spk_ctx *ctx, int side, int col, Column **out);
 int launch_unit_bits(spk_ctx *ctx, int64_t n, Column *c);
 int build_bag_rows(spk_ctx *ctx, int64_t n, Column *c);
+int build_pos_rows(spk_ctx *ctx, int64_t n, Column *c);
 int launch_utf8_decode(spk_ctx *ctx, int64_t n, const int64_t *off8, const int64_t *src_off, const int32_t *perm,
                        const uint8_t *bytes, const uint8_t *valid, Column *c, bool long_rows, const int64_t *ids);
 }
