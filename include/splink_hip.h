@@ -397,6 +397,7 @@ int spk_score(spk_ctx *ctx, double lambda, double one_minus, const double *m, co
  * emit), and only the survivors' ordinals, rows, codes are kept and later decoded. */
 #define SPK_SEL_MP 0          /* match_probability under the parameters passed to spk_select (NaN = NULL) */
 #define SPK_SEL_GAMMA 1       /* level of comparison column `col`, an integer in -1..L-1 (-1 is a value, not NULL) */
+#define SPK_SEL_TF_MP 2       /* tf_adjusted_match_prob of the call's tables (NaN = NULL); spk_select_tf* only */
 #define SPK_SEL_LT 0
 #define SPK_SEL_LE 1
 #define SPK_SEL_GT 2
@@ -407,7 +408,7 @@ int spk_score(spk_ctx *ctx, double lambda, double one_minus, const double *m, co
 #define SPK_SEL_IS_NOT_NULL 7
 #define SPK_SELECT_MAX_TERMS 8
 typedef struct {
-    int32_t field; /* SPK_SEL_MP / SPK_SEL_GAMMA */
+    int32_t field; /* SPK_SEL_MP / SPK_SEL_GAMMA / SPK_SEL_TF_MP */
     int32_t col;   /* comparison column (SPK_SEL_GAMMA) */
     int32_t op;    /* SPK_SEL_LT .. SPK_SEL_IS_NOT_NULL */
     int32_t pad;
@@ -432,6 +433,32 @@ int spk_select_copy(spk_ctx *ctx, int64_t start, int64_t count, int64_t *out_ord
  * emit pass; the host round trip between them is not in it), -1 otherwise. */
 int spk_select_info(spk_ctx *ctx, int64_t *out_n_selected, double *out_ms);
 int spk_select_release(spk_ctx *ctx);
+/* The same with terms on tf_adjusted_match_prob = bayes(mp, adj_1, ..., adj_n) (term_frequencies.py:98-117; replaces
+ * filtering the frame make_adjustment_for_term_frequencies returns).  That score depends on the pair's code (through
+ * mp) and on its two rows (through the tf value ids), so it is decided per pair, as a cascade: the SPK_SEL_MP and
+ * SPK_SEL_GAMMA terms go through the pattern bitset as in spk_select, and only the pairs whose pattern passes them
+ * gather their value ids and table entries and evaluate the SPK_SEL_TF_MP terms (NaN = NULL, three-valued as above).
+ * The value compared and returned is the one spk_tf_apply* gives for the pair under the same tables and the mp of
+ * lambda / m / u, bit for bit (one shared device function).  Value ids and tables as for spk_tf_apply (host ids) and
+ * spk_tf_apply_columns (device dictionary ids); they are used during the call only.  m and u are required, n_tf_cols
+ * is 1..8, terms may mix all three fields (at most SPK_SELECT_MAX_TERMS in total; none with field SPK_SEL_TF_MP is
+ * legal and still yields the tf outputs), and the context needs a pair set with rows (SPK_E_STATE for a loaded gamma
+ * table).  The result is the context's one selection, as after spk_select (spk_select_copy, spk_select_info,
+ * spk_select_release and spk_components work on it), which also holds the survivors' tf_adjusted_match_prob and
+ * adjustments.  Nothing of P elements in fp64 is stored: the count pass keeps one keep bit per pair (P / 8 bytes)
+ * for the emit pass and frees it.  Reads and writes nothing of spk_score's scores, the device-resident tf results of
+ * spk_tf_apply*, the tf sums' state or the EM state.  A failing call leaves no selection. */
+int spk_select_tf(spk_ctx *ctx, double lambda, double one_minus, const double *m, const double *u, int n_tf_cols,
+                  const int64_t *const *ids_side0, const int64_t *const *ids_side1, const double *const *adj_tables,
+                  const int64_t *table_sizes, int n_terms, const spk_select_term *terms, int64_t *out_n_selected);
+int spk_select_tf_columns(spk_ctx *ctx, double lambda, double one_minus, const double *m, const double *u,
+                          int n_tf_cols, const int32_t *cols, const double *const *adj_tables,
+                          const int64_t *table_sizes, int n_terms, const spk_select_term *terms,
+                          int64_t *out_n_selected);
+/* Survivors [start, start + count) of the last spk_select_tf*: tf_adjusted_match_prob and the adjustments
+ * (either may be NULL).  SPK_E_STATE after a plain spk_select, without a selection, or for a stale one. */
+int spk_select_copy_tf(spk_ctx *ctx, int64_t start, int64_t count, double *out_tf_mp,
+                       double *out_adj /* [count x n_tf_cols] or NULL */);
 
 /* ---- connected components of the kept pairs (replaces handing df_e.filter(...) to GraphFrames'
  *      connectedComponents; later reference releases: cluster_pairwise_predictions_at_threshold) ---- */

@@ -38,6 +38,7 @@ SELECT_TERM_DTYPE = np.dtype([("field", "<i4"), ("col", "<i4"), ("op", "<i4"), (
                              align=True)
 assert SELECT_TERM_DTYPE.itemsize == 24
 SEL_MP, SEL_GAMMA = 0, 1  # SPK_SEL_MP, SPK_SEL_GAMMA
+SEL_TF_MP = 2  # SPK_SEL_TF_MP: tf_adjusted_match_prob (select_tf / select_tf_columns only)
 SEL_OP = {"<": 0, "<=": 1, ">": 2, ">=": 3, "=": 4, "!=": 5, "is null": 6, "is not null": 7}  # SPK_SEL_LT ..
 SELECT_MAX_TERMS = 8  # SPK_SELECT_MAX_TERMS
 # Pair ordinals per count of the selection's compaction.  Mirrored from SEL_CHUNK in csrc/spk_select.hip (the
@@ -70,6 +71,7 @@ EXPORTS = [
     "spk_gammas_set_lev_kernel", "spk_gammas_set_lev_bound",
     "spk_block_residual", "spk_block_residual_info",
     "spk_select", "spk_select_copy", "spk_select_info", "spk_select_release",
+    "spk_select_tf", "spk_select_tf_columns", "spk_select_copy_tf",
     "spk_components", "spk_components_edges", "spk_components_copy", "spk_components_info", "spk_components_release",
 ]
 TF_LIMBS = 14  # SPK_TF_LIMBS
@@ -554,6 +556,65 @@ class Context:
                                    ctypes.c_int(len(t)), _ptr(t) if len(t) else ctypes.c_void_p(0), ctypes.byref(n)),
               "spk_select")
         return n.value
+
+    @staticmethod
+    def _select_terms(terms):
+        t = np.zeros(len(terms), dtype=SELECT_TERM_DTYPE)
+        for i, (field, col, op, value) in enumerate(terms):
+            t[i] = (field, col, op, 0, value)
+        return t
+
+    def select_tf(self, lam, one_minus, m, u, ids0_list, ids1_list, tables, terms) -> int:
+        """spk_select_tf: select as `select`, with terms on tf_adjusted_match_prob (field SEL_TF_MP) under the given
+        host value ids per row and adjustment tables (as tf_apply); returns how many pairs are kept."""
+        n = len(tables)
+        keep = [np.ascontiguousarray(a, dtype=np.int64) for a in ids0_list] + \
+               [np.ascontiguousarray(a, dtype=np.int64) for a in ids1_list] + \
+               [np.ascontiguousarray(t, dtype=np.float64) if len(t) else np.zeros(1) for t in tables]
+        if len(ids0_list) != n or len(ids1_list) != n:
+            raise ValueError("select_tf: one id array per side and table")
+        P = ctypes.c_void_p * max(n, 1)
+        ids0 = P(*[a.ctypes.data for a in keep[:n]])
+        ids1 = P(*[a.ctypes.data for a in keep[n:2 * n]])
+        tabs = P(*[a.ctypes.data for a in keep[2 * n:]])
+        sizes = np.array([len(t) for t in tables] + [0], dtype=np.int64)
+        t = self._select_terms(terms)
+        m = np.ascontiguousarray(m, dtype=np.float64)
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        k = ctypes.c_int64(0)
+        check(self._lib.spk_select_tf(self._h, ctypes.c_double(lam), ctypes.c_double(one_minus), _ptr(m), _ptr(u),
+                                      ctypes.c_int(n), ids0, ids1, tabs, _ptr(sizes), ctypes.c_int(len(t)),
+                                      _ptr(t) if len(t) else ctypes.c_void_p(0), ctypes.byref(k)), "spk_select_tf")
+        return k.value
+
+    def select_tf_columns(self, lam, one_minus, m, u, cols, tables, terms) -> int:
+        """spk_select_tf_columns: the same with the value ids taken from the device dictionary ids of the string
+        columns `cols` (as tf_apply_columns)."""
+        n = len(tables)
+        if len(cols) != n:
+            raise ValueError("select_tf_columns: one column per table")
+        keep = [np.ascontiguousarray(t, dtype=np.float64) if len(t) else np.zeros(1) for t in tables]
+        tabs = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in keep])
+        sizes = np.array([len(t) for t in tables] + [0], dtype=np.int64)
+        cols = np.ascontiguousarray(list(cols) + [0], dtype=np.int32)
+        t = self._select_terms(terms)
+        m = np.ascontiguousarray(m, dtype=np.float64)
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        k = ctypes.c_int64(0)
+        check(self._lib.spk_select_tf_columns(self._h, ctypes.c_double(lam), ctypes.c_double(one_minus), _ptr(m), _ptr(u),
+                                              ctypes.c_int(n), _ptr(cols), tabs, _ptr(sizes), ctypes.c_int(len(t)),
+                                              _ptr(t) if len(t) else ctypes.c_void_p(0), ctypes.byref(k)),
+              "spk_select_tf_columns")
+        return k.value
+
+    def select_copy_tf(self, start: int, count: int, n_tf: int, adj=True):
+        """Survivors [start, start + count) of the last select_tf*: (tf_adjusted_match_prob, adjustments
+        [count, n_tf] or None)."""
+        out = np.empty(count, dtype=np.float64)
+        a = np.empty((count, n_tf), dtype=np.float64) if adj else None
+        check(self._lib.spk_select_copy_tf(self._h, ctypes.c_int64(start), ctypes.c_int64(count), _ptr(out), _ptr(a)),
+              "spk_select_copy_tf")
+        return out, a
 
     def select_copy(self, start: int, count: int, K: int, rows=True, gammas=True, mp=True):
         """Survivors [start, start + count) of the last select: (ordinal int64, l, r int32 or None, gammas int8

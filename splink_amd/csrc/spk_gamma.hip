@@ -3469,6 +3469,7 @@ extern "C" int spk_ctx_memory(spk_ctx *ctx, int64_t *out8) {
            b(ctx->tf_nruns) + b(ctx->tf_mp) + b(ctx->tf_hist) +
            b(ctx->tf_sort) +
            b(ctx->sel.ord) + b(ctx->sel.l) + b(ctx->sel.r) + b(ctx->sel.code) + b(ctx->sel.mpat) +
+           b(ctx->sel.tf_mp) + b(ctx->sel.adj) +
            b(ctx->comp.label);
     for (int i = 0; i < 7; ++i) m[7] += m[i];
     for (int i = 0; i < 8; ++i) out8[i] = m[i];

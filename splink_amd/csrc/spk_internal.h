@@ -254,6 +254,11 @@ struct Selection {
     DevBuf<uint32_t> code;   // its packed comparison code
     DevBuf<double> mpat;     // mp per pattern under spk_select's parameters (has_mp)
     bool has_rows = false, has_mp = false;
+    // spk_select_tf*: the survivors' tf_adjusted_match_prob and their n_tf adjustments [n x n_tf] under that call's
+    // tables (which are gone when it returns)
+    bool has_tf = false;
+    int n_tf = 0;
+    DevBuf<double> tf_mp, adj;
     int K = 0;
     std::vector<int32_t> n_levels;
     std::vector<int64_t> stride;

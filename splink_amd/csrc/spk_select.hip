@@ -12,10 +12,18 @@
 // pairs) per slab, the wave's lanes hold consecutive pairs, and for element j of every lane one ballot gives the
 // kept pairs of the slab at that element; a pair's position is the popcounts of those ballots below its lane plus
 // the kept elements before it in its own lane.
+//
+// spk_select_tf* adds terms on tf_adjusted_match_prob, which is a function of the pair's code (through mp) and of its
+// two rows (through the tf value ids), so it is decided per pair, as a cascade: the pattern stage above is unchanged
+// and a pair whose pattern fails it gathers nothing; k_select_tf_count evaluates the tf terms of the pattern-kept
+// pairs (tf_pair's arithmetic, spk_tf_pair.h), counts, and writes one 64-bit ballot word per (chunk, slab, element):
+// a keep bitmap of P / 8 bytes.  k_select_tf_emit takes the ranks from those words and recomputes
+// tf_adjusted_match_prob and the adjustments for the survivors only.
 #include <algorithm>
 #include <cmath>
 
 #include "spk_prim.h"
+#include "spk_tf_pair.h"
 
 namespace spk {
 
@@ -27,6 +35,7 @@ constexpr int64_t SEL_LDS_PAT = 1 << 18;  // keep bitset in LDS up to this many 
 constexpr int SEL_MAXK = 64;            // PatArgs' column limit
 
 typedef uint32_t sel_u32x4 __attribute__((ext_vector_type(4)));
+typedef int32_t sel_i32x4 __attribute__((ext_vector_type(4)));
 
 struct SelPatArgs {
     int K, n_terms;
@@ -90,6 +99,38 @@ struct SelectArgs {
     uint32_t *out_code;
 };
 
+// The codes of the chunk at ordinal `base`, 16 bytes per lane and slab (lane's pairs are consecutive).
+template <typename CodeT>
+__device__ inline void sel_load_chunk(const CodeT *__restrict__ codes, int64_t base, int64_t P, int lane,
+                                      sel_u32x4 (&v)[SEL_CHUNK / (64 * (16 / (int)sizeof(CodeT)))]) {
+    constexpr int V = 16 / (int)sizeof(CodeT);
+    constexpr int SLABS = (int)(SEL_CHUNK / (64 * V));
+    if (base + SEL_CHUNK <= P) {  // whole chunk: every lane's 16 bytes lie inside the codes (wave-uniform)
+        const sel_u32x4 *src = reinterpret_cast<const sel_u32x4 *>(codes + base);
+#pragma unroll
+        for (int s = 0; s < SLABS; ++s) v[s] = __builtin_nontemporal_load(src + s * 64 + lane);
+    } else {  // the last chunk: code by code, zero past the end (masked out by the ordinal where it is used)
+#pragma unroll
+        for (int s = 0; s < SLABS; ++s) {
+            uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const int64_t p = base + ((int64_t)s * 64 + lane) * V + j;
+                const uint32_t x = p < P ? (uint32_t)codes[p] : 0u;
+                if (sizeof(CodeT) == 2) w[j >> 1] |= x << (16 * (j & 1));
+                else w[j] = x;
+            }
+            v[s] = sel_u32x4{w[0], w[1], w[2], w[3]};
+        }
+    }
+}
+
+// Code j of a lane's slab vector.
+template <typename CodeT>
+__device__ inline uint32_t sel_code(const sel_u32x4 &v, int j) {
+    return sizeof(CodeT) == 2 ? (v[j >> 1] >> (16 * (j & 1))) & 0xFFFFu : v[j];
+}
+
 template <typename CodeT, bool LDS, bool EMIT>
 __global__ __launch_bounds__(SEL_THREADS) void k_select(SelectArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_keep[];
@@ -112,24 +153,7 @@ __global__ __launch_bounds__(SEL_THREADS) void k_select(SelectArgs A) {
         }
         const int64_t base = c * SEL_CHUNK;
         sel_u32x4 v[SLABS];
-        if (base + SEL_CHUNK <= A.P) {  // whole chunk: every lane's 16 bytes lie inside the codes (wave-uniform)
-            const sel_u32x4 *src = reinterpret_cast<const sel_u32x4 *>(codes + base);
-#pragma unroll
-            for (int s = 0; s < SLABS; ++s) v[s] = __builtin_nontemporal_load(src + s * 64 + lane);
-        } else {  // the last chunk: code by code, zero past the end (masked out below by the ordinal)
-#pragma unroll
-            for (int s = 0; s < SLABS; ++s) {
-                uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                for (int j = 0; j < V; ++j) {
-                    const int64_t p = base + ((int64_t)s * 64 + lane) * V + j;
-                    const uint32_t x = p < A.P ? (uint32_t)codes[p] : 0u;
-                    if (sizeof(CodeT) == 2) w[j >> 1] |= x << (16 * (j & 1));
-                    else w[j] = x;
-                }
-                v[s] = sel_u32x4{w[0], w[1], w[2], w[3]};
-            }
-        }
+        sel_load_chunk<CodeT>(codes, base, A.P, lane, v);
         int wave_total = 0;
 #pragma unroll
         for (int s = 0; s < SLABS; ++s) {
@@ -138,7 +162,7 @@ __global__ __launch_bounds__(SEL_THREADS) void k_select(SelectArgs A) {
             unsigned km = 0;
 #pragma unroll
             for (int j = 0; j < V; ++j) {
-                const uint32_t x = sizeof(CodeT) == 2 ? (v[s][j >> 1] >> (16 * (j & 1))) & 0xFFFFu : v[s][j];
+                const uint32_t x = sel_code<CodeT>(v[s], j);
                 code[j] = x;
                 const bool k = p0 + j < A.P && (int64_t)x < A.n_pat && ((T[x >> 5] >> (x & 31u)) & 1u);
                 km |= (k ? 1u : 0u) << j;
@@ -174,6 +198,208 @@ __global__ __launch_bounds__(SEL_THREADS) void k_select(SelectArgs A) {
     }
 }
 
+// What the tf kernels need beyond SelectArgs: the call's id arrays and tables, the selection's own mp per pattern
+// (never ctx->mp), the SPK_SEL_TF_MP terms, the keep bitmap and the survivors' tf outputs.
+struct SelTfArgs {
+    TfApply T;
+    const double *mpat;
+    int n_terms;
+    int32_t op[SPK_SELECT_MAX_TERMS];
+    double value[SPK_SELECT_MAX_TERMS];
+    unsigned long long *bitmap;  // [n_chunks x SEL_CHUNK / 64]: word (chunk, slab, element) = the ballot of its 64 pairs
+    double *out_tf, *out_adj;    // emit pass: [n_sel], [n_sel x T.n]
+};
+
+// The pattern-kept pairs of a lane's slab as a mask over its V elements (k_select's test).
+template <typename CodeT>
+__device__ inline unsigned sel_pattern_mask(const sel_u32x4 &v, int64_t p0, int64_t P, int64_t n_pat,
+                                            const uint32_t *__restrict__ T, uint32_t (&code)[16 / (int)sizeof(CodeT)]) {
+    constexpr int V = 16 / (int)sizeof(CodeT);
+    unsigned km = 0;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        const uint32_t x = sel_code<CodeT>(v, j);
+        code[j] = x;
+        const bool k = p0 + j < P && (int64_t)x < n_pat && ((T[x >> 5] >> (x & 31u)) & 1u);
+        km |= (k ? 1u : 0u) << j;
+    }
+    return km;
+}
+
+// Count pass with tf terms.  Chunk, slab and lane layout of k_select.  A slab none of whose pairs passed the
+// pattern stage gathers nothing; otherwise the lanes load their pairs' rows (consecutive: 16-byte vectors), and for
+// the pattern-kept pairs, column by column, the value ids of every element, then the table entries, then the fold:
+// the loads of all elements are issued before the first is used.  One ballot per element gives the chunk count and
+// the bitmap word.
+template <typename CodeT, bool LDS>
+__global__ __launch_bounds__(SEL_THREADS) void k_select_tf_count(SelectArgs A, SelTfArgs F) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_keep[];
+    if (LDS) {
+        for (int i = threadIdx.x; i < A.keep_words; i += SEL_THREADS) s_keep[i] = A.keep[i];
+        __syncthreads();
+    }
+    const uint32_t *T = LDS ? s_keep : A.keep;
+    constexpr int V = 16 / (int)sizeof(CodeT);
+    constexpr int SLABS = (int)(SEL_CHUNK / (64 * V));
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const CodeT *codes = reinterpret_cast<const CodeT *>(A.codes);
+    const int64_t n_waves = (int64_t)gridDim.x * SEL_WAVES;
+    for (int64_t c = (int64_t)blockIdx.x * SEL_WAVES + wave; c < A.n_chunks; c += n_waves) {
+        const int64_t base = c * SEL_CHUNK;
+        const bool whole = base + SEL_CHUNK <= A.P;  // wave-uniform
+        unsigned long long *words = F.bitmap + c * (SEL_CHUNK / 64);
+        sel_u32x4 v[SLABS];
+        sel_load_chunk<CodeT>(codes, base, A.P, lane, v);
+        int wave_total = 0;
+#pragma unroll
+        for (int s = 0; s < SLABS; ++s) {
+            const int64_t p0 = base + ((int64_t)s * 64 + lane) * V;  // this lane's first pair of the slab
+            uint32_t code[V];
+            const unsigned km = sel_pattern_mask<CodeT>(v[s], p0, A.P, A.n_pat, T, code);
+            if (__ballot(km != 0u) == 0ull) {  // wave-uniform: nothing to gather
+                if (lane == 0) {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) words[s * V + j] = 0ull;
+                }
+                continue;
+            }
+            int32_t l[V], r[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) l[j] = r[j] = 0;
+            if (km != 0u) {
+                if (whole) {  // p0 is a multiple of V >= 4: 16-byte aligned, and p0 + V <= P
+                    const sel_i32x4 *L = reinterpret_cast<const sel_i32x4 *>(A.pl + p0);
+                    const sel_i32x4 *R = reinterpret_cast<const sel_i32x4 *>(A.pr + p0);
+#pragma unroll
+                    for (int q = 0; q < V / 4; ++q) {
+                        const sel_i32x4 xl = __builtin_nontemporal_load(L + q), xr = __builtin_nontemporal_load(R + q);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            l[4 * q + e] = xl[e];
+                            r[4 * q + e] = xr[e];
+                        }
+                    }
+                } else {  // the last chunk: a kept element lies below P
+#pragma unroll
+                    for (int j = 0; j < V; ++j)
+                        if ((km >> j) & 1u) {
+                            l[j] = __builtin_nontemporal_load(A.pl + p0 + j);
+                            r[j] = __builtin_nontemporal_load(A.pr + p0 + j);
+                        }
+                }
+            }
+            double m[V], a[V], b[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                m[j] = (km >> j) & 1u ? F.mpat[code[j]] : 0.0;  // code < n_pat: the pattern mask checked it
+                tf_begin(m[j], a[j], b[j]);
+            }
+            for (int t = 0; t < F.T.n; ++t) {
+                const int64_t *__restrict__ i0 = F.T.ids0[t];
+                const int64_t *__restrict__ i1 = F.T.ids1[t];
+                const double *__restrict__ tab = F.T.tab[t];
+                const int64_t tab_n = F.T.tab_n[t];
+                int64_t ia[V], ib[V];
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    ia[j] = ib[j] = -1;
+                    if ((km >> j) & 1u) {
+                        ia[j] = i0[l[j]];
+                        ib[j] = i1[r[j]];
+                    }
+                }
+                double x[V];
+#pragma unroll
+                for (int j = 0; j < V; ++j) x[j] = tf_adj(ia[j], ib[j], tab, tab_n);  // -1: no load
+#pragma unroll
+                for (int j = 0; j < V; ++j) tf_fold(a[j], b[j], x[j]);
+            }
+            unsigned kt = 0;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const double tf = tf_finish(m[j], a[j], b[j]);
+                bool k = (km >> j) & 1u;
+                for (int t = 0; t < F.n_terms; ++t) k = k && sel_term_true(F.op[t], tf != tf, tf, F.value[t]);
+                kt |= (k ? 1u : 0u) << j;
+            }
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const unsigned long long w = __ballot((kt >> j) & 1u);
+                wave_total += __popcll(w);
+                if (lane == 0) words[s * V + j] = w;
+            }
+        }
+        if (lane == 0) A.chunk_count[c] = wave_total;
+    }
+}
+
+// Emit pass of a selection with tf tables: k_select's outputs, and for the survivors tf_adjusted_match_prob and the
+// adjustments, recomputed with tf_pair.  BITMAP: the kept pairs are the count pass's bitmap words (there were tf
+// terms); otherwise the pattern bitset decides, as in k_select.
+template <typename CodeT, bool LDS, bool BITMAP>
+__global__ __launch_bounds__(SEL_THREADS) void k_select_tf_emit(SelectArgs A, SelTfArgs F) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_keep[];
+    if (LDS && !BITMAP) {
+        for (int i = threadIdx.x; i < A.keep_words; i += SEL_THREADS) s_keep[i] = A.keep[i];
+        __syncthreads();
+    }
+    const uint32_t *T = LDS ? s_keep : A.keep;
+    constexpr int V = 16 / (int)sizeof(CodeT);
+    constexpr int SLABS = (int)(SEL_CHUNK / (64 * V));
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const CodeT *codes = reinterpret_cast<const CodeT *>(A.codes);
+    const int64_t n_waves = (int64_t)gridDim.x * SEL_WAVES;
+    for (int64_t c = (int64_t)blockIdx.x * SEL_WAVES + wave; c < A.n_chunks; c += n_waves) {
+        int64_t run = A.chunk_off[c];
+        if (A.chunk_off[c + 1] == run) continue;  // nothing kept here (wave-uniform)
+        const int64_t base = c * SEL_CHUNK;
+        const unsigned long long *words = BITMAP ? F.bitmap + c * (SEL_CHUNK / 64) : nullptr;
+        sel_u32x4 v[SLABS];
+        sel_load_chunk<CodeT>(codes, base, A.P, lane, v);
+#pragma unroll
+        for (int s = 0; s < SLABS; ++s) {
+            const int64_t p0 = base + ((int64_t)s * 64 + lane) * V;
+            uint32_t code[V];
+            unsigned km = 0;
+            int before = 0, all = 0;
+            if (BITMAP) {
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    code[j] = sel_code<CodeT>(v[s], j);
+                    const unsigned long long w = words[s * V + j];
+                    km |= (unsigned)((w >> lane) & 1ull) << j;
+                    all += __popcll(w);
+                    before += __popcll(w & below);
+                }
+            } else {
+                km = sel_pattern_mask<CodeT>(v[s], p0, A.P, A.n_pat, T, code);
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const unsigned long long w = __ballot((km >> j) & 1u);
+                    all += __popcll(w);
+                    before += __popcll(w & below);
+                }
+            }
+            int64_t q = run + before;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                if ((km >> j) & 1u) {
+                    const int64_t p = p0 + j;
+                    const int32_t l = __builtin_nontemporal_load(A.pl + p), r = __builtin_nontemporal_load(A.pr + p);
+                    A.out_ord[q] = p;
+                    A.out_code[q] = code[j];
+                    A.out_l[q] = l;
+                    A.out_r[q] = r;
+                    F.out_tf[q] = tf_pair(F.T, F.mpat[code[j]], l, r, F.out_adj + q * F.T.n);
+                    ++q;
+                }
+            }
+            run += all;
+        }
+    }
+}
+
 struct SelDecodeArgs {
     int64_t start, count;
     int K;
@@ -195,12 +421,17 @@ __global__ __launch_bounds__(256) void k_select_decode(SelDecodeArgs A) {
     if (A.out_mp) A.out_mp[i] = A.mpat[c];
 }
 
+// The grid of every per-pair kernel here: capped, the waves stride over the chunks.
+static unsigned select_grid(spk_ctx *ctx, int64_t n_chunks) {
+    int64_t g = (n_chunks + SEL_WAVES - 1) / SEL_WAVES;
+    return (unsigned)std::max<int64_t>(std::min<int64_t>(g, SEL_WG_PER_CU * (int64_t)ctx->n_cu), 1);
+}
+
 template <typename CodeT, bool EMIT>
 static int launch_select(spk_ctx *ctx, const SelectArgs &A, bool lds) {
-    int64_t g = (A.n_chunks + SEL_WAVES - 1) / SEL_WAVES;
-    g = std::max<int64_t>(std::min<int64_t>(g, SEL_WG_PER_CU * (int64_t)ctx->n_cu), 1);
-    if (lds) k_select<CodeT, true, EMIT><<<(unsigned)g, SEL_THREADS, (size_t)A.keep_words * 4, ctx->stream>>>(A);
-    else k_select<CodeT, false, EMIT><<<(unsigned)g, SEL_THREADS, 0, ctx->stream>>>(A);
+    const unsigned g = select_grid(ctx, A.n_chunks);
+    if (lds) k_select<CodeT, true, EMIT><<<g, SEL_THREADS, (size_t)A.keep_words * 4, ctx->stream>>>(A);
+    else k_select<CodeT, false, EMIT><<<g, SEL_THREADS, 0, ctx->stream>>>(A);
     SPK_HIP(hipGetLastError());
     return SPK_OK;
 }
@@ -210,20 +441,54 @@ static int launch_select_codes(spk_ctx *ctx, const SelectArgs &A, bool lds) {
     return ctx->code_bytes == 2 ? launch_select<uint16_t, EMIT>(ctx, A, lds) : launch_select<uint32_t, EMIT>(ctx, A, lds);
 }
 
-// The selection into S (a local of spk_select: a failure on the way leaves the context without one).
+template <typename CodeT>
+static int launch_tf_count(spk_ctx *ctx, const SelectArgs &A, const SelTfArgs &F, bool lds) {
+    const unsigned g = select_grid(ctx, A.n_chunks);
+    if (lds) k_select_tf_count<CodeT, true><<<g, SEL_THREADS, (size_t)A.keep_words * 4, ctx->stream>>>(A, F);
+    else k_select_tf_count<CodeT, false><<<g, SEL_THREADS, 0, ctx->stream>>>(A, F);
+    SPK_HIP(hipGetLastError());
+    return SPK_OK;
+}
+
+template <typename CodeT>
+static int launch_tf_emit(spk_ctx *ctx, const SelectArgs &A, const SelTfArgs &F, bool lds, bool bitmap) {
+    const unsigned g = select_grid(ctx, A.n_chunks);
+    if (bitmap) k_select_tf_emit<CodeT, false, true><<<g, SEL_THREADS, 0, ctx->stream>>>(A, F);
+    else if (lds) k_select_tf_emit<CodeT, true, false><<<g, SEL_THREADS, (size_t)A.keep_words * 4, ctx->stream>>>(A, F);
+    else k_select_tf_emit<CodeT, false, false><<<g, SEL_THREADS, 0, ctx->stream>>>(A, F);
+    SPK_HIP(hipGetLastError());
+    return SPK_OK;
+}
+
+// The selection into S (a local of spk_select*: a failure on the way leaves the context without one).  tf: the staged
+// id arrays and tables of spk_select_tf* (the SPK_SEL_TF_MP terms are evaluated per pair, the others per pattern), or
+// null for spk_select.
 static int build_selection(spk_ctx *ctx, double lambda, double one_minus, const double *m, const double *u, int n_terms,
-                           const spk_select_term *terms, Selection &S) {
+                           const spk_select_term *terms, const TfApply *tf, Selection &S) {
     const int64_t P = ctx->n_pairs, n_pat = ctx->n_patterns;
     const int K = ctx->K;
     SelPatArgs PA{};
+    SelTfArgs F{};
     PA.K = K;
-    PA.n_terms = n_terms;
     PA.n_pat = n_pat;
     for (int k = 0; k < K; ++k) {
         PA.stride[k] = (int32_t)ctx->stride[k];
         PA.nlev[k] = (uint8_t)ctx->n_levels[k];
     }
-    for (int t = 0; t < n_terms; ++t) PA.terms[t] = terms[t];
+    for (int t = 0; t < n_terms; ++t) {
+        if (terms[t].field == SPK_SEL_TF_MP) {
+            F.op[F.n_terms] = terms[t].op;
+            F.value[F.n_terms++] = terms[t].value;
+        } else {
+            PA.terms[PA.n_terms++] = terms[t];
+        }
+    }
+    const bool tf_terms = F.n_terms > 0;
+    if (tf) {
+        F.T = *tf;
+        S.has_tf = true;
+        S.n_tf = tf->n;
+    }
     S.K = K;
     S.n_levels = ctx->n_levels;
     S.stride = ctx->stride;
@@ -248,10 +513,14 @@ static int build_selection(spk_ctx *ctx, double lambda, double one_minus, const 
     DevBuf<unsigned long long> keep;
     DevBuf<uint8_t> tmp;
     CountScan chunks;
+    DevBuf<unsigned long long> bitmap;  // per-pair keep bits of the tf count pass: P / 8 bytes, gone at return
     SPK_TRY(keep.alloc((size_t)words64 + 1));
     if (S.has_mp) SPK_TRY(S.mpat.alloc((size_t)n_pat + 1));
     const int64_t n_chunks = (P + SEL_CHUNK - 1) / SEL_CHUNK;
     SPK_TRY(chunks.alloc(ctx, n_chunks));
+    if (tf_terms) SPK_TRY(bitmap.alloc((size_t)(n_chunks * (SEL_CHUNK / 64)) + 1));
+    F.mpat = S.mpat.p;
+    F.bitmap = bitmap.p;
     // ---- per pattern: mp table, keep bitset; per chunk: the kept pairs; their scan
     if (ctx->timing) SPK_HIP(hipEventRecord(ctx->sel_ev0, ctx->stream));
     if (S.has_mp) SPK_TRY(pattern_mp_table(ctx, lambda, one_minus, m, u, S.mpat.p));
@@ -272,7 +541,9 @@ static int build_selection(spk_ctx *ctx, double lambda, double one_minus, const 
     const bool lds = n_pat <= SEL_LDS_PAT;
     if (n_chunks > 0) {
         A.chunk_count = chunks.count.p;
-        SPK_TRY(launch_select_codes<false>(ctx, A, lds));
+        if (!tf_terms) SPK_TRY(launch_select_codes<false>(ctx, A, lds));
+        else if (ctx->code_bytes == 2) SPK_TRY(launch_tf_count<uint16_t>(ctx, A, F, lds));
+        else SPK_TRY(launch_tf_count<uint32_t>(ctx, A, F, lds));
     }
     SPK_TRY(scan_total(ctx, chunks, tmp, ctx->timing ? ctx->sel_ev1 : nullptr));  // synchronises
     SPK_TRY(lap());
@@ -285,6 +556,12 @@ static int build_selection(spk_ctx *ctx, double lambda, double one_minus, const 
         SPK_TRY(S.l.alloc((size_t)n_sel + 1));
         SPK_TRY(S.r.alloc((size_t)n_sel + 1));
     }
+    if (tf) {
+        SPK_TRY(S.tf_mp.alloc((size_t)n_sel + 1));
+        SPK_TRY(S.adj.alloc((size_t)n_sel * tf->n + 1));
+        F.out_tf = S.tf_mp.p;
+        F.out_adj = S.adj.p;
+    }
     if (n_sel > 0) {
         A.chunk_count = nullptr;
         A.chunk_off = chunks.off.p;
@@ -293,7 +570,9 @@ static int build_selection(spk_ctx *ctx, double lambda, double one_minus, const 
         A.out_l = S.l.p;
         A.out_r = S.r.p;
         if (ctx->timing) SPK_HIP(hipEventRecord(ctx->sel_ev0, ctx->stream));
-        SPK_TRY(launch_select_codes<true>(ctx, A, lds));
+        if (!tf) SPK_TRY(launch_select_codes<true>(ctx, A, lds));
+        else if (ctx->code_bytes == 2) SPK_TRY(launch_tf_emit<uint16_t>(ctx, A, F, lds, tf_terms));
+        else SPK_TRY(launch_tf_emit<uint32_t>(ctx, A, F, lds, tf_terms));
         if (ctx->timing) SPK_HIP(hipEventRecord(ctx->sel_ev1, ctx->stream));
         SPK_HIP(hipStreamSynchronize(ctx->stream));
         SPK_TRY(lap());
@@ -308,32 +587,107 @@ static int build_selection(spk_ctx *ctx, double lambda, double one_minus, const 
 
 using namespace spk;
 
-extern "C" int spk_select(spk_ctx *ctx, double lambda, double one_minus, const double *m, const double *u,
-                          int n_terms, const spk_select_term *terms, int64_t *out_n_selected) {
-    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_select: null ctx");
+// What spk_select and spk_select_tf* check alike, after dropping the previous selection: the arguments first
+// (SPK_E_INVALID), then the state.  tf: SPK_SEL_TF_MP terms are legal, m / u are required, and so is a pair set with
+// rows.
+static int select_begin(spk_ctx *ctx, const char *what, const double *m, const double *u, int n_terms,
+                        const spk_select_term *terms, bool tf) {
+    const std::string w(what);
+    SPK_REQUIRE(ctx, SPK_E_INVALID, w + ": null ctx");
     SPK_HIP(hipSetDevice(ctx->device));
     ctx->sel.clear();  // whatever happens below, the previous selection is gone
     SPK_REQUIRE(n_terms >= 0 && n_terms <= SPK_SELECT_MAX_TERMS, SPK_E_INVALID,
-                "spk_select: at most SPK_SELECT_MAX_TERMS (8) terms");
-    SPK_REQUIRE(n_terms == 0 || terms, SPK_E_INVALID, "spk_select: null terms");
-    SPK_REQUIRE((m == nullptr) == (u == nullptr), SPK_E_INVALID, "spk_select: m and u come together");
-    SPK_REQUIRE(ctx->codes_valid, SPK_E_STATE, "spk_select: no gammas");
+                w + ": at most SPK_SELECT_MAX_TERMS (8) terms");
+    SPK_REQUIRE(n_terms == 0 || terms, SPK_E_INVALID, w + ": null terms");
+    SPK_REQUIRE((m == nullptr) == (u == nullptr), SPK_E_INVALID, w + ": m and u come together");
+    SPK_REQUIRE(!tf || (m && u), SPK_E_INVALID, w + ": m and u are required");
+    SPK_REQUIRE(ctx->codes_valid, SPK_E_STATE, w + ": no gammas");
     SPK_TRY(settle_gammas(ctx, nullptr));
-    SPK_REQUIRE(ctx->codes_valid, SPK_E_STATE, "spk_select: no gammas");
-    SPK_REQUIRE(ctx->K <= SEL_MAXK, SPK_E_LIMIT, "spk_select: too many comparison columns");
+    SPK_REQUIRE(ctx->codes_valid, SPK_E_STATE, w + ": no gammas");
+    SPK_REQUIRE(ctx->K <= SEL_MAXK, SPK_E_LIMIT, w + ": too many comparison columns");
     for (int t = 0; t < n_terms; ++t) {
         const spk_select_term &T = terms[t];
-        SPK_REQUIRE(T.field == SPK_SEL_MP || T.field == SPK_SEL_GAMMA, SPK_E_INVALID, "spk_select: unknown field");
-        SPK_REQUIRE(T.op >= SPK_SEL_LT && T.op <= SPK_SEL_IS_NOT_NULL, SPK_E_INVALID, "spk_select: unknown operator");
-        SPK_REQUIRE(T.field != SPK_SEL_MP || (m && u), SPK_E_INVALID,
-                    "spk_select: a match_probability term needs m and u");
+        SPK_REQUIRE(T.field == SPK_SEL_MP || T.field == SPK_SEL_GAMMA || (tf && T.field == SPK_SEL_TF_MP), SPK_E_INVALID,
+                    w + ": unknown field");
+        SPK_REQUIRE(T.op >= SPK_SEL_LT && T.op <= SPK_SEL_IS_NOT_NULL, SPK_E_INVALID, w + ": unknown operator");
+        SPK_REQUIRE(T.field != SPK_SEL_MP || (m && u), SPK_E_INVALID, w + ": a match_probability term needs m and u");
         SPK_REQUIRE(T.field != SPK_SEL_GAMMA || (T.col >= 0 && T.col < ctx->K), SPK_E_INVALID,
-                    "spk_select: gamma column out of range");
+                    w + ": gamma column out of range");
     }
+    if (tf) {
+        const int64_t P = ctx->n_pairs;
+        SPK_REQUIRE(ctx->pairs_valid && ctx->pl.p && ctx->pr.p && ctx->pl.n >= (size_t)P && ctx->pr.n >= (size_t)P,
+                    SPK_E_STATE, w + ": no pair rows (a loaded gamma table)");
+    }
+    return SPK_OK;
+}
+
+extern "C" int spk_select(spk_ctx *ctx, double lambda, double one_minus, const double *m, const double *u,
+                          int n_terms, const spk_select_term *terms, int64_t *out_n_selected) {
+    SPK_TRY(select_begin(ctx, "spk_select", m, u, n_terms, terms, false));
     Selection S;
-    SPK_TRY(build_selection(ctx, lambda, one_minus, m, u, n_terms, terms, S));
+    SPK_TRY(build_selection(ctx, lambda, one_minus, m, u, n_terms, terms, nullptr, S));
     ctx->sel = std::move(S);
     if (out_n_selected) *out_n_selected = ctx->sel.n;
+    return SPK_OK;
+}
+
+extern "C" int spk_select_tf(spk_ctx *ctx, double lambda, double one_minus, const double *m, const double *u,
+                             int n_tf_cols, const int64_t *const *ids_side0, const int64_t *const *ids_side1,
+                             const double *const *adj_tables, const int64_t *table_sizes, int n_terms,
+                             const spk_select_term *terms, int64_t *out_n_selected) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_select_tf: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    ctx->sel.clear();  // a failing call leaves no selection
+    SPK_REQUIRE(n_tf_cols >= 1 && n_tf_cols <= 8, SPK_E_INVALID, "spk_select_tf: 1..8 columns");
+    SPK_REQUIRE(ids_side0 && ids_side1 && adj_tables && table_sizes, SPK_E_INVALID, "spk_select_tf: null arg");
+    SPK_TRY(select_begin(ctx, "spk_select_tf", m, u, n_terms, terms, true));
+    TfStage G;  // the id arrays and tables live until this call returns
+    SPK_TRY(tf_stage_host_ids(ctx, n_tf_cols, ids_side0, ids_side1, G));
+    SPK_TRY(tf_stage_tables(ctx, adj_tables, table_sizes, G));
+    Selection S;
+    SPK_TRY(build_selection(ctx, lambda, one_minus, m, u, n_terms, terms, &G.T, S));
+    ctx->sel = std::move(S);
+    if (out_n_selected) *out_n_selected = ctx->sel.n;
+    return SPK_OK;
+}
+
+extern "C" int spk_select_tf_columns(spk_ctx *ctx, double lambda, double one_minus, const double *m, const double *u,
+                                     int n_tf_cols, const int32_t *cols, const double *const *adj_tables,
+                                     const int64_t *table_sizes, int n_terms, const spk_select_term *terms,
+                                     int64_t *out_n_selected) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_select_tf_columns: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    ctx->sel.clear();  // a failing call leaves no selection
+    SPK_REQUIRE(n_tf_cols >= 1 && n_tf_cols <= 8, SPK_E_INVALID, "spk_select_tf_columns: 1..8 columns");
+    SPK_REQUIRE(cols && adj_tables && table_sizes, SPK_E_INVALID, "spk_select_tf_columns: null arg");
+    SPK_TRY(select_begin(ctx, "spk_select_tf_columns", m, u, n_terms, terms, true));
+    TfStage G;
+    SPK_TRY(tf_stage_column_ids(ctx, n_tf_cols, cols, G));
+    SPK_TRY(tf_stage_tables(ctx, adj_tables, table_sizes, G));
+    Selection S;
+    SPK_TRY(build_selection(ctx, lambda, one_minus, m, u, n_terms, terms, &G.T, S));
+    ctx->sel = std::move(S);
+    if (out_n_selected) *out_n_selected = ctx->sel.n;
+    return SPK_OK;
+}
+
+extern "C" int spk_select_copy_tf(spk_ctx *ctx, int64_t start, int64_t count, double *out_tf_mp, double *out_adj) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_select_copy_tf: null ctx");
+    const Selection &S = ctx->sel;
+    SPK_REQUIRE(S.valid, SPK_E_STATE, "spk_select_copy_tf: no selection (run spk_select_tf*)");
+    SPK_REQUIRE(S.has_tf, SPK_E_STATE, "spk_select_copy_tf: the selection was made without tf tables (spk_select)");
+    SPK_REQUIRE(ctx->codes_valid && S.pairs_epoch == ctx->pairs_epoch && S.gamma_seq == ctx->gamma_seq &&
+                    S.fix_seq == ctx->codes_fix_seq,
+                SPK_E_STATE, "spk_select_copy_tf: the pairs or codes changed since spk_select_tf*");
+    SPK_REQUIRE(start >= 0 && count >= 0 && start + count <= S.n, SPK_E_INVALID, "spk_select_copy_tf: range");
+    if (!count) return SPK_OK;
+    SPK_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    if (out_tf_mp) SPK_HIP(hipMemcpyAsync(out_tf_mp, S.tf_mp.p + start, (size_t)count * 8, hipMemcpyDeviceToHost, st));
+    if (out_adj)
+        SPK_HIP(hipMemcpyAsync(out_adj, S.adj.p + start * S.n_tf, (size_t)count * S.n_tf * 8, hipMemcpyDeviceToHost, st));
+    SPK_HIP(hipStreamSynchronize(st));
     return SPK_OK;
 }
 

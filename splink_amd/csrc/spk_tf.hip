@@ -21,6 +21,7 @@
 #include <rocprim/device/device_run_length_encode.hpp>
 
 #include "spk_internal.h"
+#include "spk_tf_pair.h"
 
 namespace spk {
 
@@ -335,42 +336,14 @@ static int tf_exact(spk_ctx *ctx, int64_t n_values, const int64_t *d0, const int
     return SPK_OK;
 }
 
-struct TfApply {
-    int n;
-    const int64_t *ids0[8];
-    const int64_t *ids1[8];
-    const double *tab[8];
-    int64_t tab_n[8];
-};
-
-// bayes(mp, adj...) = Πp / (Πp + Π(1-p)) (term_frequencies.py:21-46, :98-117)
+// bayes(mp, adj...) = Πp / (Πp + Π(1-p)) (term_frequencies.py:21-46, :98-117): tf_pair (spk_tf_pair.h)
 __global__ void k_tf_apply(TfApply T, int64_t start, int64_t n, const int32_t *__restrict__ pl,
                            const int32_t *__restrict__ pr, const double *__restrict__ mp, double *__restrict__ out,
                            double *__restrict__ out_adj) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     int64_t p = start + i;
-    double m = mp[p];
-    double adj[8];
-    for (int c = 0; c < T.n; ++c) {
-        int64_t a = T.ids0[c][pl[p]], b = T.ids1[c][pr[p]];
-        double v = 0.5;
-        if (a >= 0 && a == b && a < T.tab_n[c]) {
-            double x = T.tab[c][a];
-            if (!isnan(x)) v = x;
-        }
-        adj[c] = v;
-        if (out_adj) out_adj[i * T.n + c] = v;
-    }
-    if (isnan(m)) {
-        out[i] = NAN;
-        return;
-    }
-    double a = m, b = 1.0 - m;
-    for (int c = 0; c < T.n; ++c) a = a * adj[c];
-    for (int c = 0; c < T.n; ++c) b = b * (1.0 - adj[c]);
-    double d = a + b;
-    out[i] = d == 0.0 ? NAN : a / d;
+    out[i] = tf_pair(T, mp[p], pl[p], pr[p], out_adj ? out_adj + i * T.n : nullptr);
 }
 
 
@@ -521,17 +494,56 @@ extern "C" int spk_tf_column_values(spk_ctx *ctx, int col, int64_t *out_n_values
     return SPK_OK;
 }
 
-static int tf_apply_dev(spk_ctx *ctx, TfApply &T, const double *const *adj_tables, const int64_t *table_sizes,
-                        int64_t start, int64_t count, double *out_tf_mp, double *out_adj) {
-    DevBuf<double> dt[8], dout, dadj;
-    for (int c = 0; c < T.n; ++c) {
-        SPK_TRY(dt[c].alloc((size_t)table_sizes[c] + 1));
-        if (table_sizes[c])
-            SPK_HIP(hipMemcpyAsync(dt[c].p, adj_tables[c], (size_t)table_sizes[c] * 8, hipMemcpyHostToDevice,
-                                   ctx->stream));
-        T.tab[c] = dt[c].p;
-        T.tab_n[c] = table_sizes[c];
+namespace spk {
+
+int tf_stage_host_ids(spk_ctx *ctx, int n_tf_cols, const int64_t *const *ids_side0, const int64_t *const *ids_side1,
+                      TfStage &S) {
+    Table &t0 = ctx->table[0], &t1 = ctx->side_table(1);
+    S.T.n = n_tf_cols;
+    for (int c = 0; c < n_tf_cols; ++c) {
+        SPK_TRY(S.d0[c].alloc((size_t)t0.n + 1));
+        SPK_TRY(S.d1[c].alloc((size_t)t1.n + 1));
+        SPK_HIP(hipMemcpyAsync(S.d0[c].p, ids_side0[c], (size_t)t0.n * 8, hipMemcpyHostToDevice, ctx->stream));
+        SPK_HIP(hipMemcpyAsync(S.d1[c].p, ids_side1[c], (size_t)t1.n * 8, hipMemcpyHostToDevice, ctx->stream));
+        S.T.ids0[c] = S.d0[c].p;
+        S.T.ids1[c] = S.d1[c].p;
     }
+    return SPK_OK;
+}
+
+int tf_stage_column_ids(spk_ctx *ctx, int n_tf_cols, const int32_t *cols, TfStage &S) {
+    Table &t0 = ctx->table[0], &t1 = ctx->side_table(1);
+    S.T.n = n_tf_cols;
+    for (int c = 0; c < n_tf_cols; ++c) {
+        int64_t n0 = 0, n1 = 0;
+        SPK_TRY(column_ids(ctx, t0, cols[c], S.d0[c], &n0));
+        if (&t1 != &t0) SPK_TRY(column_ids(ctx, t1, cols[c], S.d1[c], &n1));
+        S.T.ids0[c] = S.d0[c].p;
+        S.T.ids1[c] = &t1 != &t0 ? S.d1[c].p : S.d0[c].p;
+    }
+    return SPK_OK;
+}
+
+int tf_stage_tables(spk_ctx *ctx, const double *const *adj_tables, const int64_t *table_sizes, TfStage &S) {
+    for (int c = 0; c < S.T.n; ++c) {
+        SPK_REQUIRE(table_sizes[c] >= 0, SPK_E_INVALID, "tf: negative table size");
+        SPK_TRY(S.dt[c].alloc((size_t)table_sizes[c] + 1));
+        if (table_sizes[c])
+            SPK_HIP(hipMemcpyAsync(S.dt[c].p, adj_tables[c], (size_t)table_sizes[c] * 8, hipMemcpyHostToDevice,
+                                   ctx->stream));
+        S.T.tab[c] = S.dt[c].p;
+        S.T.tab_n[c] = table_sizes[c];
+    }
+    return SPK_OK;
+}
+
+}  // namespace spk
+
+static int tf_apply_dev(spk_ctx *ctx, TfStage &S, const double *const *adj_tables, const int64_t *table_sizes,
+                        int64_t start, int64_t count, double *out_tf_mp, double *out_adj) {
+    DevBuf<double> dout, dadj;
+    SPK_TRY(tf_stage_tables(ctx, adj_tables, table_sizes, S));
+    const TfApply &T = S.T;
     // out_tf_mp = NULL: the results stay on the device (ctx->tf_mp, read by range with spk_tf_copy), as spk_score
     // keeps mp there -- at cfg3's 3.08e9 pairs the host copy alone (24.6 GB into pageable memory) took ~5.8 s of
     // the 6.1 s tf stage (profiles/r6_fulljob_cfg3_10Mx10M_1gpu.json)
@@ -596,18 +608,9 @@ extern "C" int spk_tf_apply_columns(spk_ctx *ctx, int n_tf_cols, const int32_t *
     SPK_REQUIRE(start >= 0 && count >= 0 && start + count <= ctx->n_pairs, SPK_E_INVALID, "spk_tf_apply_columns: range");
     SPK_HIP(hipSetDevice(ctx->device));
     SPK_TRY(settle_gammas(ctx, nullptr));
-    Table &t0 = ctx->table[0], &t1 = ctx->side_table(1);
-    DevBuf<int64_t> d0[8], d1[8];
-    TfApply T{};
-    T.n = n_tf_cols;
-    for (int c = 0; c < n_tf_cols; ++c) {
-        int64_t n0 = 0, n1 = 0;
-        SPK_TRY(column_ids(ctx, t0, cols[c], d0[c], &n0));
-        if (&t1 != &t0) SPK_TRY(column_ids(ctx, t1, cols[c], d1[c], &n1));
-        T.ids0[c] = d0[c].p;
-        T.ids1[c] = &t1 != &t0 ? d1[c].p : d0[c].p;
-    }
-    return tf_apply_dev(ctx, T, adj_tables, table_sizes, start, count, out_tf_mp, out_adj);
+    TfStage S;
+    SPK_TRY(tf_stage_column_ids(ctx, n_tf_cols, cols, S));
+    return tf_apply_dev(ctx, S, adj_tables, table_sizes, start, count, out_tf_mp, out_adj);
 }
 
 extern "C" int spk_tf_apply(spk_ctx *ctx, int n_tf_cols, const int64_t *const *ids_side0,
@@ -619,17 +622,7 @@ extern "C" int spk_tf_apply(spk_ctx *ctx, int n_tf_cols, const int64_t *const *i
     SPK_REQUIRE(start >= 0 && count >= 0 && start + count <= ctx->n_pairs, SPK_E_INVALID, "spk_tf_apply: range");
     SPK_HIP(hipSetDevice(ctx->device));
     SPK_TRY(settle_gammas(ctx, nullptr));
-    Table &t0 = ctx->table[0], &t1 = ctx->side_table(1);
-    DevBuf<int64_t> d0[8], d1[8];
-    TfApply T{};
-    T.n = n_tf_cols;
-    for (int c = 0; c < n_tf_cols; ++c) {
-        SPK_TRY(d0[c].alloc((size_t)t0.n + 1));
-        SPK_TRY(d1[c].alloc((size_t)t1.n + 1));
-        SPK_HIP(hipMemcpyAsync(d0[c].p, ids_side0[c], (size_t)t0.n * 8, hipMemcpyHostToDevice, ctx->stream));
-        SPK_HIP(hipMemcpyAsync(d1[c].p, ids_side1[c], (size_t)t1.n * 8, hipMemcpyHostToDevice, ctx->stream));
-        T.ids0[c] = d0[c].p;
-        T.ids1[c] = d1[c].p;
-    }
-    return tf_apply_dev(ctx, T, adj_tables, table_sizes, start, count, out_tf_mp, out_adj);
+    TfStage S;
+    SPK_TRY(tf_stage_host_ids(ctx, n_tf_cols, ids_side0, ids_side1, S));
+    return tf_apply_dev(ctx, S, adj_tables, table_sizes, start, count, out_tf_mp, out_adj);
 }

@@ -6,8 +6,9 @@ pipeline and its users need: `toPandas()`, `count()`, `columns`, `persist()` / `
 `unpersist()`, `createOrReplaceTempView()`.  Pairs, comparison codes and scores stay on the
 GPU; `toPandas()` copies them back and gathers the retained input columns with the
 reference's column names and order.  `filter(condition)` / `where` (Spark's DataFrame.filter on the
-scored frame) select on the device instead: a `FilteredFrame` copies back the survivors only, and its
-`clusters()` (GraphFrames' connectedComponents over the kept pairs) leaves the device with one label per record.
+scored frame, or on the term-frequency stage's frame: term_frequencies.py) select on the device instead: a
+`FilteredFrame` copies back the survivors only, and its `clusters()` (GraphFrames' connectedComponents over the
+kept pairs) leaves the device with one label per record.
 """
 from __future__ import annotations
 
@@ -341,9 +342,18 @@ class FilteredFrame(SplinkDataFrame):
             self._pdf = self._materialise()
         return self._pdf.copy()
 
+    def _scored_parent(self):
+        """The ExpectationFrame whose parameters the survivors' match_probability and prob_gamma_* come from, or None
+        (an unscored parent)."""
+        return self.parent if isinstance(self.parent, ExpectationFrame) else None
+
+    def _extra_columns(self, n):
+        """Columns of this frame beyond the scored frame's, for the n survivors of the context's selection."""
+        return {}
+
     def _materialise(self):
-        job, parent = self.job, self.parent
-        scored = isinstance(parent, ExpectationFrame)
+        job, parent = self.job, self._scored_parent()
+        scored = parent is not None
         names = self.gammas.meta[0]  # the frame's own columns: the selection is made on its codes (_select)
         n = self._select()
         if list(job.code_meta[0]) != list(names):  # select_copy writes K levels per survivor into a buffer sized here
@@ -358,9 +368,12 @@ class FilteredFrame(SplinkDataFrame):
             mp = np.empty(0, dtype=np.float64)
         gidx = {g: i for i, g in enumerate(names)}
         probs = parent._prob_columns(gam) if scored else {}
+        extra = self._extra_columns(n)
         data = OrderedDict()
         for c in self._column_order():
-            if c == "match_probability" and scored:
+            if c in extra:
+                data[c] = extra[c]
+            elif c == "match_probability" and scored:
                 data[c] = mp
             elif c in gidx:
                 data[c] = gam[:, gidx[c]].astype(np.int32)

@@ -2,8 +2,10 @@
 
 The reference's users filter the scored frame with Spark SQL, `df_e.filter("match_probability > 0.9")` or a
 condition on `gamma_*` columns.  Both are functions of a pair's comparison pattern, so a conjunction over them is
-decided once per pattern on the device.  This module parses the condition (sqlexpr) and turns it into at most
-`MAX_TERMS` terms `(field, col, op, value)`; anything else raises ValueError naming what it met.
+decided once per pattern on the device.  The frame of the term-frequency stage is filtered on
+`tf_adjusted_match_prob` as well, which the device decides per pair (spk_select_tf).  This module parses the
+condition (sqlexpr) and turns it into at most `MAX_TERMS` terms `(field, col, op, value)`; anything else raises
+ValueError naming what it met.
 """
 from __future__ import annotations
 
@@ -14,18 +16,20 @@ from . import _native as N
 from . import sqlexpr as S
 
 MAX_TERMS = N.SELECT_MAX_TERMS
-FIELD_MP, FIELD_GAMMA = N.SEL_MP, N.SEL_GAMMA
+FIELD_MP, FIELD_GAMMA, FIELD_TF = N.SEL_MP, N.SEL_GAMMA, N.SEL_TF_MP
 OP = N.SEL_OP
 _FLIP = {"<": ">", "<=": ">=", ">": "<", ">=": "<=", "=": "=", "!=": "!="}
 
 SUPPORTED = ("supported: a conjunction (AND) of at most %d terms, each `<column> <op> <number>` (or the number on "
              "the left) with <op> one of < <= > >= = != <>, or `<column> is [not] null`, where <column> is "
              "match_probability (scored frames) or one of the frame's gamma_* columns" % MAX_TERMS)
+SUPPORTED_TF = SUPPORTED.replace("match_probability (scored frames)",
+                                 "tf_adjusted_match_prob (the term-frequency frame), match_probability (scored frames)")
 
 
 @dataclass(frozen=True)
 class Term:
-    field: int    # FIELD_MP / FIELD_GAMMA
+    field: int    # FIELD_MP / FIELD_GAMMA / FIELD_TF
     col: int      # comparison column of a FIELD_GAMMA term (0 otherwise)
     op: int       # OP[...]
     value: float  # the literal (0.0 for is [not] null)
@@ -53,6 +57,11 @@ class Predicate:
     @property
     def needs_mp(self) -> bool:
         return any(t.field == FIELD_MP for t in self.terms)
+
+    @property
+    def needs_tf(self) -> bool:
+        """Some term reads tf_adjusted_match_prob: the selection is decided per pair, not per pattern."""
+        return any(t.field == FIELD_TF for t in self.terms)
 
 
 def _checked(terms, never) -> Predicate:
@@ -86,18 +95,21 @@ def _describe(node) -> str:
     return type(node).__name__
 
 
-def _reject(node, text):
-    raise ValueError(f"filter: unsupported {_describe(node)} in condition {text!r}; {SUPPORTED}")
+def _reject(node, text, supported=SUPPORTED):
+    raise ValueError(f"filter: unsupported {_describe(node)} in condition {text!r}; {supported}")
 
 
 def _number(node):
     return isinstance(node, S.Lit) and isinstance(node.value, (int, float)) and not isinstance(node.value, bool)
 
 
-def _column(node, gamma_index, allow_mp, text):
+def _column(node, gamma_index, allow_mp, text, allow_tf=False):
     """(field, col) of a column node the frame can filter on."""
+    supported = SUPPORTED_TF if allow_tf else SUPPORTED
     if not isinstance(node, S.Col) or node.qualifier:
-        _reject(node, text)
+        _reject(node, text, supported)
+    if node.name == "tf_adjusted_match_prob" and allow_tf:
+        return FIELD_TF, 0
     if node.name == "match_probability":
         if not allow_mp:
             raise ValueError(f"filter: column 'match_probability' in condition {text!r}: this frame is not scored "
@@ -105,31 +117,34 @@ def _column(node, gamma_index, allow_mp, text):
         return FIELD_MP, 0
     if node.name in gamma_index:
         return FIELD_GAMMA, gamma_index[node.name]
-    _reject(node, text)
+    _reject(node, text, supported)
 
 
-def compile_condition(condition: str, gamma_names: Sequence[str], allow_mp: bool = True) -> Predicate:
-    """The terms of `condition` over a frame whose gamma columns are `gamma_names` (in comparison-column order)."""
+def compile_condition(condition: str, gamma_names: Sequence[str], allow_mp: bool = True,
+                      allow_tf: bool = False) -> Predicate:
+    """The terms of `condition` over a frame whose gamma columns are `gamma_names` (in comparison-column order).
+    allow_tf: the frame carries tf_adjusted_match_prob (the term-frequency frame)."""
+    supported = SUPPORTED_TF if allow_tf else SUPPORTED
     if not isinstance(condition, str):
         raise TypeError(f"filter: the condition must be a SQL string, got {type(condition).__name__}")
     gamma_index = {g.lower(): i for i, g in enumerate(gamma_names)}
     terms, never = [], False
     for node in S.conjuncts(S.parse(condition)):
         if isinstance(node, S.IsNull):
-            field, col = _column(node.a, gamma_index, allow_mp, condition)
+            field, col = _column(node.a, gamma_index, allow_mp, condition, allow_tf)
             if field == FIELD_GAMMA:  # a gamma is never NULL (-1 is a level): folded here
                 never = never or not node.negated
                 continue
             terms.append(Term(field, col, OP["is not null" if node.negated else "is null"], 0.0))
             continue
         if not (isinstance(node, S.Bin) and node.op in _FLIP):
-            _reject(node, condition)
+            _reject(node, condition, supported)
         a, b, op = node.a, node.b, node.op
         if _number(a) and not _number(b):
             a, b, op = b, a, _FLIP[op]
         if not _number(b):
-            _reject(b if isinstance(a, S.Col) else a, condition)
-        field, col = _column(a, gamma_index, allow_mp, condition)
+            _reject(b if isinstance(a, S.Col) else a, condition, supported)
+        field, col = _column(a, gamma_index, allow_mp, condition, allow_tf)
         value = float(b.value)
         if field == FIELD_GAMMA and value != int(value):
             raise ValueError(f"filter: non-integral literal {b.value!r} compared with a gamma column in condition "

@@ -19,8 +19,10 @@ from . import _native as N
 from . import distributed as D
 from . import table as T
 from .check_types import check_types
-from .frames import ExpectationFrame, SplinkDataFrame, _HostColumns, df_e_column_order, reject_filtered
+from .frames import (ExpectationFrame, FilteredFrame, SplinkDataFrame, _HostColumns, df_e_column_order,
+                     reject_filtered)
 from .params import Params
+from .select import compile_condition
 
 
 def _bayes_pair(a, b):
@@ -34,14 +36,42 @@ def _bayes_pair(a, b):
 
 
 class TermFrequencyFrame(SplinkDataFrame):
-    def __init__(self, df_e: ExpectationFrame, settings, tf_cols, tf_mp, adj, retain_adjustment_columns):
+    """The tf stage's frame.  The per-value adjustment tables are computed when it is made; the per-pair part
+    (spk_tf_apply*) runs on the first toPandas(), and filter() / clusters() never run it: they select on the device
+    (spk_select_tf*) and copy the survivors only."""
+
+    def __init__(self, df_e: ExpectationFrame, settings, tf_cols, tables, one_minus, retain_adjustment_columns,
+                 dev_cols=None, host_ids=None):
         self.df_e = df_e
         self.job = df_e.job
         self.settings = settings
         self.tf_cols = tf_cols
-        self.tf_mp = tf_mp
-        self.adj = adj
+        self.tables = tables        # per tf column: the adjustment per value id
+        self.one_minus = one_minus  # the 1 - λ the tables were combined with
+        self.dev_cols = dev_cols    # the columns' device dictionary ids ...
+        self.host_ids = host_ids    # ... or (ids of side 0, ids of side 1) per column, factorised on the host
         self.retain = retain_adjustment_columns
+        self._pair = None           # (tf_adjusted_match_prob, adjustments [P, n_tf])
+
+    def _apply(self):
+        if self._pair is None:
+            job = self.job
+            self.df_e.gammas.ensure_codes()
+            job.score(self.df_e.lam, self.df_e.level_probs, want_host=False)  # device mp for exactly this df_e
+            if self.dev_cols is not None:
+                self._pair = job.ctx.tf_apply_columns(self.dev_cols, self.tables, 0, job.n_pairs, want_adj=True)
+            else:
+                ids0, ids1 = self.host_ids
+                self._pair = job.ctx.tf_apply(ids0, ids1, self.tables, 0, job.n_pairs, want_adj=True)
+        return self._pair
+
+    @property
+    def tf_mp(self):
+        return self._apply()[0]
+
+    @property
+    def adj(self):
+        return self._apply()[1]
 
     def _column_order(self):
         cols = ["tf_adjusted_match_prob", "match_probability"] + df_e_column_order(self.settings, tf_adj_cols=True)
@@ -60,6 +90,67 @@ class TermFrequencyFrame(SplinkDataFrame):
             else:
                 data[c] = base[c].to_numpy()
         return pd.DataFrame(data)
+
+    def filter(self, condition):
+        """tf.filter("tf_adjusted_match_prob > 0.99 and gamma_surname >= 1"): the pairs for which the condition is
+        TRUE, selected on the device (spk_select_tf*); only the survivors come back, with every column of this
+        frame."""
+        return TfFilteredFrame(self, compile_condition(condition, self.df_e.gammas.meta[0], allow_mp=True,
+                                                       allow_tf=True))
+
+    where = filter
+
+    def clusters(self, threshold):
+        """Shorthand for filter(f"tf_adjusted_match_prob > {threshold!r}").clusters()."""
+        return self.filter(f"tf_adjusted_match_prob > {threshold!r}").clusters()
+
+
+class TfFilteredFrame(FilteredFrame):
+    """`tf.filter(condition)`: toPandas() equals tf.toPandas()[mask].reset_index(drop=True).  A predicate without a
+    tf term is selected the same way, since the survivors carry the tf columns either way."""
+
+    def __init__(self, parent: TermFrequencyFrame, predicate):
+        super().__init__(parent, predicate)
+        self.gammas = parent.df_e.gammas
+
+    def filter(self, condition):
+        more = compile_condition(condition, self.gammas.meta[0], allow_mp=True, allow_tf=True)
+        return TfFilteredFrame(self.parent, self.predicate.and_(more))
+
+    where = filter
+
+    def _scored_parent(self):
+        return self.parent.df_e
+
+    def _select(self):
+        job, tf = self.job, self.parent
+        self.gammas.ensure_codes()
+        if self._n is not None and job.selection_owner is self and self._seq == job.codes_seq:
+            return self._n
+        df_e = tf.df_e
+        m, u = job.flat_tables(df_e.level_probs)
+        lam, terms = float(df_e.lam), self.predicate.native_terms()
+        if tf.dev_cols is not None:
+            n = job.ctx.select_tf_columns(lam, float(1 - df_e.lam), m, u, tf.dev_cols, tf.tables, terms)
+        else:
+            ids0, ids1 = tf.host_ids
+            n = job.ctx.select_tf(lam, float(1 - df_e.lam), m, u, ids0, ids1, tf.tables, terms)
+        job.selection_owner = self
+        self._seq = job.codes_seq
+        self._n = int(n)
+        return self._n
+
+    def _extra_columns(self, n):
+        tf = self.parent
+        if n:
+            tf_mp, adj = self.job.ctx.select_copy_tf(0, n, len(tf.tf_cols), adj=tf.retain)
+        else:
+            tf_mp, adj = np.empty(0, dtype=np.float64), np.empty((0, len(tf.tf_cols)), dtype=np.float64)
+        out = {"tf_adjusted_match_prob": tf_mp}
+        if tf.retain:
+            for i, c in enumerate(tf.tf_cols):
+                out[c + "_adj"] = adj[:, i]
+        return out
 
 
 @check_types
@@ -112,8 +203,8 @@ def make_adjustment_for_term_frequencies(df_e: object, params: Params, settings:
         with np.errstate(invalid="ignore", divide="ignore"):
             adj_lambda = np.where(counts > 0, sums / np.maximum(counts, 1), np.nan)
         tables.append(_bayes_pair(adj_lambda, one_minus))
-    if on_device:
-        tf_mp, adj = job.ctx.tf_apply_columns(dev_cols, tables, 0, job.n_pairs, want_adj=True)
-    else:
-        tf_mp, adj = job.ctx.tf_apply(ids0_list, ids1_list, tables, 0, job.n_pairs, want_adj=True)
-    return TermFrequencyFrame(df_e, settings, tf_cols, tf_mp, adj, retain_adjustment_columns)
+    # the per-pair part is left to the frame: toPandas() applies the tables to every pair, filter() / clusters()
+    # select on the device and copy the survivors only
+    return TermFrequencyFrame(df_e, settings, tf_cols, tables, one_minus, retain_adjustment_columns,
+                              dev_cols=dev_cols if on_device else None,
+                              host_ids=None if on_device else (ids0_list, ids1_list))
