@@ -67,7 +67,7 @@ int spk_ctx_lds_per_block(spk_ctx *ctx, int *out);
  * buffers as handed over), [1] record encodings (decoded columns: units, metadata, bit-planes, bag rows,
  * numeric values; row permutations, ranks, blocking keys), [2] filter row images, [3] candidate pairs (row
  * indices, rule-view positions and rows), [4] comparison codes, [5] comparison work lists (filter lists,
- * exact / slow lists, region counts), [6] EM, scoring and tf state, the last selection (spk_select) and the last
+ * exact / slow lists, region counts), [6] EM, scoring and tf state, the last selection (spk_select, spk_select_best) and the last
  * components' labels (spk_components*), [7] the sum.  For sizing a share of a
  * job against a device's memory (there is no reference counterpart: Spark spills). */
 int spk_ctx_memory(spk_ctx *ctx, int64_t *out8);
@@ -459,6 +459,38 @@ int spk_select_tf_columns(spk_ctx *ctx, double lambda, double one_minus, const d
  * (either may be NULL).  SPK_E_STATE after a plain spk_select, without a selection, or for a stale one. */
 int spk_select_copy_tf(spk_ctx *ctx, int64_t start, int64_t count, double *out_tf_mp,
                        double *out_adj /* [count x n_tf_cols] or NULL */);
+
+/* ---- best match per record (replaces the window query the reference's users run over the frame
+ *      expectation_step.py returns: row_number() over (partition by unique_id_l order by match_probability desc) = 1,
+ *      often once per side and then joined, to link each record to its best candidate) ---- */
+/* Narrows the context's selection to the best pair per record.  S = the survivors whose score is not NULL (NaN); the
+ * score is `field`: SPK_SEL_MP (the selection's own match_probability) or SPK_SEL_TF_MP (its tf_adjusted_match_prob).
+ * Pair a beats pair b iff score(a) > score(b), or the scores are equal as doubles and ordinal(a) < ordinal(b): a
+ * strict total order (Spark's row_number leaves ties unspecified; here the ordinal decides, since thousands of pairs
+ * share one comparison pattern and so one score).  A record is a row of an input table; link_only never identifies a
+ * left with a right record, dedupe_only and link_and_dedupe index table 0 on both sides. */
+#define SPK_BEST_L 0          /* kept: the pair beats every other pair of S with the same left record */
+#define SPK_BEST_R 1          /* the same by right record */
+#define SPK_BEST_EITHER 2     /* best[x] = the pair that beats all pairs of S touching record x on either side; kept iff
+                                 it is best[l] or best[r] */
+#define SPK_BEST_MUTUAL 3     /* kept iff it is best[l] and best[r]: every record is then in at most one kept pair */
+/* keep_ties = 0: as above.  keep_ties = 1: every pair whose score equals its group's maximum is a best pair of the
+ * group (no ordinal tie-break), combined per mode in the same way.  A pair with a NULL score is never kept and never
+ * beats anything.  The kept pairs stay in ascending pair ordinal and REPLACE the context's selection:
+ * spk_select_copy, spk_select_copy_tf, spk_select_info (whose milliseconds stay those of the selecting call) and
+ * spk_components work on them unchanged, and their buffers, sized to the kept count, count under [6] of
+ * spk_ctx_memory; the per-record arrays of the passes are freed before the call returns.  An empty selection is
+ * legal and keeps 0.  SPK_E_INVALID: unknown field, mode or keep_ties.  SPK_E_STATE: no selection; a stale one; one
+ * without pair rows (a loaded gamma table); SPK_SEL_MP on a selection made without m / u; SPK_SEL_TF_MP on one not
+ * made by spk_select_tf*.  A failing call leaves no selection.  The result does not depend on launch shape or on the
+ * arrival order of the atomics.  Reads the selection and the tables' row counts only: the scores of spk_score, tf
+ * state, EM state and component labels are not touched. */
+int spk_select_best(spk_ctx *ctx, int field /* SPK_SEL_MP | SPK_SEL_TF_MP */, int mode, int keep_ties,
+                    int64_t *out_n_kept);
+/* The last spk_select_best: survivors before it and pairs kept (-1 each: none yet, or the last call failed), and
+ * with timing on (spk_ctx_enable_timing) the device milliseconds of its launches (group maxima, first index, keep
+ * flags and scan, emit; the host round trip between them is not in it), -1 otherwise. */
+int spk_select_best_info(spk_ctx *ctx, int64_t *out_n_before, int64_t *out_n_kept, double *out_ms);
 
 /* ---- connected components of the kept pairs (replaces handing df_e.filter(...) to GraphFrames'
  *      connectedComponents; later reference releases: cluster_pairwise_predictions_at_threshold) ---- */

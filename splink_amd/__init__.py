@@ -17,7 +17,7 @@ from .blocking import block_using_rules
 from .case_statements import _check_jaro_registered
 from .check_types import check_types
 from .expectation_step import run_expectation_step
-from .frames import ClusterFrame, FilteredFrame, SplinkDataFrame
+from .frames import BestMatchFrame, ClusterFrame, FilteredFrame, SplinkDataFrame
 from .gammas import add_gammas
 from .iterate import iterate
 from .params import Params, load_params_from_json
@@ -28,7 +28,7 @@ from .validate import validate_settings
 
 __all__ = ["Splink", "load_from_json", "AmdSession", "session", "Params", "block_using_rules", "add_gammas",
            "iterate", "run_expectation_step", "make_adjustment_for_term_frequencies", "complete_settings_dict",
-           "ClusterFrame", "FilteredFrame"]
+           "ClusterFrame", "FilteredFrame", "BestMatchFrame"]
 
 
 def _is_frame(x):

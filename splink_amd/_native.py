@@ -41,6 +41,7 @@ SEL_MP, SEL_GAMMA = 0, 1  # SPK_SEL_MP, SPK_SEL_GAMMA
 SEL_TF_MP = 2  # SPK_SEL_TF_MP: tf_adjusted_match_prob (select_tf / select_tf_columns only)
 SEL_OP = {"<": 0, "<=": 1, ">": 2, ">=": 3, "=": 4, "!=": 5, "is null": 6, "is not null": 7}  # SPK_SEL_LT ..
 SELECT_MAX_TERMS = 8  # SPK_SELECT_MAX_TERMS
+BEST_L, BEST_R, BEST_EITHER, BEST_MUTUAL = 0, 1, 2, 3  # SPK_BEST_L .. SPK_BEST_MUTUAL (select_best's modes)
 # Pair ordinals per count of the selection's compaction.  Mirrored from SEL_CHUNK in csrc/spk_select.hip (the
 # library exports no call for it); only the tests' edge sizes depend on it.
 SELECT_CHUNK = 2048
@@ -72,6 +73,7 @@ EXPORTS = [
     "spk_block_residual", "spk_block_residual_info",
     "spk_select", "spk_select_copy", "spk_select_info", "spk_select_release",
     "spk_select_tf", "spk_select_tf_columns", "spk_select_copy_tf",
+    "spk_select_best", "spk_select_best_info",
     "spk_components", "spk_components_edges", "spk_components_copy", "spk_components_info", "spk_components_release",
 ]
 TF_LIMBS = 14  # SPK_TF_LIMBS
@@ -637,6 +639,24 @@ class Context:
 
     def select_release(self):
         check(self._lib.spk_select_release(self._h), "spk_select_release")
+
+    def select_best(self, field: int, mode: int, keep_ties) -> int:
+        """spk_select_best: narrow the last select to the best pair per record by `field` (SEL_MP or SEL_TF_MP) under
+        `mode` (BEST_L .. BEST_MUTUAL); keep_ties: every pair at its group's maximum.  Returns how many are kept;
+        they replace the selection (select_copy, select_copy_tf, select_info, components work on them)."""
+        n = ctypes.c_int64(0)
+        check(self._lib.spk_select_best(self._h, ctypes.c_int(int(field)), ctypes.c_int(int(mode)),
+                                        ctypes.c_int(int(keep_ties)), ctypes.byref(n)), "spk_select_best")
+        return n.value
+
+    def select_best_info(self):
+        """(survivors before the last select_best or -1, pairs it kept or -1, ms of its launches with timing on or -1)."""
+        b = ctypes.c_int64(-1)
+        k = ctypes.c_int64(-1)
+        ms = ctypes.c_double(-1.0)
+        check(self._lib.spk_select_best_info(self._h, ctypes.byref(b), ctypes.byref(k), ctypes.byref(ms)),
+              "spk_select_best_info")
+        return b.value, k.value, ms.value
 
     # ---- connected components of the kept pairs -----------------------------------------------
     def components(self):

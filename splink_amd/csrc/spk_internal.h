@@ -475,6 +475,9 @@ struct spk_ctx {
     spk::Selection sel;
     hipEvent_t sel_ev0 = nullptr, sel_ev1 = nullptr;
     uint64_t codes_fix_seq = 0;
+    // the last spk_select_best (spk_best.hip): survivors before, pairs kept (-1: none, or it failed), device milliseconds
+    int64_t best_before = -1, best_kept = -1;
+    double best_ms = -1.0;
     // spk_components*: the last labels and the HIP events around its launches (created on first use with timing on)
     spk::Components comp;
     hipEvent_t cc_ev0 = nullptr, cc_ev1 = nullptr;

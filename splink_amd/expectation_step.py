@@ -13,7 +13,7 @@ import pandas as pd
 
 from .check_types import check_types
 from .engine import Job, session_device
-from .frames import ExpectationFrame, GammaFrame
+from .frames import BestMatchFrame, ExpectationFrame, GammaFrame, reject_filtered
 from .params import Params
 
 logger = logging.getLogger(__name__)
@@ -36,6 +36,8 @@ def _as_gamma_frame(df_with_gamma, params: Params, settings, spark) -> GammaFram
 
 @check_types
 def run_expectation_step(df_with_gamma: object, params: Params, settings: dict, spark: object, compute_ll=False):
+    if isinstance(df_with_gamma, BestMatchFrame):  # it has gamma columns, and would pass for a gamma table of its rows
+        reject_filtered(df_with_gamma, "run_expectation_step")
     gf = _as_gamma_frame(df_with_gamma, params, settings, spark)
     if compute_ll:
         ll = get_overall_log_likelihood(gf, params, spark)

@@ -8,7 +8,9 @@ GPU; `toPandas()` copies them back and gathers the retained input columns with t
 reference's column names and order.  `filter(condition)` / `where` (Spark's DataFrame.filter on the
 scored frame, or on the term-frequency stage's frame: term_frequencies.py) select on the device instead: a
 `FilteredFrame` copies back the survivors only, and its `clusters()` (GraphFrames' connectedComponents over the
-kept pairs) leaves the device with one label per record.
+kept pairs) leaves the device with one label per record.  Its `best_matches(per, ties)` (the users' window query
+row_number() over (partition by unique_id_l order by match_probability desc) = 1) narrows the survivors to the best
+pair per record on the device: a `BestMatchFrame`.
 """
 from __future__ import annotations
 
@@ -289,6 +291,13 @@ class ExpectationFrame(SplinkDataFrame):
         """Shorthand for filter(f"match_probability > {threshold!r}").clusters()."""
         return self.filter(f"match_probability > {threshold!r}").clusters()
 
+    def best_matches(self, threshold=None, per="l", ties="first"):
+        """Shorthand for filter(f"match_probability > {threshold!r}").best_matches(per, ties); threshold=None: the
+        best match among every pair."""
+        from .select import Predicate
+        f = FilteredFrame(self, Predicate()) if threshold is None else self.filter(f"match_probability > {threshold!r}")
+        return f.best_matches(per=per, ties=ties)
+
 
 class FilteredFrame(SplinkDataFrame):
     """`parent.filter(condition)`: lazily selected on the device.  count() runs the selection and returns the
@@ -396,6 +405,71 @@ class FilteredFrame(SplinkDataFrame):
         connectedComponents on the reference's filtered frame), computed on the device: a `ClusterFrame`."""
         return ClusterFrame(self)
 
+    # the scores best_matches() can rank by, the default first
+    _best_by = ("match_probability",)
+
+    def best_matches(self, per="l", ties="first", by=None):
+        """For each record its best pair among this frame's pairs (the reference's users' window query,
+        row_number() over (partition by unique_id_l order by match_probability desc) = 1), narrowed on the device
+        (spk_select_best): a `BestMatchFrame`.  per: "l" / "r" the best pair of every left / right record, "either"
+        the pairs that are the best of one of their two records, "mutual" of both (a one-to-one link).  Equal scores:
+        ties="first" keeps the pair that comes first in the frame, ties="all" every pair at the maximum."""
+        return BestMatchFrame(self, per, ties, self._best_by[0] if by is None else by)
+
+
+class BestMatchFrame(FilteredFrame):
+    """`filtered.best_matches(per, ties)`: lazily narrowed on the device.  The frame has the filtered frame's columns
+    and a subset of its rows, in its order; clusters() gives the components of the kept pairs (per="mutual": a
+    matching)."""
+
+    def __init__(self, inner: FilteredFrame, per, ties, by):
+        from .select import best_match_args
+        if inner._scored_parent() is None:
+            raise ValueError("best_matches: this frame has no score to rank the pairs by (it was filtered from an "
+                             "unscored frame): filter the frame run_expectation_step returns")
+        self._args = best_match_args(per, ties, by, allowed_by=inner._best_by)
+        job = inner.job
+        if getattr(job, "passthrough", None) is not None:
+            raise ValueError("best_matches() needs the records: a job made from a gamma table has pairs without rows")
+        if job.n_shards > 1:
+            raise ValueError("best_matches() on a sharded job: a record's pairs span the shards (take the best of the "
+                             "shards' best matches on the host)")
+        super().__init__(inner.parent, inner.predicate)
+        self.inner = inner
+        self.gammas = inner.gammas
+        self.per, self.ties, self.by = per, ties, by
+
+    def _column_order(self):
+        return self.inner._column_order()
+
+    def _scored_parent(self):
+        return self.inner._scored_parent()
+
+    def _extra_columns(self, n):
+        return self.inner._extra_columns(n)
+
+    def _refuse(self, *args, **kwargs):
+        raise ValueError("a best-match frame takes no further filter() or best_matches(): filter first, then take the "
+                         "best matches (a filter after the narrowing asks a different question)")
+
+    filter = where = best_matches = _refuse
+
+    def _select(self):
+        """Make the context's selection this frame's: the inner frame's selection (its own re-select rules: it
+        selects again unless the context still holds its survivors), narrowed to the best pair per record."""
+        job = self.job
+        self.gammas.ensure_codes()
+        if self._n is not None and job.selection_owner is self and self._seq == job.codes_seq:
+            return self._n
+        self.inner._select()
+        job.selection_owner = None  # the narrowing replaces the inner frame's survivors, or leaves none if it fails
+        field, mode, keep_ties = self._args
+        n = job.ctx.select_best(field, mode, keep_ties)
+        job.selection_owner = self
+        self._seq = job.codes_seq
+        self._n = int(n)
+        return self._n
+
 
 COPY_NODES = 1 << 26  # labels per spk_components_copy
 
@@ -470,6 +544,9 @@ class ClusterFrame(SplinkDataFrame):
 
 def reject_filtered(frame, what):
     """The stage functions run over every pair of a job: a filtered frame must not slip into them."""
+    if isinstance(frame, BestMatchFrame):
+        raise ValueError(f"{what} does not take a best-match frame (it would run over all of the job's pairs, not the "
+                         "kept ones): pass the frame filter() was called on")
     if isinstance(frame, FilteredFrame):
         raise ValueError(f"{what} does not take a filtered frame (it would run over all of the job's pairs, not the "
                          "survivors): pass the frame filter() was called on")

@@ -27,6 +27,24 @@ SUPPORTED_TF = SUPPORTED.replace("match_probability (scored frames)",
                                  "tf_adjusted_match_prob (the term-frequency frame), match_probability (scored frames)")
 
 
+BEST_PER = {"l": N.BEST_L, "r": N.BEST_R, "either": N.BEST_EITHER, "mutual": N.BEST_MUTUAL}
+BEST_TIES = {"first": 0, "all": 1}
+BEST_BY = {"match_probability": FIELD_MP, "tf_adjusted_match_prob": FIELD_TF}
+
+
+def best_match_args(per="l", ties="first", by="match_probability", allowed_by=("match_probability",)):
+    """(field, mode, keep_ties) of spk_select_best for best_matches(per=, ties=, by=); `allowed_by`: the scores the
+    frame carries.  Anything else raises ValueError naming the legal values."""
+    def pick(what, value, table, legal):
+        if not isinstance(value, str) or value not in legal:
+            raise ValueError(f"best_matches: {what}={value!r}; legal values: " + ", ".join(repr(v) for v in legal))
+        return table[value]
+    mode = pick("per", per, BEST_PER, tuple(BEST_PER))
+    keep_ties = pick("ties", ties, BEST_TIES, tuple(BEST_TIES))
+    field = pick("by", by, BEST_BY, tuple(b for b in BEST_BY if b in allowed_by))
+    return field, mode, keep_ties
+
+
 @dataclass(frozen=True)
 class Term:
     field: int    # FIELD_MP / FIELD_GAMMA / FIELD_TF

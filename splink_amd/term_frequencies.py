@@ -104,6 +104,14 @@ class TermFrequencyFrame(SplinkDataFrame):
         """Shorthand for filter(f"tf_adjusted_match_prob > {threshold!r}").clusters()."""
         return self.filter(f"tf_adjusted_match_prob > {threshold!r}").clusters()
 
+    def best_matches(self, threshold=None, per="l", ties="first"):
+        """Shorthand for filter(f"tf_adjusted_match_prob > {threshold!r}").best_matches(per, ties); threshold=None:
+        the best match among every pair."""
+        from .select import Predicate
+        f = (TfFilteredFrame(self, Predicate()) if threshold is None
+             else self.filter(f"tf_adjusted_match_prob > {threshold!r}"))
+        return f.best_matches(per=per, ties=ties)
+
 
 class TfFilteredFrame(FilteredFrame):
     """`tf.filter(condition)`: toPandas() equals tf.toPandas()[mask].reset_index(drop=True).  A predicate without a
@@ -118,6 +126,9 @@ class TfFilteredFrame(FilteredFrame):
         return TfFilteredFrame(self.parent, self.predicate.and_(more))
 
     where = filter
+
+    # best_matches() ranks by tf_adjusted_match_prob unless by="match_probability"
+    _best_by = ("tf_adjusted_match_prob", "match_probability")
 
     def _scored_parent(self):
         return self.parent.df_e
