@@ -520,6 +520,35 @@ int spk_components_copy(spk_ctx *ctx, int64_t start, int64_t count, uint32_t *ou
 int spk_components_info(spk_ctx *ctx, int64_t *out_n_nodes, int64_t *out_n_edges, int *out_rounds, double *out_ms);
 int spk_components_release(spk_ctx *ctx);
 
+/* ---- pairs against labels (no counterpart in the reference release; later releases:
+ *      truth_space_table_from_labels_column, estimate_m_from_label_column) ---- */
+#define SPK_LABEL_NON_MATCH 0   /* both labels non-NULL and different */
+#define SPK_LABEL_MATCH     1   /* both labels non-NULL and equal */
+#define SPK_LABEL_UNKNOWN   2   /* either label NULL */
+#define SPK_LABEL_STATES    3
+/* One pass over the context's pairs that counts them per (truth state, comparison pattern):
+ * out_counts[s * n_patterns + code] = pairs with state s and packed code `code`; the three states sum to bin `code`
+ * of spk_em_histogram.  match_probability is a function of the code alone, so these counts hold the exact confusion
+ * matrix at every threshold and the supervised m / u / lambda estimate.  ids_side* are one label id per record, in
+ * device row order (as for spk_tf_accumulate), one id space for both sides; any negative id is NULL.  ids_side1 may
+ * be NULL when the pairs' right rows index table 0 (dedupe_only, link_and_dedupe).  The ids are narrowed to 32 bits
+ * on the device (half the gathered footprint); an id >= 2^31 is SPK_E_INVALID.  With m and u, out_pattern_mp[code]
+ * is the match_probability of the pattern under lambda / one_minus / m / u as for spk_score, by the same device
+ * function, bit for bit; without them it must be NULL.  The counts are integers: they do not depend on launch shape or
+ * on the arrival order of the atomics, and ranks holding shards of the pairs sum them.
+ * SPK_E_STATE: no comparison codes, or no pair rows (a loaded gamma table).  SPK_E_INVALID: NULL ids_side0; NULL
+ * ids_side1 under link_only; NULL out_counts; out_pattern_mp without m / u.  SPK_E_LIMIT: 3 * n_patterns > 2^30.
+ * Reads the pairs and the codes only: no selection, score, tf, EM or component state is touched, and the call's
+ * device buffers are freed before it returns. */
+int spk_label_histogram(spk_ctx *ctx, const int64_t *ids_side0, const int64_t *ids_side1,
+                        double lambda, double one_minus, const double *m, const double *u,
+                        uint64_t *out_counts   /* host [SPK_LABEL_STATES x n_patterns], state-major */,
+                        double *out_pattern_mp /* host [n_patterns] or NULL */);
+/* The last spk_label_histogram: pairs counted (-1: none yet, or the last call failed), and with timing on
+ * (spk_ctx_enable_timing) the device milliseconds of its launches (id narrowing, pattern table, counter clear and
+ * the histogram; the uploads and read-backs are not in it), -1 otherwise. */
+int spk_label_info(spk_ctx *ctx, int64_t *out_pairs, double *out_ms);
+
 /* ---- term-frequency adjustment (term_frequencies.py:122-168) ------------------- */
 /* For value ids of one column (per row, -1 NULL; both sides in one id space) accumulate, over
  * pairs with equal non-null values, Σ mp and count(mp) per value id (n_values slots), after spk_score.

@@ -20,6 +20,7 @@ from .expectation_step import run_expectation_step
 from .frames import BestMatchFrame, ClusterFrame, FilteredFrame, SplinkDataFrame
 from .gammas import add_gammas
 from .iterate import iterate
+from .labels import LabelCounts, estimate_from_labels
 from .params import Params, load_params_from_json
 from .session import AmdSession, session
 from .settings import complete_settings_dict
@@ -28,7 +29,7 @@ from .validate import validate_settings
 
 __all__ = ["Splink", "load_from_json", "AmdSession", "session", "Params", "block_using_rules", "add_gammas",
            "iterate", "run_expectation_step", "make_adjustment_for_term_frequencies", "complete_settings_dict",
-           "ClusterFrame", "FilteredFrame", "BestMatchFrame"]
+           "ClusterFrame", "FilteredFrame", "BestMatchFrame", "LabelCounts", "estimate_from_labels"]
 
 
 def _is_frame(x):

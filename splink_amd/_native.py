@@ -75,7 +75,13 @@ EXPORTS = [
     "spk_select_tf", "spk_select_tf_columns", "spk_select_copy_tf",
     "spk_select_best", "spk_select_best_info",
     "spk_components", "spk_components_edges", "spk_components_copy", "spk_components_info", "spk_components_release",
+    "spk_label_histogram", "spk_label_info",
 ]
+LABEL_NON_MATCH, LABEL_MATCH, LABEL_UNKNOWN, LABEL_STATES = 0, 1, 2, 3  # SPK_LABEL_*
+# LDS bytes up to which spk_label_histogram keeps its 3 x n_patterns 32-bit counters in the workgroup (capped by
+# lds_per_block()); past it the counts go to global memory.  Mirrored from LH_LDS_BYTES in csrc/spk_labels.hip;
+# only the tests' choice of pattern spaces depends on it.
+LABEL_LDS_BYTES = 64 * 1024
 TF_LIMBS = 14  # SPK_TF_LIMBS
 
 
@@ -702,6 +708,40 @@ class Context:
 
     def components_release(self):
         check(self._lib.spk_components_release(self._h), "spk_components_release")
+
+    # ---- pairs against labels -----------------------------------------------------------------
+    def label_histogram(self, ids0, ids1=None, lam=None, one_minus=None, m=None, u=None):
+        """spk_label_histogram: (counts int64 [3, n_patterns] by LABEL_NON_MATCH / LABEL_MATCH / LABEL_UNKNOWN,
+        match_probability per pattern float64 [n_patterns] under lam / one_minus / m / u, or None without m / u).
+        ids0 / ids1: one label id per record in device row order (negative = NULL, one id space); ids1 = None when
+        the pairs' right rows index table 0."""
+        ids0 = np.ascontiguousarray(ids0, dtype=np.int64)
+        ids1 = None if ids1 is None else np.ascontiguousarray(ids1, dtype=np.int64)
+        if (m is None) != (u is None):
+            raise ValueError("label_histogram: m and u come together")
+        scored = m is not None
+        m = np.ascontiguousarray(m, dtype=np.float64) if scored else None
+        u = np.ascontiguousarray(u, dtype=np.float64) if scored else None
+        n_pat = self.n_patterns()
+        counts = np.zeros((LABEL_STATES, max(n_pat, 1)), dtype=np.uint64)
+        mp = np.empty(max(n_pat, 1), dtype=np.float64) if scored else None
+        if ids0.size == 0:  # an empty table: a non-NULL pointer the library never reads
+            ids0 = np.zeros(1, np.int64)
+        if ids1 is not None and ids1.size == 0:
+            ids1 = np.zeros(1, np.int64)
+        check(self._lib.spk_label_histogram(self._h, _ptr(ids0), _ptr(ids1),
+                                            ctypes.c_double(float(lam) if scored else 0.0),
+                                            ctypes.c_double(float(one_minus) if scored else 0.0), _ptr(m), _ptr(u),
+                                            _ptr(counts), _ptr(mp)), "spk_label_histogram")
+        counts = counts[:, :n_pat].astype(np.int64)
+        return counts, (mp[:n_pat] if scored else None)
+
+    def label_info(self):
+        """(pairs the last label_histogram counted or -1, ms of its launches with timing on or -1)."""
+        n = ctypes.c_int64(-1)
+        ms = ctypes.c_double(-1.0)
+        check(self._lib.spk_label_info(self._h, ctypes.byref(n), ctypes.byref(ms)), "spk_label_info")
+        return n.value, ms.value
 
     def _udf(self, fn, left, right):
         from .table import encode_utf8

@@ -481,6 +481,11 @@ struct spk_ctx {
     // spk_components*: the last labels and the HIP events around its launches (created on first use with timing on)
     spk::Components comp;
     hipEvent_t cc_ev0 = nullptr, cc_ev1 = nullptr;
+    // the last spk_label_histogram (spk_labels.hip): pairs counted (-1: none, or it failed), device milliseconds, and
+    // the HIP events around its launches (created on first use with timing on); its buffers live for the call only
+    int64_t label_pairs = -1;
+    double label_ms = -1.0;
+    hipEvent_t lab_ev0 = nullptr, lab_ev1 = nullptr;
     // the (value, pattern) runs of the last tf scale pass over a device-id column, reused by its sum pass
     spk::DevBuf<unsigned long long> tf_uniq;
     spk::DevBuf<unsigned int> tf_runs, tf_nruns;

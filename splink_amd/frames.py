@@ -145,6 +145,50 @@ class _HostColumns:
         return v
 
 
+def _label_ids(job, label_column):
+    """(ids of side 0, ids of side 1 or None): one dense label id per record in device row order, -1 = NULL, one
+    id space for both sides (link_only: side 1 is the right table; otherwise the right rows index table 0)."""
+    from . import table as T
+    sides = (0, 1) if job.link_type == "link_only" else (0,)
+    for s in sides:
+        if label_column not in job.inputs[s].columns:
+            raise ValueError(f"label column {label_column!r} is missing from input table {s}")
+    key = ("label_ids", label_column)  # kept with the host columns: a new row order (block) drops both
+    if key not in job._host_cols:
+        vals = []
+        for s in sides:
+            v = job.host_values(s, label_column)
+            if v.dtype == object:
+                v = pd.Series([None if T.is_null_scalar(x) else x for x in v.tolist()], dtype=object)
+            vals.append(pd.Series(v))  # numeric dtypes: NaN / NaT are the NULLs, and factorize gives them -1
+        codes, _ = T.factorize_joint(vals)
+        job._host_cols[key] = (codes[0], codes[1] if len(codes) > 1 else None)
+    return job._host_cols[key]
+
+
+def _label_counts(gamma_frame, label_column, lam=None, level_probs=None):
+    """LabelCounts of a frame's pairs against `label_column` of the input tables (spk_label_histogram); with lam /
+    level_probs also the match_probability of every pattern under them."""
+    from . import distributed as D
+    from .labels import LabelCounts, true_pairs_total
+    job = gamma_frame.job
+    if getattr(job, "passthrough", None) is not None:
+        raise ValueError("label_counts() needs the records: a job made from a gamma table has pairs without rows")
+    ids0, ids1 = _label_ids(job, label_column)
+    gamma_frame.ensure_codes()
+    if level_probs is None:
+        counts, mp = job.ctx.label_histogram(ids0, ids1)
+    else:
+        m, u = job.flat_tables(level_probs)
+        counts, mp = job.ctx.label_histogram(ids0, ids1, float(lam), float(1 - lam), m, u)
+    if job.reduces_across_ranks() or job.force_reduce:
+        # ranks hold shards of the pairs: exact integer sums, so every rank ends with the one-GPU counts.  Every
+        # rank holds all the records, so the true pairs are counted locally.
+        D.allreduce_host_(counts, force=job.force_reduce)
+    names, levels = gamma_frame.meta
+    return LabelCounts(names, levels, counts, mp, job.link_type, true_pairs_total(job.link_type, ids0, ids1))
+
+
 class ComparisonFrame(SplinkDataFrame):
     """Candidate pairs (block_using_rules)."""
 
@@ -225,6 +269,12 @@ class GammaFrame(SplinkDataFrame):
 
     where = filter
 
+    def label_counts(self, label_column):
+        """The pairs per (truth state, comparison pattern) against the input column `label_column` (equal labels =
+        a true match, a NULL label on either side = unlabelled), counted on the device: a `LabelCounts` without
+        scores (its patterns() and m_step() work, truth_table() needs the scored frame's)."""
+        return _label_counts(self, label_column)
+
 
 class ExpectationFrame(SplinkDataFrame):
     """E-step output (run_expectation_step): lazily scored with the parameters it was created with."""
@@ -297,6 +347,16 @@ class ExpectationFrame(SplinkDataFrame):
         from .select import Predicate
         f = FilteredFrame(self, Predicate()) if threshold is None else self.filter(f"match_probability > {threshold!r}")
         return f.best_matches(per=per, ties=ties)
+
+    def label_counts(self, label_column):
+        """GammaFrame.label_counts with the match_probability of every pattern under this frame's parameters."""
+        return _label_counts(self.gammas, label_column, self.lam, self.level_probs)
+
+    def truth_table(self, label_column, thresholds=None):
+        """The confusion matrix of `match_probability > threshold` against the labels in the input column
+        `label_column`, at the given thresholds or (None) at every distinct score: the exact ROC and
+        precision / recall curve.  Shorthand for label_counts(label_column).truth_table(thresholds)."""
+        return self.label_counts(label_column).truth_table(thresholds)
 
 
 class FilteredFrame(SplinkDataFrame):

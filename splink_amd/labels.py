@@ -1,0 +1,176 @@
+"""Scoring a linkage against labels (no counterpart in the reference release; later releases:
+truth_space_table_from_labels_column, roc_chart_from_labels_column, estimate_m_from_label_column).
+
+match_probability is a function of a pair's comparison pattern alone, so one device pass that counts the pairs per
+(truth state, pattern) (spk_label_histogram) leaves the host with everything it needs, over n_patterns rows only:
+the exact confusion matrix at every threshold, the true pairs blocking never produced, and the supervised estimate
+of m / u / λ -- one M-step with match_probability replaced by the label.  This module is the host side: pure
+numpy / pandas, importable without a device.
+"""
+from __future__ import annotations
+
+import numpy as np
+import pandas as pd
+
+from .engine import N_HEAD, m_step_rows
+
+NON_MATCH, MATCH, UNKNOWN = 0, 1, 2  # SPK_LABEL_NON_MATCH / _MATCH / _UNKNOWN: the rows of LabelCounts.counts
+
+
+def _group_sizes(ids):
+    """{label id: records} over the non-NULL (non-negative) ids, as (sorted ids, counts)."""
+    ids = np.asarray(ids, dtype=np.int64)
+    return np.unique(ids[ids >= 0], return_counts=True)
+
+
+def true_pairs_total(link_type, ids0, ids1=None) -> int:
+    """The record pairs with equal non-NULL labels that the link type compares at all, whether or not blocking
+    produced them: Σ C(n_g, 2) over the one table of dedupe_only and link_and_dedupe (for the latter the vertical
+    concatenation: a pair within the left, within the right or across), Σ n_g(left) · n_g(right) for link_only."""
+    v0, c0 = _group_sizes(ids0)
+    if link_type != "link_only":
+        return int(sum(int(c) * (int(c) - 1) // 2 for c in c0.tolist()))
+    if ids1 is None:
+        raise ValueError("true_pairs_total: link_only needs the right table's label ids")
+    v1, c1 = _group_sizes(ids1)
+    _, i0, i1 = np.intersect1d(v0, v1, assume_unique=True, return_indices=True)
+    return int(sum(int(a) * int(b) for a, b in zip(c0[i0].tolist(), c1[i1].tolist())))
+
+
+def _ratio(num, den):
+    """num / den elementwise on integer arrays, NaN for 0 / 0."""
+    num, den = np.asarray(num, dtype=np.int64), np.asarray(den, dtype=np.int64)
+    out = np.full(len(num), np.nan, dtype=np.float64)
+    ok = den != 0
+    out[ok] = num[ok] / den[ok]
+    return out
+
+
+class LabelCounts:
+    """Pairs per (truth state, comparison pattern) of one pair set, and what follows from them.
+
+    names / n_levels: the gamma columns (`gamma_*`) and their level counts, which define the packed code
+    (code = Σ_k (γ_k + 1) · Π_{j<k} (L_j + 1)); counts int64 [3, n_patterns] by NON_MATCH / MATCH / UNKNOWN (either
+    label NULL); mp: match_probability per pattern (NaN = NULL) or None for an unscored frame; true_pairs_total as
+    the function of that name gives it."""
+
+    def __init__(self, names, n_levels, counts, mp=None, link_type="dedupe_only", true_pairs_total=0):
+        self.names = list(names)
+        self.n_levels = [int(L) for L in n_levels]
+        n_pat = 1
+        for L in self.n_levels:
+            n_pat *= L + 1
+        self.counts = np.ascontiguousarray(counts, dtype=np.int64)
+        if self.counts.shape != (3, n_pat):
+            raise ValueError(f"LabelCounts: counts must be [3, {n_pat}] for levels {self.n_levels}")
+        self.mp = None if mp is None else np.ascontiguousarray(mp, dtype=np.float64)
+        if self.mp is not None and self.mp.shape != (n_pat,):
+            raise ValueError(f"LabelCounts: mp must be [{n_pat}]")
+        self.link_type = link_type
+        self.true_pairs_total = int(true_pairs_total)
+        self.missed_by_blocking = self.true_pairs_total - int(self.counts[MATCH].sum())
+
+    @property
+    def n_patterns(self) -> int:
+        return self.counts.shape[1]
+
+    def levels(self, codes) -> np.ndarray:
+        """int32 [len(codes), K]: the gamma levels of packed codes, decoded as the pattern space packs them."""
+        codes = np.asarray(codes, dtype=np.int64)
+        out = np.empty((len(codes), len(self.n_levels)), dtype=np.int32)
+        stride = 1
+        for k, L in enumerate(self.n_levels):
+            out[:, k] = (codes // stride) % (L + 1) - 1
+            stride *= L + 1
+        return out
+
+    def patterns(self) -> pd.DataFrame:
+        """One row per pattern that occurs, ascending code: the gamma_* levels, match_probability if scored, then
+        n_match, n_non_match, n_unlabelled."""
+        codes = np.flatnonzero(self.counts.sum(axis=0) > 0)
+        lev = self.levels(codes)
+        data = {name: lev[:, k] for k, name in enumerate(self.names)}
+        if self.mp is not None:
+            data["match_probability"] = self.mp[codes]
+        data["n_match"] = self.counts[MATCH, codes]
+        data["n_non_match"] = self.counts[NON_MATCH, codes]
+        data["n_unlabelled"] = self.counts[UNKNOWN, codes]
+        return pd.DataFrame(data)
+
+    def truth_table(self, thresholds=None) -> pd.DataFrame:
+        """The confusion matrix of `match_probability > threshold` against the labels, one row per threshold,
+        ascending -- filter()'s and clusters(threshold)'s `>`; a NULL (NaN) score is never predicted a match.
+        thresholds=None: every distinct non-NULL score of a pattern that occurs, preceded by one threshold below
+        them all, i.e. every point of the exact ROC.  tp, fp, tn, fn count labelled pairs only; n_unlabelled_above
+        the pairs above the threshold with a NULL label; precision, recall, fpr, f1 are NaN for 0 / 0;
+        recall_of_all_true_pairs = tp / true_pairs_total also counts the true pairs blocking never produced."""
+        if self.mp is None:
+            raise ValueError("truth_table: these counts carry no match_probability (label_counts() of an unscored "
+                             "frame): take them from the frame run_expectation_step returns")
+        occurs = (self.counts.sum(axis=0) > 0) & ~np.isnan(self.mp)
+        score = self.mp[occurs]
+        order = np.argsort(score, kind="stable")
+        score = score[order]
+        # suffix[:, i] = pairs of each state at the i-th smallest score and above (suffix[:, n] = 0)
+        by_state = self.counts[:, occurs][:, order]
+        suffix = np.zeros((3, len(score) + 1), dtype=np.int64)
+        suffix[:, :-1] = np.cumsum(by_state[:, ::-1], axis=1)[:, ::-1]
+        if thresholds is None:
+            distinct = np.unique(score)
+            t = np.concatenate([[np.nextafter(distinct[0], -np.inf)], distinct]) if len(distinct) else distinct
+        else:
+            t = np.sort(np.asarray(list(thresholds), dtype=np.float64))
+            if np.isnan(t).any():
+                raise ValueError("truth_table: a threshold is NaN")
+        first_above = np.searchsorted(score, t, side="right")  # score[i] > t  <=>  i >= first_above
+        above = suffix[:, first_above]
+        tp, fp, unl = above[MATCH], above[NON_MATCH], above[UNKNOWN]
+        fn = int(self.counts[MATCH].sum()) - tp
+        tn = int(self.counts[NON_MATCH].sum()) - fp
+        return pd.DataFrame({
+            "threshold": t, "tp": tp, "fp": fp, "tn": tn, "fn": fn, "n_unlabelled_above": unl,
+            "precision": _ratio(tp, tp + fp), "recall": _ratio(tp, tp + fn), "fpr": _ratio(fp, fp + tn),
+            "f1": _ratio(2 * tp, 2 * tp + fp + fn),
+            "recall_of_all_true_pairs": _ratio(tp, np.full(len(t), self.true_pairs_total, dtype=np.int64)),
+        })
+
+    def m_step_stats(self) -> np.ndarray:
+        """The M-step's statistics vector (engine.N_HEAD + 4 per (column, level incl. -1), as spk_em_finalize
+        returns it) with match_probability replaced by the label: 1 for MATCH, 0 for NON_MATCH, unlabelled pairs
+        left out.  (The log-likelihood slots stay 0: the M-step does not read them.)"""
+        nm, nn = self.counts[MATCH], self.counts[NON_MATCH]
+        lab = nm + nn
+        stats = np.zeros(N_HEAD + 4 * sum(L + 1 for L in self.n_levels), dtype=np.float64)
+        stats[0], stats[1], stats[2] = nm.sum(), lab.sum(), lab.sum()
+        lev = self.levels(np.arange(self.n_patterns))
+        off = N_HEAD
+        for k, L in enumerate(self.n_levels):
+            for v in range(-1, L):
+                at = lev[:, k] == v
+                rows = int(lab[at].sum())
+                stats[off: off + 4] = (rows, rows, int(nm[at].sum()), int(nn[at].sum()))
+                off += 4
+        return stats
+
+    def m_step(self):
+        """(λ, π rows) in the shape engine.m_step_rows returns: the supervised estimate of the parameters."""
+        return m_step_rows(self.m_step_stats(), self.names, self.n_levels)
+
+
+def estimate_from_labels(df_gammas: object, params, settings: dict, spark: object, label_column: str):
+    """The supervised counterpart of iterate(): one M-step over the labelled pairs of `df_gammas` (the frame
+    add_gammas returns) with match_probability replaced by `label_column_l == label_column_r`, through
+    params._update_params, then the E-step under the new parameters.  Returns that scored frame."""
+    from .expectation_step import run_expectation_step
+    from .frames import ExpectationFrame, GammaFrame, reject_filtered
+    reject_filtered(df_gammas, "estimate_from_labels")
+    gf = df_gammas.gammas if isinstance(df_gammas, ExpectationFrame) else df_gammas
+    if not isinstance(gf, GammaFrame):
+        raise ValueError("estimate_from_labels needs the records' labels: pass the frame add_gammas returns (a gamma "
+                         "table has pairs without rows)")
+    counts = gf.label_counts(label_column)
+    if int(counts.counts[:UNKNOWN].sum()) == 0:
+        raise ValueError(f"estimate_from_labels: no pair has a label on both sides in column {label_column!r}")
+    lam, rows = counts.m_step()
+    params._update_params(lam, rows)
+    return run_expectation_step(gf, params, settings, spark)
