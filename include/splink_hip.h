@@ -164,6 +164,42 @@ int spk_pairs_count(spk_ctx *ctx, int64_t *out);
 int spk_pairs_copy(spk_ctx *ctx, int64_t start, int64_t count, int32_t *out_l, int32_t *out_r);
 /* Use caller-provided pairs (e.g. add_gammas on an externally built comparison frame). */
 int spk_pairs_load(spk_ctx *ctx, int64_t n, const int32_t *rows_l, const int32_t *rows_r);
+/* Random record pairs, drawn on the device (no counterpart in the reference release; later releases:
+ * estimate_u_using_random_sampling).  Replaces the pair set by the surviving draws among the ordinals
+ * [first_draw, first_draw + n_draws) of a sample of total_draws, in ordinal order; like a loaded list the set has
+ * no rules, no views and no key terms, and spk_gammas follows as usual.  Draw i is a function of (seed, i,
+ * total_draws, the table sizes, the ranks) only -- not of the range, the grid or the launch shape -- so the
+ * concatenation of the results over any partition of [0, total_draws) into ranges is the whole sample.  The draws
+ * are independent: this is sampling WITH replacement, the same pair may occur more than once (about
+ * N^2 / (2 * pairs) duplicates among N draws from `pairs` possible pairs).
+ *
+ * Definition (all arithmetic mod 2^64; n0, n1 the row counts of table 0 and table 1; rank as spk_table_set_rank):
+ *   mix(x):      x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31
+ *                (the splitmix64 finaliser)
+ *   word(i, j) = mix(mix(seed) + 0x9E3779B97F4A7C15 * (3 * i + j + 1)),  j = 0, 1, 2
+ *   below(w, n) = (w * n) >> 64  (the high 64 bits of the 128-bit product)
+ *   anchor (stratified: draw i's anchor lies in the i-th of total_draws equal slices of table 0, so the anchors are
+ *   non-decreasing in i and the anchor side of the comparison pass streams through the table):
+ *     lo = (i * n0) / total_draws,  hi = ((i + 1) * n0) / total_draws  (exact integer quotients)
+ *     a = lo + below(word(i, 0), hi - lo) when hi > lo, else a = lo
+ *   link_only:  b = below(word(i, 1), n1); the pair is (l, r) = (a, b), a row of table 0 and a row of table 1.  Every
+ *     draw survives.  No pairs when n0 = 0 or n1 = 0.
+ *   dedupe_only, link_and_dedupe (one table):  b = below(word(i, 1), n0 - 1), then b += (b >= a).  The pair is the two
+ *     rows ordered by rank, the lower rank as l.  The draw is dropped when the ranks are equal, and under the
+ *     NULL-unique-id rule of spk_block (spk_table_set_rank_null with divisor d > 0: dropped when rank(l) / d ==
+ *     rank(r) / d and either rank % d == d - 1).  Every sampled pair is thus one the blocking of no rules (the
+ *     cartesian product under the link-type predicate) produces.  No pairs when n0 < 2.
+ *   word(i, 2) is reserved: nothing reads it now, so a later per-draw decision does not move the pairs.
+ *
+ * SPK_E_STATE: tables not loaded, or no rank under dedupe_only / link_and_dedupe.  SPK_E_INVALID: a negative
+ * total_draws, first_draw or n_draws, or a range that ends past total_draws.  SPK_E_LIMIT: total_draws * n0 does not
+ * fit in 63 bits.  A failing call leaves no pair set. */
+int spk_pairs_sample(spk_ctx *ctx, int link_type, uint64_t seed, int64_t total_draws, int64_t first_draw,
+                     int64_t n_draws, int64_t *out_n_pairs);
+/* The last spk_pairs_sample: draws generated and pairs kept (-1 each: none yet, or the last call failed), and with
+ * timing on (spk_ctx_enable_timing) the device milliseconds of its launches (count kernel, scan, emit kernel),
+ * -1 otherwise. */
+int spk_pairs_sample_info(spk_ctx *ctx, int64_t *out_draws, int64_t *out_kept, double *out_ms);
 
 /* ---- comparison programs (replaces add_gammas / the CASE templates,
  *      gammas.py:65-124, case_statements.py:62-277) ----------------------------- */

@@ -22,6 +22,7 @@ from .gammas import add_gammas
 from .iterate import iterate
 from .labels import LabelCounts, estimate_from_labels
 from .params import Params, load_params_from_json
+from .sampling import estimate_u_using_random_sampling, random_pairs
 from .session import AmdSession, session
 from .settings import complete_settings_dict
 from .term_frequencies import make_adjustment_for_term_frequencies
@@ -29,7 +30,8 @@ from .validate import validate_settings
 
 __all__ = ["Splink", "load_from_json", "AmdSession", "session", "Params", "block_using_rules", "add_gammas",
            "iterate", "run_expectation_step", "make_adjustment_for_term_frequencies", "complete_settings_dict",
-           "ClusterFrame", "FilteredFrame", "BestMatchFrame", "LabelCounts", "estimate_from_labels"]
+           "ClusterFrame", "FilteredFrame", "BestMatchFrame", "LabelCounts", "estimate_from_labels",
+           "estimate_u_using_random_sampling", "random_pairs"]
 
 
 def _is_frame(x):
@@ -87,6 +89,13 @@ class Splink:
                        save_state_fn=self.save_state_fn)
         df_gammas.unpersist()
         return df_e
+
+    def estimate_u_using_random_sampling(self, max_pairs: int, seed: int = 0, fix: bool = True):
+        """u of every comparison level from `max_pairs` random record pairs of the linker's own tables, drawn and
+        compared on the device; with fix=True the EM of get_scored_comparisons then moves only m and λ.  Returns
+        the (gamma column, level) table of counts and u (sampling.estimate_u_using_random_sampling)."""
+        return estimate_u_using_random_sampling(self.settings, self.params, self.spark, max_pairs, seed=seed,
+                                                fix=fix, df_l=self.df_l, df_r=self.df_r, df=self.df)
 
     def make_term_frequency_adjustments(self, df_e: SplinkDataFrame):
         return make_adjustment_for_term_frequencies(df_e, self.params, self.settings, retain_adjustment_columns=True,

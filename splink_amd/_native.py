@@ -76,7 +76,11 @@ EXPORTS = [
     "spk_select_best", "spk_select_best_info",
     "spk_components", "spk_components_edges", "spk_components_copy", "spk_components_info", "spk_components_release",
     "spk_label_histogram", "spk_label_info",
+    "spk_pairs_sample", "spk_pairs_sample_info",
 ]
+# Draws per workgroup of spk_pairs_sample's kernel (256 threads x 8 consecutive draws).  Mirrored from SM_CHUNK in
+# csrc/spk_sample.hip; only the tests' edge sizes depend on it.
+SAMPLE_CHUNK = 2048
 LABEL_NON_MATCH, LABEL_MATCH, LABEL_UNKNOWN, LABEL_STATES = 0, 1, 2, 3  # SPK_LABEL_*
 # LDS bytes up to which spk_label_histogram keeps its 3 x n_patterns 32-bit counters in the workgroup (capped by
 # lds_per_block()); past it the counts go to global memory.  Mirrored from LH_LDS_BYTES in csrc/spk_labels.hip;
@@ -346,6 +350,26 @@ class Context:
         rows_r = np.ascontiguousarray(rows_r, dtype=np.int32)
         check(self._lib.spk_pairs_load(self._h, ctypes.c_int64(len(rows_l)), _ptr(rows_l), _ptr(rows_r)),
               "spk_pairs_load")
+
+    def pairs_sample(self, link_type: int, seed: int, total: int, first: int, count: int) -> int:
+        """spk_pairs_sample: replace the pair set by the surviving draws among the ordinals [first, first + count)
+        of a random sample of `total` draws under `seed` (with replacement; splink_hip.h has the definition);
+        returns how many pairs survive."""
+        n = ctypes.c_int64(0)
+        check(self._lib.spk_pairs_sample(self._h, ctypes.c_int(int(link_type)),
+                                         ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_int64(int(total)),
+                                         ctypes.c_int64(int(first)), ctypes.c_int64(int(count)), ctypes.byref(n)),
+              "spk_pairs_sample")
+        return n.value
+
+    def pairs_sample_info(self):
+        """(draws of the last pairs_sample or -1, pairs it kept or -1, ms of its launches with timing on or -1)."""
+        d = ctypes.c_int64(-1)
+        k = ctypes.c_int64(-1)
+        ms = ctypes.c_double(-1.0)
+        check(self._lib.spk_pairs_sample_info(self._h, ctypes.byref(d), ctypes.byref(k), ctypes.byref(ms)),
+              "spk_pairs_sample_info")
+        return d.value, k.value, ms.value
 
     @staticmethod
     def gammas_args(programs, when_first, when_n, when_level, instrs, operands, lit_offsets, lit_bytes):

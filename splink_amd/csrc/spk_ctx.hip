@@ -532,6 +532,8 @@ void spk_ctx_destroy(spk_ctx *ctx) {
     if (ctx->cc_ev1) (void)hipEventDestroy(ctx->cc_ev1);
     if (ctx->lab_ev0) (void)hipEventDestroy(ctx->lab_ev0);
     if (ctx->lab_ev1) (void)hipEventDestroy(ctx->lab_ev1);
+    if (ctx->smp_ev0) (void)hipEventDestroy(ctx->smp_ev0);
+    if (ctx->smp_ev1) (void)hipEventDestroy(ctx->smp_ev1);
     if (ctx->ev_info) (void)hipEventDestroy(ctx->ev_info);
     if (ctx->ev_stats) (void)hipEventDestroy(ctx->ev_stats);
     if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);

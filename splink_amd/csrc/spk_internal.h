@@ -486,6 +486,11 @@ struct spk_ctx {
     int64_t label_pairs = -1;
     double label_ms = -1.0;
     hipEvent_t lab_ev0 = nullptr, lab_ev1 = nullptr;
+    // the last spk_pairs_sample (spk_sample.hip): draws generated and pairs kept (-1: none, or it failed), device
+    // milliseconds of its launches, and the HIP events around them (created on first use with timing on)
+    int64_t sample_draws = -1, sample_kept = -1;
+    double sample_ms = -1.0;
+    hipEvent_t smp_ev0 = nullptr, smp_ev1 = nullptr;
     // the (value, pattern) runs of the last tf scale pass over a device-id column, reused by its sum pass
     spk::DevBuf<unsigned long long> tf_uniq;
     spk::DevBuf<unsigned int> tf_runs, tf_nruns;

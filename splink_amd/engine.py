@@ -488,6 +488,15 @@ class Job:
         self.codes_token = None
         self.codes_seq += 1
 
+    def sample_pairs(self, total: int, first: int, count: int, seed: int = 0):
+        """Random pairs drawn on the device (spk_pairs_sample): the surviving draws among the ordinals
+        [first, first + count) of a sample of `total` become the pair set; returns how many."""
+        self.n_pairs = self.ctx.pairs_sample(N.LINK_TYPES[self.link_type], seed, total, first, count)
+        self._pairs_host = None
+        self.codes_token = None
+        self.codes_seq += 1
+        return self.n_pairs
+
     def pair_rows(self):
         if self._pairs_host is None:
             self._pairs_host = self.ctx.pairs_copy(0, self.n_pairs)
@@ -570,6 +579,20 @@ class Job:
             torch.cuda.synchronize(self.device)
             return self.ctx.em_finalize(hist.data_ptr(), lam_d, one_minus, m, u, n_stats)
         return self.ctx.em_iteration(lam_d, one_minus, m, u, n_stats)
+
+    def pattern_histogram(self) -> np.ndarray:
+        """Pairs per comparison pattern of the installed codes (spk_em_histogram) as a host int64 [n_patterns];
+        summed over the ranks when the pair set is sharded over the process group (exact integers)."""
+        import torch
+        hist = self._device_hist()
+        if self.n_pairs > 0:
+            self.ctx.em_histogram(hist.data_ptr())  # zeroes, fills and synchronises its stream
+        else:
+            hist.zero_()
+        if self.reduces_across_ranks() or self.force_reduce:
+            D.allreduce_histogram_(hist, force=self.force_reduce)
+        torch.cuda.synchronize(self.device)
+        return hist.cpu().numpy().astype(np.int64, copy=True)
 
     def _device_hist(self):
         import torch

@@ -43,6 +43,9 @@ class Params:
         self.params = {"λ": settings["proportion_of_matches"], "π": {}}
         self.log_likelihood_exists = False
         self.real_params = None
+        # True: an M-step leaves every u (prob_dist_non_match) as it was and moves only m and λ
+        # (estimate_u_using_random_sampling sets it: u then comes from random pairs, not from the blocked ones)
+        self.fix_u_probabilities = False
         self._generate_param_dict()
 
     @property
@@ -162,11 +165,22 @@ class Params:
         self._save_params_to_iteration_history()
         self._reset_param_values_to_none()
         self._populate_params(lambda_value, pi_df_collected)
+        if self.fix_u_probabilities:
+            self._restore_u_from(self.param_history[-1])
         self.iteration += 1
+
+    def _restore_u_from(self, saved):
+        """Every prob_dist_non_match probability back to its value in `saved` (a params dict of the history)."""
+        for gamma_str, d in saved["π"].items():
+            for level in d["prob_dist_non_match"].values():
+                self._set_pi_value(gamma_str, level["value"], "non_match", level["probability"])
 
     # ---- persistence ----------------------------------------------------------------------------
     def _to_dict(self):
-        return {"current_params": self.params, "historical_params": self.param_history, "settings": self.settings}
+        out = {"current_params": self.params, "historical_params": self.param_history, "settings": self.settings}
+        if self.fix_u_probabilities:  # written only when set: a model without it is the reference's document
+            out["fix_u_probabilities"] = True
+        return out
 
     def save_params_to_json_file(self, path=None, overwrite=False):
         if not path:
@@ -249,11 +263,12 @@ def load_params_from_json(path):
 
 
 def load_params_from_dict(param_dict):
-    if set(param_dict.keys()) != {"current_params", "settings", "historical_params"}:
+    if set(param_dict.keys()) - {"fix_u_probabilities"} != {"current_params", "settings", "historical_params"}:
         raise ValueError("Your saved params seem to be corrupted")
     p = Params(settings=param_dict["settings"], spark=None)
     p.params = param_dict["current_params"]
     p.param_history = param_dict["historical_params"]
+    p.fix_u_probabilities = bool(param_dict.get("fix_u_probabilities", False))
     return p
 
 
