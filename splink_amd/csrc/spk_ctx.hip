@@ -383,24 +383,24 @@ int spk_ctx::end(Kern k) {
     return SPK_OK;
 }
 
-int spk_ctx::xbegin(int k) {
+int spk_ctx::xbegin(Slot &s, int k) {
     if (!timing || !timing_exact) return SPK_OK;
-    while ((int)xev0.size() <= k) {
+    while ((int)s.xev0.size() <= k) {
         hipEvent_t a = nullptr, b = nullptr;
         SPK_HIP(hipEventCreate(&a));
         SPK_HIP(hipEventCreate(&b));
-        xev0.push_back(a);
-        xev1.push_back(b);
-        xev_used.push_back(0);
+        s.xev0.push_back(a);
+        s.xev1.push_back(b);
+        s.xev_used.push_back(0);
     }
-    xev_used[k] = 0;
-    SPK_HIP(hipEventRecord(xev0[k], stream));
+    s.xev_used[k] = 0;
+    SPK_HIP(hipEventRecord(s.xev0[k], s.stream));
     return SPK_OK;
 }
-int spk_ctx::xend(int k) {
+int spk_ctx::xend(Slot &s, int k) {
     if (!timing || !timing_exact) return SPK_OK;
-    SPK_HIP(hipEventRecord(xev1[k], stream));
-    xev_used[k] = 1;
+    SPK_HIP(hipEventRecord(s.xev1[k], s.stream));
+    s.xev_used[k] = 1;
     return SPK_OK;
 }
 
@@ -423,9 +423,8 @@ void spk_ctx::pairs_replaced(int64_t n) {
     sel.clear();        // a selection's survivors are pairs of the old set (spk_select_copy refuses it by epoch as well)
     // the next three were cleared by spk_block_residual alone:
     // gamma_pending: with codes_valid false, settle_slot only waits for the read-back event and returns; the
-    //   stream is synchronised here, and the alternate slot's flag is dropped without a wait there too
-    gamma_pending = false;
-    alt.gamma_pending = false;
+    //   stream is synchronised here, and the second slot's flag is dropped without a wait there too
+    for (Slot &s : slot) s.gamma_pending = false;
     // slow_seen_valid: read by spk_gammas after it has compared slow_key_pairs with pairs_epoch, bumped above
     slow_seen_valid = false;
     // mpat_valid: read behind codes_valid (tf_ready); codes come back only through spk_gammas or
@@ -491,7 +490,7 @@ int spk_ctx_create(int device, spk_ctx **out) {
             (void)hipEventCreate(&c->ev0[b][k]);
             (void)hipEventCreate(&c->ev1[b][k]);
         }
-    (void)hipEventCreateWithFlags(&c->ev_info, hipEventDisableTiming);
+    (void)hipEventCreateWithFlags(&c->slot[0].ev_info, hipEventDisableTiming);
     (void)hipEventCreateWithFlags(&c->ev_stats, hipEventDisableTiming);
     *out = c;
     return SPK_OK;
@@ -506,21 +505,19 @@ void spk_ctx_destroy(spk_ctx *ctx) {
             (void)hipEventDestroy(ctx->ev0[b][k]);
             (void)hipEventDestroy(ctx->ev1[b][k]);
         }
-    for (size_t k = 0; k < ctx->xev0.size(); ++k) {
-        (void)hipEventDestroy(ctx->xev0[k]);
-        (void)hipEventDestroy(ctx->xev1[k]);
+    if (ctx->split_ready) (void)hipStreamSynchronize(ctx->slot[1].stream);
+    for (spk_ctx::Slot &s : ctx->slot) {
+        for (size_t k = 0; k < s.xev0.size(); ++k) {
+            (void)hipEventDestroy(s.xev0[k]);
+            (void)hipEventDestroy(s.xev1[k]);
+        }
+        if (s.ev_info) (void)hipEventDestroy(s.ev_info);
+        if (s.h_info) (void)hipHostFree(s.h_info);
     }
     if (ctx->split_ready) {
-        (void)hipStreamSynchronize(ctx->alt.stream);
-        for (size_t k = 0; k < ctx->alt.xev0.size(); ++k) {
-            (void)hipEventDestroy(ctx->alt.xev0[k]);
-            (void)hipEventDestroy(ctx->alt.xev1[k]);
-        }
-        (void)hipEventDestroy(ctx->alt.ev_info);
         (void)hipEventDestroy(ctx->ev_fork);
         (void)hipEventDestroy(ctx->ev_join);
-        if (ctx->alt.h_info) (void)hipHostFree(ctx->alt.h_info);
-        (void)hipStreamDestroy(ctx->alt.stream);
+        (void)hipStreamDestroy(ctx->slot[1].stream);
     }
     if (ctx->gexec) (void)hipGraphExecDestroy(ctx->gexec);
     if (ctx->graph) (void)hipGraphDestroy(ctx->graph);
@@ -534,10 +531,8 @@ void spk_ctx_destroy(spk_ctx *ctx) {
     if (ctx->lab_ev1) (void)hipEventDestroy(ctx->lab_ev1);
     if (ctx->smp_ev0) (void)hipEventDestroy(ctx->smp_ev0);
     if (ctx->smp_ev1) (void)hipEventDestroy(ctx->smp_ev1);
-    if (ctx->ev_info) (void)hipEventDestroy(ctx->ev_info);
     if (ctx->ev_stats) (void)hipEventDestroy(ctx->ev_stats);
     if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);
-    if (ctx->h_info) (void)hipHostFree(ctx->h_info);
     hipStream_t own = ctx->own_stream;
     delete ctx;
     if (own) (void)hipStreamDestroy(own);

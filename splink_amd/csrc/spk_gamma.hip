@@ -2268,68 +2268,63 @@ static int huge_scratch(int64_t units, int64_t cells, DevBuf<uint8_t> &buf, Scra
 }
 
 // What the exact / slow / huge passes of the last spk_gammas need, kept so that an overflow of the work
-// lists or cells past SLOW_LIMIT can be settled after the call returned (settle_gammas).
+// lists or cells past SLOW_LIMIT can be settled after the call returned (settle_gammas): the column decisions
+// once per call (spk_ctx::gcols), and in each window's slot its arguments and what its settlement read.
 namespace spk {
-struct GammaPlan {
-    GammaArgs A{};
+struct GammaCols {
     std::vector<SimpleCol> simple;
     std::vector<int> simple_of;
     std::vector<char> may_exact, huge_in_slow, free_text, bag;
-    std::vector<char> slow_skipped;  // columns whose slow-list kernels this call did not launch
-    int K = 0, n_regions = 0, n_info = 0, n_cnt = 0, n_all = 0;
-    int64_t g_exact = 1, max_units = 1;
+    int K = 0, n_info = 0, n_cnt = 0, n_all = 0;
+    int64_t max_units = 1;
+};
+struct GammaPlan {
+    GammaArgs A{};                   // the window as a pair set of its own
+    int n_regions = 0;
+    int64_t g_exact = 1;
+    int64_t first = 0;               // its first pair ordinal
+    std::vector<char> slow_skipped;  // columns whose slow-list kernels the window did not launch
+    // read by its settlement, per column: start of the exact list in xlist, exact-pass cells, slow list not empty
+    std::vector<int64_t> xbase, exact;
+    std::vector<uint8_t> slow_seen;
+    int64_t deferred = 0;            // its slow-list cells
 };
 }  // namespace spk
 
-template <class T>
-static void swap_buf(spk::DevBuf<T> &a, spk::DevBuf<T> &b) {
-    std::swap(a.p, b.p);
-    std::swap(a.n, b.n);
+spk_ctx::~spk_ctx() {
+    for (spk::RawCol *r : raw) delete r;
+    delete gcols;
+    for (Slot &s : slot) delete s.gplan;
 }
-
-void spk_ctx::swap_slot() {
-    swap_buf(work, alt.work);
-    swap_buf(xlist, alt.xlist);
-    swap_buf(xpref, alt.xpref);
-    swap_buf(xinfo, alt.xinfo);
-    swap_buf(region_count, alt.region_count);
-    std::swap(xcap, alt.xcap);
-    std::swap(h_info, alt.h_info);
-    std::swap(h_info_n, alt.h_info_n);
-    std::swap(ev_info, alt.ev_info);
-    std::swap(gplan, alt.gplan);
-    std::swap(gamma_pending, alt.gamma_pending);
-    std::swap(stream, alt.stream);
-    std::swap(xev0, alt.xev0);
-    std::swap(xev1, alt.xev1);
-    std::swap(xev_used, alt.xev_used);
-}
+using Slot = spk_ctx::Slot;
 
 // The exact and slow passes over the lists the filter wrote (list capacity `cap`).  k_prefix sizes the
 // lists on the device; if they exceed `cap` every exact kernel is a no-op and settle_gammas re-runs
 // this phase with the right capacity.
 // The slow-list kernels of column k (or of the fused JW columns jk): the cells the exact pass left.
-static int enqueue_slow(spk_ctx *ctx, GammaPlan &G, int k, const ColSet *jk) {
+static int enqueue_slow(spk_ctx *ctx, Slot &S, int k, const ColSet *jk) {
+    const GammaCols &C = *ctx->gcols;
+    GammaPlan &G = *S.gplan;
     GammaArgs &A = G.A;
     if (jk) {
-        k_gamma_slow<<<dim3((unsigned)(4 * ctx->n_cu), (unsigned)jk->n), 64, 0, ctx->stream>>>(A, *jk, ctx->xlist.p,
-                                                                                              ctx->xinfo.p);
+        k_gamma_slow<<<dim3((unsigned)(4 * ctx->n_cu), (unsigned)jk->n), 64, 0, S.stream>>>(A, *jk, S.xlist.p,
+                                                                                              S.xinfo.p);
     } else {
-        const int si = G.simple_of[k];
-        const bool lev = si >= 0 && G.simple[si].cls == SC_LEV;
+        const int si = C.simple_of[k];
+        const bool lev = si >= 0 && C.simple[si].cls == SC_LEV;
         const ColSet one_k{1, {k, 0, 0, 0}};
         if (lev) {
             // (a lane-refill form of this pass over 128-bit planes lost 0.5 ms per cfg5 γ pass and was removed in
             // round 6)
             constexpr int SLOWLEV_WG_PER_CU = 8;  // the 128-bit scan holds 3 waves per SIMD: 3 workgroups per CU at once
             const int64_t g_sl = std::max<int64_t>(1, std::min<int64_t>(G.g_exact, (int64_t)SLOWLEV_WG_PER_CU * ctx->n_cu));
-            if (G.simple[si].np >= N_PLANES)
-                k_gamma_slow_lev<true><<<(unsigned)g_sl, X_THREADS, 0, ctx->stream>>>(A, si, ctx->xlist.p, ctx->xinfo.p);
+            if (C.simple[si].np >= N_PLANES)
+                k_gamma_slow_lev<true><<<(unsigned)g_sl, X_THREADS, 0, S.stream>>>(A, si, S.xlist.p, S.xinfo.p);
             else
-                k_gamma_slow_lev<false><<<(unsigned)g_sl, X_THREADS, 0, ctx->stream>>>(A, si, ctx->xlist.p, ctx->xinfo.p);
-            k_gamma_rest<<<(unsigned)(4 * ctx->n_cu), 64, 0, ctx->stream>>>(A, k, ctx->xlist.p, ctx->xinfo.p);
+                k_gamma_slow_lev<false><<<(unsigned)g_sl, X_THREADS, 0, S.stream>>>(A, si, S.xlist.p, S.xinfo.p);
+            k_gamma_rest<<<(unsigned)(4 * ctx->n_cu), 64, 0, S.stream>>>(A, k, S.xlist.p, S.xinfo.p);
         } else {
-            k_gamma_slow<<<(unsigned)(4 * ctx->n_cu), 64, 0, ctx->stream>>>(A, one_k, ctx->xlist.p, ctx->xinfo.p);
+            k_gamma_slow<<<(unsigned)(4 * ctx->n_cu), 64, 0, S.stream>>>(A, one_k, S.xlist.p, S.xinfo.p);
         }
     }
     SPK_HIP(hipGetLastError());
@@ -2337,26 +2332,28 @@ static int enqueue_slow(spk_ctx *ctx, GammaPlan &G, int k, const ColSet *jk) {
 }
 
 // skip: leave out the slow-list kernels of columns whose slow lists were empty in the last settled call
-static int enqueue_phase(spk_ctx *ctx, GammaPlan &G, int64_t cap, bool skip = false) {
+static int enqueue_phase(spk_ctx *ctx, Slot &S, int64_t cap, bool skip = false) {
+    const GammaCols &C = *ctx->gcols;
+    GammaPlan &G = *S.gplan;
     GammaArgs &A = G.A;
-    const int K = G.K;
+    const int K = C.K;
     G.slow_skipped.assign((size_t)K, 0);
     auto quiet = [&](int k) {
         return skip && (ctx->slow_force_skip ||
                         (ctx->slow_seen_valid && k < (int)ctx->slow_seen.size() && !ctx->slow_seen[k]));
     };
-    SPK_TRY(ctx->xlist.alloc((size_t)(2 * cap)));
-    A.slow = ctx->xlist.p + cap;
-    A.slow_off = ctx->xinfo.p;
-    ctx->xcap = cap;
+    SPK_TRY(S.xlist.alloc((size_t)(2 * cap)));
+    A.slow = S.xlist.p + cap;
+    A.slow_off = S.xinfo.p;
+    S.xcap = cap;
     if (A.P <= 0) {
-        SPK_HIP(hipMemsetAsync(ctx->xinfo.p, 0, (size_t)G.n_info * 8, ctx->stream));
+        SPK_HIP(hipMemsetAsync(S.xinfo.p, 0, (size_t)C.n_info * 8, S.stream));
         return SPK_OK;
     }
-    k_prefix<<<(unsigned)K, PFX_THREADS, 0, ctx->stream>>>(
-        ctx->region_count.p, K, G.n_regions, cap, ctx->xpref.p, ctx->xinfo.p,
-        reinterpret_cast<unsigned long long *>(ctx->xinfo.p + G.n_info + G.n_cnt + 1));
-    const std::vector<SimpleCol> &simple = G.simple;
+    k_prefix<<<(unsigned)K, PFX_THREADS, 0, S.stream>>>(
+        S.region_count.p, K, G.n_regions, cap, S.xpref.p, S.xinfo.p,
+        reinterpret_cast<unsigned long long *>(S.xinfo.p + C.n_info + C.n_cnt + 1));
+    const std::vector<SimpleCol> &simple = C.simple;
     // Jaro-Winkler template columns: compact every list, then one exact launch over all of them
     // JW exact launches: a JW cell is one short latency-bound evaluation, and the kernel holds 3 waves per
     // SIMD, so a grid of 8 workgroups per CU ran in rounds of dispatch latency; JW_WG_PER_CU per column
@@ -2367,24 +2364,24 @@ static int enqueue_phase(spk_ctx *ctx, GammaPlan &G, int64_t cap, bool skip = fa
     jw.g = (int)g_jw;
     ColSet jk{};
     for (int k = 0; k < K; ++k) {
-        if (!G.may_exact[k] || G.simple_of[k] < 0) continue;
-        const SimpleCol &sc = simple[G.simple_of[k]];
+        if (!C.may_exact[k] || C.simple_of[k] < 0) continue;
+        const SimpleCol &sc = simple[C.simple_of[k]];
         if (sc.cls != SC_JW || sc.kind != SK_STR || jw.n == 4) continue;
         jk.k[jk.n++] = k;
         jw.k[jw.n] = sc.k;
         jw.col[jw.n] = sc.col;
-        jw.si[jw.n++] = G.simple_of[k];
+        jw.si[jw.n++] = C.simple_of[k];
     }
     // One compaction launch for the JW lists and the other plain-compacted lists (up to four columns): the
     // launch is one workgroup per region and column, and a short list's workgroups cost dispatch rounds alone
     // (cfg2: the JW lists' launch took as long as the email list's, 15 us each)
     ColSet pre = jk;
     for (int k = 0; k < K && pre.n < 4; ++k) {
-        if (!G.may_exact[k]) continue;
-        const int si = G.simple_of[k];
+        if (!C.may_exact[k]) continue;
+        const int si = C.simple_of[k];
         bool in_jw = false;
         for (int c = 0; c < jw.n; ++c) in_jw = in_jw || jw.si[c] == si;
-        if (in_jw || (si >= 0 && simple[si].cls == SC_LEV && G.bag[k])) continue;
+        if (in_jw || (si >= 0 && simple[si].cls == SC_LEV && C.bag[k])) continue;
         pre.k[pre.n++] = k;
     }
     auto precompacted = [&](int k) {
@@ -2393,53 +2390,53 @@ static int enqueue_phase(spk_ctx *ctx, GammaPlan &G, int64_t cap, bool skip = fa
         return false;
     };
     if (pre.n)
-        k_compact<<<dim3((unsigned)G.n_regions, (unsigned)pre.n), 256, 0, ctx->stream>>>(A, pre, ctx->xpref.p,
-                                                                                        ctx->xlist.p, ctx->xinfo.p);
+        k_compact<<<dim3((unsigned)G.n_regions, (unsigned)pre.n), 256, 0, S.stream>>>(A, pre, S.xpref.p,
+                                                                                        S.xlist.p, S.xinfo.p);
     // (running this launch on a second stream beside the Levenshtein pass measured no faster:
     // 1.198-1.205 ms per cfg2 pass either way)
     for (int c = 0; c < K; ++c)
-        if (c < (int)ctx->xev_used.size()) ctx->xev_used[c] = 0;
+        if (c < (int)S.xev_used.size()) S.xev_used[c] = 0;
     if (jw.n) {
-        SPK_TRY(ctx->xbegin(jk.k[0]));
-        k_gamma_exact_simple<X_JW><<<(unsigned)(g_jw * jw.n), X_THREADS, 0, ctx->stream>>>(A, jw, ctx->xlist.p,
-                                                                                                ctx->xinfo.p);
-        SPK_TRY(ctx->xend(jk.k[0]));
+        SPK_TRY(ctx->xbegin(S, jk.k[0]));
+        k_gamma_exact_simple<X_JW><<<(unsigned)(g_jw * jw.n), X_THREADS, 0, S.stream>>>(A, jw, S.xlist.p,
+                                                                                                S.xinfo.p);
+        SPK_TRY(ctx->xend(S, jk.k[0]));
         bool all_quiet = true;
         for (int c = 0; c < jk.n; ++c) all_quiet = all_quiet && quiet(jk.k[c]);
         if (all_quiet) {
             for (int c = 0; c < jk.n; ++c) G.slow_skipped[jk.k[c]] = 1;
         } else {
-            SPK_TRY(enqueue_slow(ctx, G, -1, &jk));
+            SPK_TRY(enqueue_slow(ctx, S, -1, &jk));
         }
     }
     for (int k = 0; k < K; ++k) {
-        if (!G.may_exact[k]) continue;
-        const int si = G.simple_of[k];
+        if (!C.may_exact[k]) continue;
+        const int si = C.simple_of[k];
         const bool lev = si >= 0 && simple[si].cls == SC_LEV;
         bool fused = false;
         for (int c = 0; c < jw.n; ++c) fused = fused || jw.si[c] == si;
         if (fused) continue;
         const ColSet one_k{1, {k, 0, 0, 0}};
-        const bool refill = lev && (ctx->lev_kernel == 1 || (ctx->lev_kernel == 2 && G.free_text[k]));
-        if (lev && G.bag[k])
-            k_compact_lev<<<(unsigned)G.n_regions, CL_THREADS, 0, ctx->stream>>>(A, k, si, ctx->xpref.p, ctx->xlist.p,
-                                                                                ctx->xinfo.p);
+        const bool refill = lev && (ctx->lev_kernel == 1 || (ctx->lev_kernel == 2 && C.free_text[k]));
+        if (lev && C.bag[k])
+            k_compact_lev<<<(unsigned)G.n_regions, CL_THREADS, 0, S.stream>>>(A, k, si, S.xpref.p, S.xlist.p,
+                                                                                S.xinfo.p);
         else if (!precompacted(k))
-            k_compact<<<(unsigned)G.n_regions, 256, 0, ctx->stream>>>(A, one_k, ctx->xpref.p, ctx->xlist.p, ctx->xinfo.p);
+            k_compact<<<(unsigned)G.n_regions, 256, 0, S.stream>>>(A, one_k, S.xpref.p, S.xlist.p, S.xinfo.p);
         if (refill) {
             // one resident round (LEVQ_WAVES per SIMD, 3 for NP = 8): every wave owns a contiguous range of the list
             const int64_t wg_cu = simple[si].np >= 8 ? 3 : LEVQ_WG_PER_CU;
             const int64_t g_lev = std::max<int64_t>(1, std::min<int64_t>(G.g_exact, wg_cu * ctx->n_cu));
-            SPK_TRY(ctx->xbegin(k));
+            SPK_TRY(ctx->xbegin(S, k));
             switch (simple[si].np) {
-                case 5: k_lev_refill<5, 1><<<(unsigned)g_lev, X_THREADS, 0, ctx->stream>>>(A, si, ctx->xlist.p, ctx->xinfo.p); break;
-                case 6: k_lev_refill<6, 1><<<(unsigned)g_lev, X_THREADS, 0, ctx->stream>>>(A, si, ctx->xlist.p, ctx->xinfo.p); break;
-                case 7: k_lev_refill<7, 1><<<(unsigned)g_lev, X_THREADS, 0, ctx->stream>>>(A, si, ctx->xlist.p, ctx->xinfo.p); break;
-                default: k_lev_refill<8, 1><<<(unsigned)g_lev, X_THREADS, 0, ctx->stream>>>(A, si, ctx->xlist.p, ctx->xinfo.p); break;
+                case 5: k_lev_refill<5, 1><<<(unsigned)g_lev, X_THREADS, 0, S.stream>>>(A, si, S.xlist.p, S.xinfo.p); break;
+                case 6: k_lev_refill<6, 1><<<(unsigned)g_lev, X_THREADS, 0, S.stream>>>(A, si, S.xlist.p, S.xinfo.p); break;
+                case 7: k_lev_refill<7, 1><<<(unsigned)g_lev, X_THREADS, 0, S.stream>>>(A, si, S.xlist.p, S.xinfo.p); break;
+                default: k_lev_refill<8, 1><<<(unsigned)g_lev, X_THREADS, 0, S.stream>>>(A, si, S.xlist.p, S.xinfo.p); break;
             }
-            SPK_TRY(ctx->xend(k));
+            SPK_TRY(ctx->xend(S, k));
             if (quiet(k)) G.slow_skipped[k] = 1;
-            else SPK_TRY(enqueue_slow(ctx, G, k, nullptr));
+            else SPK_TRY(enqueue_slow(ctx, S, k, nullptr));
         } else if (lev) {
             ExactCols one{};
             one.n = 1;
@@ -2451,12 +2448,12 @@ static int enqueue_phase(spk_ctx *ctx, GammaPlan &G, int64_t cap, bool skip = fa
             one.si[0] = si;
             one.k[0] = simple[si].k;
             one.col[0] = simple[si].col;
-            SPK_TRY(ctx->xbegin(k));
-            k_gamma_exact_simple<X_LEV><<<(unsigned)g_lev, X_THREADS, 0, ctx->stream>>>(A, one, ctx->xlist.p,
-                                                                                      ctx->xinfo.p);
-            SPK_TRY(ctx->xend(k));
+            SPK_TRY(ctx->xbegin(S, k));
+            k_gamma_exact_simple<X_LEV><<<(unsigned)g_lev, X_THREADS, 0, S.stream>>>(A, one, S.xlist.p,
+                                                                                      S.xinfo.p);
+            SPK_TRY(ctx->xend(S, k));
             if (quiet(k)) G.slow_skipped[k] = 1;
-            else SPK_TRY(enqueue_slow(ctx, G, k, nullptr));
+            else SPK_TRY(enqueue_slow(ctx, S, k, nullptr));
         } else if (si >= 0 && simple[si].kind == SK_STR) {
             ExactCols one{};
             one.n = 1;
@@ -2464,21 +2461,28 @@ static int enqueue_phase(spk_ctx *ctx, GammaPlan &G, int64_t cap, bool skip = fa
             one.si[0] = si;
             one.k[0] = simple[si].k;
             one.col[0] = simple[si].col;
-            k_gamma_exact_simple<X_GENERIC><<<(unsigned)G.g_exact, X_THREADS, 0, ctx->stream>>>(A, one, ctx->xlist.p,
-                                                                                           ctx->xinfo.p);
+            k_gamma_exact_simple<X_GENERIC><<<(unsigned)G.g_exact, X_THREADS, 0, S.stream>>>(A, one, S.xlist.p,
+                                                                                           S.xinfo.p);
             if (quiet(k)) G.slow_skipped[k] = 1;
-            else SPK_TRY(enqueue_slow(ctx, G, k, nullptr));
+            else SPK_TRY(enqueue_slow(ctx, S, k, nullptr));
         } else {
-            k_gamma_exact<<<(unsigned)G.g_exact, X_THREADS, 0, ctx->stream>>>(A, k, ctx->xlist.p, ctx->xinfo.p);
-            k_gamma_slow<<<(unsigned)(4 * ctx->n_cu), 64, 0, ctx->stream>>>(A, one_k, ctx->xlist.p, ctx->xinfo.p);
+            k_gamma_exact<<<(unsigned)G.g_exact, X_THREADS, 0, S.stream>>>(A, k, S.xlist.p, S.xinfo.p);
+            k_gamma_slow<<<(unsigned)(4 * ctx->n_cu), 64, 0, S.stream>>>(A, one_k, S.xlist.p, S.xinfo.p);
         }
     }
     SPK_HIP(hipGetLastError());
     return SPK_OK;
 }
 
+// A window's info block to the host, behind what `stream` holds so far.
+static int read_info(spk_ctx *ctx, Slot &S, hipStream_t stream) {
+    SPK_HIP(hipMemcpyAsync(S.h_info, S.xinfo.p, (size_t)ctx->gcols->n_all * 8, hipMemcpyDeviceToHost, stream));
+    SPK_HIP(hipEventRecord(S.ev_info, stream));
+    return SPK_OK;
+}
+
 namespace spk {
-// Completes the last spk_gammas once its info block is on the host: a work-list overflow re-runs the
+// Completes the last spk_gammas once its info blocks are on the host: a work-list overflow re-runs the
 // exact phase with room for every listed cell, and cells with a string past SLOW_LIMIT units go through
 // the huge pass.  *fixed = true when codes changed after the call returned (a consumer that already
 // read them must read them again).  Called at the consumers' own synchronisation points.
@@ -2486,6 +2490,7 @@ static int settle_info(spk_ctx *ctx, bool *fixed);
 
 int settle_gammas(spk_ctx *ctx, bool *fixed) {
     bool f = false;
+    ctx->slot[0].stream = ctx->stream;  // a settlement's launches go where the context's work goes now
     SPK_TRY(settle_info(ctx, &f));
     if (fixed) *fixed = f;
     if (f) ++ctx->codes_fix_seq;  // a selection taken from the uncorrected codes is stale (spk_select_copy)
@@ -2497,204 +2502,243 @@ int settle_gammas(spk_ctx *ctx, bool *fixed) {
     return SPK_OK;
 }
 
-static int settle_slot(spk_ctx *ctx, bool *fixed);
-// Both windows of a two-stream split: the own slot, then the alternate one (its counts added to the first's
-// through the window carry, its slow-list flags or-ed in).
+static int settle_slot(spk_ctx *ctx, Slot &S, bool *fixed);
+// Every slot the last call used, then the call's figures: the windows' counts added to those of the windows
+// settled before (exact_carry), their slow-list flags or-ed.
 static int settle_info(spk_ctx *ctx, bool *fixed) {
     if (fixed) *fixed = false;
-    const bool two = ctx->gamma_pending && ctx->alt.gamma_pending;
-    bool f0 = false, f1 = false;
-    SPK_TRY(settle_slot(ctx, &f0));
-    if (two) {
-        ctx->exact_carry = ctx->last_exact;
-        ctx->deferred_carry = ctx->last_deferred;
-        ctx->split_first = ctx->last_exact;
-        const std::vector<int64_t> xbase0 = ctx->last_xbase;
-        const std::vector<uint8_t> seen = ctx->slow_seen;
-        ctx->swap_slot();
-        const int rc = settle_slot(ctx, &f1);
-        ctx->swap_slot();
-        ctx->alt_xbase = ctx->last_xbase;
-        ctx->last_xbase = xbase0;
-        ctx->exact_carry.clear();
-        ctx->deferred_carry = 0;
-        SPK_TRY(rc);
-        for (size_t k = 0; k < seen.size() && k < ctx->slow_seen.size(); ++k) ctx->slow_seen[k] |= seen[k];
-    } else if (ctx->alt.gamma_pending) {
-        ctx->alt.gamma_pending = false;  // its call's codes were replaced before the own slot was settled
+    bool pending = false, f = false;
+    for (int i = 0; i < ctx->last_slots; ++i) pending = pending || ctx->slot[i].gamma_pending;
+    if (!pending) return SPK_OK;
+    for (int i = 0; i < ctx->last_slots; ++i) SPK_TRY(settle_slot(ctx, ctx->slot[i], &f));
+    if (fixed) *fixed = f;
+    if (!ctx->codes_valid || !ctx->gcols) return SPK_OK;  // the codes were replaced or invalidated since
+    const int K = ctx->gcols->K;
+    const bool carry = (int)ctx->exact_carry.size() == K;  // earlier windows of the same call
+    ctx->last_exact.assign((size_t)K, 0);
+    if (carry) ctx->last_exact = ctx->exact_carry;
+    ctx->last_deferred = ctx->deferred_carry;
+    ctx->slow_seen.assign((size_t)K, 0);
+    for (int i = 0; i < ctx->last_slots; ++i) {
+        const GammaPlan &G = *ctx->slot[i].gplan;
+        for (int k = 0; k < K; ++k) {
+            ctx->last_exact[k] += G.exact[k];
+            ctx->slow_seen[k] |= G.slow_seen[k];
+        }
+        ctx->last_deferred += G.deferred;
     }
-    if (fixed) *fixed = f0 || f1;
+    ctx->slow_seen_valid = true;
     return SPK_OK;
 }
 
-static int settle_slot(spk_ctx *ctx, bool *fixed) {
-    if (fixed) *fixed = false;
-    if (!ctx->gamma_pending) return SPK_OK;
+// One window: *fixed is set when its codes changed (and left alone otherwise).
+static int settle_slot(spk_ctx *ctx, Slot &S, bool *fixed) {
+    if (!S.gamma_pending) return SPK_OK;
     // the info block is on the host once the readback behind it completed (later work -- an EM
     // iteration enqueued meanwhile -- keeps running)
-    SPK_HIP(hipEventSynchronize(ctx->ev_info));
-    ctx->gamma_pending = false;
-    if (!ctx->codes_valid || !ctx->gplan) return SPK_OK;  // the codes were replaced or invalidated since
-    GammaPlan &G = *ctx->gplan;
-    const int K = G.K;
-    if (ctx->h_info[2 * K]) {
+    SPK_HIP(hipEventSynchronize(S.ev_info));
+    S.gamma_pending = false;
+    if (!ctx->codes_valid || !ctx->gcols || !S.gplan) return SPK_OK;  // the codes were replaced or invalidated since
+    const GammaCols &C = *ctx->gcols;
+    GammaPlan &G = *S.gplan;
+    const int K = C.K;
+    if (S.h_info[2 * K]) {
         // the exact lists did not fit: nothing of the phase ran; grow them and run the phase again
-        const int64_t cap = ctx->h_info[2 * K + 1];
-        SPK_HIP(hipMemsetAsync(ctx->xinfo.p + G.n_info, 0, (size_t)(G.n_cnt + 2) * 8, ctx->stream));
-        SPK_TRY(enqueue_phase(ctx, G, cap));
-        SPK_HIP(hipMemcpyAsync(ctx->h_info, ctx->xinfo.p, (size_t)G.n_all * 8, hipMemcpyDeviceToHost, ctx->stream));
-        SPK_HIP(hipStreamSynchronize(ctx->stream));
-        if (fixed) *fixed = true;
-        if (ctx->h_info[2 * K]) {
+        const int64_t cap = S.h_info[2 * K + 1];
+        SPK_HIP(hipMemsetAsync(S.xinfo.p + C.n_info, 0, (size_t)(C.n_cnt + 2) * 8, S.stream));
+        SPK_TRY(enqueue_phase(ctx, S, cap));
+        SPK_TRY(read_info(ctx, S, S.stream));
+        SPK_HIP(hipStreamSynchronize(S.stream));
+        *fixed = true;
+        if (S.h_info[2 * K]) {
             ctx->codes_valid = false;
             SPK_REQUIRE(false, SPK_E_STATE, "spk_gammas: exact work list sizing failed");
         }
     }
-    const unsigned int *h_slow = reinterpret_cast<const unsigned int *>(ctx->h_info + G.n_info);
+    const unsigned int *h_slow = reinterpret_cast<const unsigned int *>(S.h_info + C.n_info);
     {  // slow-list kernels this call left out although the exact pass did list cells: run them now
         bool ran = false;
         ColSet jk{};
         for (int k = 0; k < K; ++k) {
             if (k >= (int)G.slow_skipped.size() || !G.slow_skipped[k] || !h_slow[k]) continue;
-            const int si = G.simple_of[k];
-            const bool lev = si >= 0 && G.simple[si].cls == SC_LEV;
+            const int si = C.simple_of[k];
+            const bool lev = si >= 0 && C.simple[si].cls == SC_LEV;
             if (!lev && jk.n < 4) jk.k[jk.n++] = k;
-            else SPK_TRY(enqueue_slow(ctx, G, k, nullptr));
+            else SPK_TRY(enqueue_slow(ctx, S, k, nullptr));
             ran = true;
         }
-        if (jk.n) SPK_TRY(enqueue_slow(ctx, G, -1, &jk));
+        if (jk.n) SPK_TRY(enqueue_slow(ctx, S, -1, &jk));
         if (ran) {
-            SPK_HIP(hipMemcpyAsync(ctx->h_info, ctx->xinfo.p, (size_t)G.n_all * 8, hipMemcpyDeviceToHost, ctx->stream));
-            SPK_HIP(hipStreamSynchronize(ctx->stream));
-            if (fixed) *fixed = true;
+            SPK_TRY(read_info(ctx, S, S.stream));
+            SPK_HIP(hipStreamSynchronize(S.stream));
+            *fixed = true;
         }
         G.slow_skipped.assign((size_t)K, 0);
     }
-    ctx->slow_seen.assign((size_t)K, 0);
-    for (int k = 0; k < K; ++k) ctx->slow_seen[k] = h_slow[k] ? 1 : 0;
-    ctx->slow_seen_valid = true;
     int err = 0;
-    std::memcpy(&err, ctx->h_info + G.n_info + G.n_cnt, sizeof(err));
+    std::memcpy(&err, S.h_info + C.n_info + C.n_cnt, sizeof(err));
     if (err & 2) {
         ctx->codes_valid = false;
         SPK_REQUIRE(false, SPK_E_INVALID, "spk_gammas: unknown instruction");
     }
-    int64_t n_slow = 0, n_huge = 0, max_huge = 0;
-    ctx->last_exact.assign((size_t)K, 0);
-    const bool carry = (int)ctx->exact_carry.size() == K;  // earlier windows of the same call
+    int64_t n_huge = 0, max_huge = 0;
+    G.deferred = 0;
     for (int k = 0; k < K; ++k) {
-        ctx->last_exact[k] = ctx->h_info[K + k] + (carry ? ctx->exact_carry[k] : 0);
-        n_slow += h_slow[k];
+        G.exact[k] = S.h_info[K + k];
+        G.slow_seen[k] = h_slow[k] ? 1 : 0;
+        G.deferred += h_slow[k];
         n_huge += h_slow[2 * K + k];
         max_huge = std::max<int64_t>(max_huge, h_slow[2 * K + k]);
     }
-    ctx->last_xbase.assign(ctx->h_info, ctx->h_info + K);
-    ctx->last_deferred = n_slow + ctx->deferred_carry;
+    G.xbase.assign(S.h_info, S.h_info + K);
     if (n_huge) {  // cells with a string longer than SLOW_LIMIT units (none in the benchmark configs)
-        Scratch S;
+        Scratch Sc;
         DevBuf<uint8_t> scratch;
-        SPK_TRY(huge_scratch(G.max_units, max_huge, scratch, S));
+        SPK_TRY(huge_scratch(C.max_units, max_huge, scratch, Sc));
         for (int k = 0; k < K; ++k) {
             const int64_t nk = h_slow[2 * K + k];
             if (!nk) continue;
-            const int32_t *items = (G.huge_in_slow[k] ? G.A.slow : ctx->xlist.p) + ctx->h_info[k];  // + xinfo[k]
-            k_gamma_huge<<<(unsigned)(S.n_slots / 64), 64, 0, ctx->stream>>>(G.A, k, items, nk, S);
+            const int32_t *items = (C.huge_in_slow[k] ? G.A.slow : S.xlist.p) + S.h_info[k];  // + xinfo[k]
+            k_gamma_huge<<<(unsigned)(Sc.n_slots / 64), 64, 0, S.stream>>>(G.A, k, items, nk, Sc);
             SPK_HIP(hipGetLastError());
         }
-        SPK_HIP(hipStreamSynchronize(ctx->stream));
-        if (fixed) *fixed = true;
+        SPK_HIP(hipStreamSynchronize(S.stream));
+        *fixed = true;
     }
     return SPK_OK;
 }
 }  // namespace spk
 
-extern "C" int spk_gammas(spk_ctx *ctx, int n_cols, const spk_column_program *cols, int n_when,
-                          const int32_t *when_first_instr, const int32_t *when_n_instr, const int32_t *when_level,
-                          int n_instr, const spk_instr *instr, int n_operands, const spk_operand *operands, int n_lits,
-                          const int64_t *lit_offsets, const uint8_t *lit_utf8) {
-    SPK_REQUIRE(ctx && cols && n_cols >= 1, SPK_E_INVALID, "spk_gammas: bad args");
-    SPK_REQUIRE(ctx->pairs_valid, SPK_E_STATE, "spk_gammas: no pairs");
-    SPK_REQUIRE(n_operands < 4096 && n_instr >= 0 && n_when >= 0, SPK_E_LIMIT, "spk_gammas: program too large");
-    SPK_HIP(hipSetDevice(ctx->device));
-#ifdef SPK_HOST_TIMING
-    const auto ht0 = std::chrono::steady_clock::now();
-#endif
-    SPK_TRY(settle_gammas(ctx, nullptr));  // the previous call's capacity feedback (its codes are replaced)
-#ifdef SPK_HOST_TIMING
-    const auto ht1 = std::chrono::steady_clock::now();
-#endif
-    // ---- host-side validation of the program against the loaded tables
-    Table &t0 = ctx->table[0];
-    Table &t1 = ctx->side_table(1);
-    for (int i = 0; i < n_operands; ++i) {
-        const spk_operand &o = operands[i];
+// ---- spk_gammas, stage by stage ------------------------------------------------------------------------------
+// The arguments of spk_gammas.
+struct Program {
+    int n_cols;
+    const spk_column_program *cols;
+    int n_when;
+    const int32_t *when_first_instr, *when_n_instr, *when_level;
+    int n_instr;
+    const spk_instr *instr;
+    int n_operands;
+    const spk_operand *operands;
+    int n_lits;
+    const int64_t *lit_offsets;
+    const uint8_t *lit_utf8;
+};
+
+// Stage 1: host-side validation of the program against the loaded tables; nlev = the columns' level counts.
+static int validate_program(const Program &p, const Table &t0, const Table &t1, std::vector<int32_t> *nlev) {
+    for (int i = 0; i < p.n_operands; ++i) {
+        const spk_operand &o = p.operands[i];
         if (o.kind == 0) {
-            Table &t = o.side ? t1 : t0;
+            const Table &t = o.side ? t1 : t0;
             SPK_REQUIRE(o.col >= 0 && o.col < (int)t.cols.size() && t.cols[o.col] && t.cols[o.col]->kind != COL_NONE,
                         SPK_E_INVALID, "spk_gammas: operand references a column that was not loaded");
         }
         if (o.kind == 1 || (o.kind == 0 && o.lit >= 0))
-            SPK_REQUIRE(o.lit < n_lits, SPK_E_INVALID, "spk_gammas: literal index out of range");
+            SPK_REQUIRE(o.lit < p.n_lits, SPK_E_INVALID, "spk_gammas: literal index out of range");
     }
-    std::vector<int32_t> nlev(n_cols);
-    for (int k = 0; k < n_cols; ++k) {
-        nlev[k] = cols[k].n_levels;
-        SPK_REQUIRE(cols[k].first_when >= 0 && cols[k].first_when + cols[k].n_when <= n_when, SPK_E_INVALID,
-                    "spk_gammas: when range");
-        SPK_REQUIRE(cols[k].else_level >= -1 && cols[k].else_level < cols[k].n_levels, SPK_E_INVALID,
+    nlev->resize((size_t)p.n_cols);
+    for (int k = 0; k < p.n_cols; ++k) {
+        const spk_column_program &c = p.cols[k];
+        (*nlev)[k] = c.n_levels;
+        SPK_REQUIRE(c.first_when >= 0 && c.first_when + c.n_when <= p.n_when, SPK_E_INVALID, "spk_gammas: when range");
+        SPK_REQUIRE(c.else_level >= -1 && c.else_level < c.n_levels, SPK_E_INVALID,
                     "spk_gammas: else level out of range");
-        for (int w = cols[k].first_when; w < cols[k].first_when + cols[k].n_when; ++w) {
-            SPK_REQUIRE(when_level[w] >= -1 && when_level[w] < cols[k].n_levels, SPK_E_INVALID,
+        for (int w = c.first_when; w < c.first_when + c.n_when; ++w) {
+            SPK_REQUIRE(p.when_level[w] >= -1 && p.when_level[w] < c.n_levels, SPK_E_INVALID,
                         "spk_gammas: THEN level out of range");
-            SPK_REQUIRE(when_first_instr[w] >= 0 && when_n_instr[w] >= 1 && when_n_instr[w] <= 16 &&
-                            when_first_instr[w] + when_n_instr[w] <= n_instr,
+            SPK_REQUIRE(p.when_first_instr[w] >= 0 && p.when_n_instr[w] >= 1 && p.when_n_instr[w] <= 16 &&
+                            p.when_first_instr[w] + p.when_n_instr[w] <= p.n_instr,
                         SPK_E_INVALID, "spk_gammas: predicate range (max 16 RPN instructions)");
         }
     }
-    for (int i = 0; i < n_instr; ++i) {
-        const spk_instr &in = instr[i];
+    for (int i = 0; i < p.n_instr; ++i) {
+        const spk_instr &in = p.instr[i];
         bool logical = in.op == SPK_OP_AND || in.op == SPK_OP_OR || in.op == SPK_OP_NOT || in.op == SPK_OP_CONST;
         if (!logical) {
-            SPK_REQUIRE(in.a >= 0 && in.a < n_operands, SPK_E_INVALID, "spk_gammas: operand index");
+            SPK_REQUIRE(in.a >= 0 && in.a < p.n_operands, SPK_E_INVALID, "spk_gammas: operand index");
             bool two = !(in.op == SPK_OP_ISNULL || in.op == SPK_OP_NOTNULL || in.op == SPK_OP_LEN);
-            if (two) SPK_REQUIRE(in.b >= 0 && in.b < n_operands, SPK_E_INVALID, "spk_gammas: operand index");
+            if (two) SPK_REQUIRE(in.b >= 0 && in.b < p.n_operands, SPK_E_INVALID, "spk_gammas: operand index");
         }
         if (in.op == SPK_OP_CONST) SPK_REQUIRE(in.i0 >= 0 && in.i0 <= 2, SPK_E_INVALID, "spk_gammas: constant");
     }
-    ctx->codes_valid = false;  // codes are rewritten in place below
-    SPK_TRY(set_pattern_space(ctx, n_cols, nlev.data()));
+    return SPK_OK;
+}
 
-    // ---- literals -> UTF-16
-    std::vector<uint16_t> lu;
-    std::vector<int64_t> loff;
-    std::vector<int32_t> llen, lcp;
-    for (int i = 0; i < n_lits; ++i) {
+// Stage 2: the literals as UTF-16, one buffer, with an empty literal at the end.
+struct Literals {
+    std::vector<uint16_t> units;
+    std::vector<int64_t> off;
+    std::vector<int32_t> len, cplen;
+};
+static Literals literals_utf16(const Program &p) {
+    Literals l;
+    for (int i = 0; i < p.n_lits; ++i) {
         int32_t ncp = 0;
-        auto u = utf8_to_utf16(lit_utf8 + lit_offsets[i], lit_offsets[i + 1] - lit_offsets[i], &ncp);
-        loff.push_back((int64_t)lu.size());
-        llen.push_back((int32_t)u.size());
-        lcp.push_back(ncp);
-        lu.insert(lu.end(), u.begin(), u.end());
+        auto u = utf8_to_utf16(p.lit_utf8 + p.lit_offsets[i], p.lit_offsets[i + 1] - p.lit_offsets[i], &ncp);
+        l.off.push_back((int64_t)l.units.size());
+        l.len.push_back((int32_t)u.size());
+        l.cplen.push_back(ncp);
+        l.units.insert(l.units.end(), u.begin(), u.end());
     }
-    lu.resize(lu.size() + 8, 0);  // 4-unit vector reads past a literal's end stay in the buffer
-    loff.push_back((int64_t)lu.size());
-    llen.push_back(0);
-    lcp.push_back(0);
+    l.units.resize(l.units.size() + 8, 0);  // 4-unit vector reads past a literal's end stay in the buffer
+    l.off.push_back((int64_t)l.units.size());
+    l.len.push_back(0);
+    l.cplen.push_back(0);
+    return l;
+}
 
+// Stage 3: which columns the template filter takes (`C.simple`, laid out in the row image) and which the
+// interpreter (`complex_k`), with everything the passes decide per column.
+struct ColumnPlan {
+    GammaCols C;
+    std::vector<int32_t> complex_k;
+    std::vector<int16_t> thr_tab;  // threshold tables of the Levenshtein-ratio tests (SimpleCol.thr_off)
+    int64_t img_stride = 0;
+    bool long_exact = false;       // a free-text Levenshtein column: its exact and slow passes dominate the pass
+};
+
+// Sketch rows of the template Levenshtein columns' strings that `wanted` names, built on first use.
+template <class Wanted, class Build>
+static int build_sketch_rows(spk_ctx *ctx, Table &t0, Table &t1, std::vector<SimpleCol> &simple, Wanted wanted,
+                             DevBuf<uint4> Column::*rows, Build build) {
+    bool built[2] = {false, false};
+    for (SimpleCol &sc : simple) {
+        if (!wanted(sc)) continue;
+        for (int s = 0; s < 2; ++s) {
+            Table &t = s ? t1 : t0;
+            Column *c = t.cols[sc.col];
+            if (c->kind != COL_STR || (c->*rows).n || t.n <= 0) continue;
+            SPK_TRY(build(ctx, t.n, c));
+            t.desc_dirty = true;
+            built[s] = true;
+        }
+    }
+    if (built[0]) SPK_TRY(ensure_desc(ctx, t0));
+    if (built[1]) SPK_TRY(ensure_desc(ctx, t1));
+    return SPK_OK;
+}
+
+static int plan_columns(spk_ctx *ctx, const Program &p, const Literals &lits, Table &t0, Table &t1, ColumnPlan *out) {
     SPK_TRY(ensure_desc(ctx, t0));
     SPK_TRY(ensure_desc(ctx, t1));
-    const int K = n_cols;
-    std::vector<SimpleCol> simple;
-    std::vector<int32_t> complex_k;
+    const int K = p.n_cols;
+    GammaCols &C = out->C;
+    std::vector<SimpleCol> &simple = C.simple;
+    std::vector<int32_t> &complex_k = out->complex_k;
     for (int k = 0; k < K; ++k) {
         SimpleCol sc;
         if (ctx->filter_mode != 0 &&
-            classify_simple(k, cols[k], when_first_instr, when_n_instr, when_level, instr, operands, t0, t1,
+            classify_simple(k, p.cols[k], p.when_first_instr, p.when_n_instr, p.when_level, p.instr, p.operands, t0, t1,
                             ctx->stride, &sc))
             simple.push_back(sc);
         else
             complex_k.push_back(k);
     }
+    auto free_text = [&](const SimpleCol &sc) {  // rows past 64 UTF-8 bytes on both sides (planes_hi)
+        const Column *a = t0.cols[sc.col], *b = t1.cols[sc.col];
+        return sc.kind == SK_STR && a && b && a->planes_hi.n && b->planes_hi.n;
+    };
     for (SimpleCol &sc : simple) {
         sc.cls = simple_class(sc);
         prepare_tests(sc);
@@ -2707,55 +2751,25 @@ extern "C" int spk_gammas(spk_ctx *ctx, int n_cols, const spk_column_program *co
         sc.has_ids = (t0.cols[sc.col]->has_ids && t1.cols[sc.col]->has_ids) ? 1 : 0;
         implied_equal(ctx, t0, t1, sc);
     }
-    // character-bag rows of the free-text Levenshtein columns' strings (k_compact_lev), built on first use.
+    // character-bag rows of the free-text Levenshtein columns' strings (k_compact_lev).
     // Free-text only: in cfg2's emails the bound decided 15 % of the listed cells (1.23 of 8.10 M), and the
     // compaction's gathers cost more than the scans it saved (γ pass 1.070 -> 1.168 ms; cfg5's addresses
     // 4.88 -> 3.85 ms; profiles/r5_ab_lev_bag.log).
-    if (ctx->lev_bag) {
-        bool built[2] = {false, false};
-        for (const SimpleCol &sc : simple) {
-            if (sc.cls != SC_LEV || sc.kind != SK_STR || !t0.cols[sc.col]->planes_hi.n || !t1.cols[sc.col]->planes_hi.n)
-                continue;
-            for (int s = 0; s < 2; ++s) {
-                Table &t = s ? t1 : t0;
-                Column *c = t.cols[sc.col];
-                if (c->kind != COL_STR || c->bag.n || t.n <= 0) continue;
-                SPK_TRY(build_bag_rows(ctx, t.n, c));
-                t.desc_dirty = true;
-                built[s] = true;
-            }
-        }
-        if (built[0]) SPK_TRY(ensure_desc(ctx, t0));
-        if (built[1]) SPK_TRY(ensure_desc(ctx, t1));
-    }
-    // positional sketch rows of the other template Levenshtein columns' strings (the filter's two-segment bound),
-    // built on first use
-    {
-        bool built[2] = {false, false};
-        for (SimpleCol &sc : simple) {
-            const bool free_text = sc.kind == SK_STR && t0.cols[sc.col]->planes_hi.n && t1.cols[sc.col]->planes_hi.n;
-            sc.pos = (sc.cls == SC_LEV && sc.kind == SK_STR && ctx->lev_bound == 1 && !free_text) ? 1 : 0;
-            if (!sc.pos) continue;
-            for (int s = 0; s < 2; ++s) {
-                Table &t = s ? t1 : t0;
-                Column *c = t.cols[sc.col];
-                if (c->kind != COL_STR || c->pos.n || t.n <= 0) continue;
-                SPK_TRY(build_pos_rows(ctx, t.n, c));
-                t.desc_dirty = true;
-                built[s] = true;
-            }
-        }
-        if (built[0]) SPK_TRY(ensure_desc(ctx, t0));
-        if (built[1]) SPK_TRY(ensure_desc(ctx, t1));
-    }
-    // threshold tables of the Levenshtein-ratio tests (SimpleCol.thr_off)
-    std::vector<int16_t> thr_tab;
+    if (ctx->lev_bag)
+        SPK_TRY(build_sketch_rows(
+            ctx, t0, t1, simple, [&](const SimpleCol &sc) { return sc.cls == SC_LEV && free_text(sc); }, &Column::bag,
+            build_bag_rows));
+    // positional sketch rows of the other template Levenshtein columns' strings (the filter's two-segment bound)
+    for (SimpleCol &sc : simple)
+        sc.pos = (sc.cls == SC_LEV && sc.kind == SK_STR && ctx->lev_bound == 1 && !free_text(sc)) ? 1 : 0;
+    SPK_TRY(build_sketch_rows(
+        ctx, t0, t1, simple, [](const SimpleCol &sc) { return sc.pos != 0; }, &Column::pos, build_pos_rows));
     for (SimpleCol &sc : simple) {
         for (int i = 0; i < MAX_TESTS; ++i) sc.thr_off[i] = -1;
         if (sc.cls != SC_LEV) continue;
         for (int i = 0; i < sc.n_tests; ++i) {
             if (sc.op[i] != SPK_OP_LEVRATIO || (sc.cmp[i] != SPK_CMP_LE && sc.cmp[i] != SPK_CMP_LT)) continue;
-            sc.thr_off[i] = (int32_t)thr_tab.size();
+            sc.thr_off[i] = (int32_t)out->thr_tab.size();
             for (int S = 0; S < THR_S; ++S) {
                 // `v / den cmp t` holds for v <= the entry (monotone in v); S = 0 is NULL (den = 0)
                 int th = -1;
@@ -2763,11 +2777,11 @@ extern "C" int spk_gammas(spk_ctx *ctx, int n_cols, const spk_column_program *co
                 for (int v = 0; v < THR_S && S > 0; ++v)
                     if (host_cmp((double)v / den, sc.t[i], sc.cmp[i])) th = v;
                     else break;
-                thr_tab.push_back((int16_t)th);
+                out->thr_tab.push_back((int16_t)th);
             }
         }
     }
-    const int64_t img_stride = layout_image(simple);
+    out->img_stride = layout_image(simple);
     // simple columns the filter kernel cannot take (no filter class, no room in the image) join the
     // interpreter's columns
     for (size_t i = 0; i < simple.size();) {
@@ -2779,7 +2793,49 @@ extern "C" int spk_gammas(spk_ctx *ctx, int n_cols, const spk_column_program *co
         }
     }
     std::sort(complex_k.begin(), complex_k.end());
-    // Every program array goes up in one packed copy into a buffer the context keeps.
+
+    // the decisions of the exact and slow passes (host decisions only; the lists are sized on the device by k_prefix)
+    C.K = K;
+    C.simple_of.assign(K, -1);
+    for (size_t i = 0; i < simple.size(); ++i) C.simple_of[simple[i].k] = (int)i;
+    C.may_exact.assign(K, 1);  // columns whose filter can leave cells undecided (a dictionary-id equality or
+                               // numeric column never does)
+    for (const SimpleCol &sc : simple)
+        if (sc.kind == SK_NUM || sc.cls == SC_NUM || (sc.cls == SC_EQ && sc.has_ids)) C.may_exact[sc.k] = 0;
+    C.free_text.assign(K, 0);
+    C.bag.assign(K, 0);  // free-text Levenshtein columns with character-bag rows (k_compact_lev)
+    for (const SimpleCol &sc : simple) {
+        const Column *a = t0.cols[sc.col], *b = t1.cols[sc.col];
+        C.free_text[sc.k] = (a && b && a->planes_hi.n && b->planes_hi.n) ? 1 : 0;
+        C.bag[sc.k] = (C.free_text[sc.k] && sc.cls == SC_LEV && a->bag.n && b->bag.n && ctx->lev_bag) ? 1 : 0;
+        out->long_exact = out->long_exact || (sc.cls == SC_LEV && C.free_text[sc.k]);
+    }
+    C.huge_in_slow.assign(K, 0);  // column k's huge list: slow-list region (Levenshtein) or exact-list region
+    for (int k = 0; k < K; ++k)
+        C.huge_in_slow[k] = (C.may_exact[k] && C.simple_of[k] >= 0 && simple[C.simple_of[k]].cls == SC_LEV) ? 1 : 0;
+    // One device info block per window, read back with one copy: xinfo (k_prefix: list bases and counts,
+    // overflow, total), then the slow / rest / huge list lengths (3K uint32) and the error word, both zeroed per
+    // window.
+    C.n_info = 2 * K + 2;
+    C.n_cnt = (3 * K + 1) / 2;          // int64 slots of the 3K uint32 list lengths
+    C.n_all = C.n_info + C.n_cnt + 2;   // + the error word and k_prefix's completion counter
+    // every string a program can meet is a row of a loaded string column (UTF-8 bytes bound its UTF-16
+    // units), a substring of one, or a literal: the huge pass's scratch per lane
+    C.max_units = 1;
+    for (const Table *t : {&t0, &t1})
+        for (const Column *c : t->cols)
+            if (c && c->kind == COL_STR) C.max_units = std::max<int64_t>(C.max_units, c->max_bytes);
+    for (int i = 0; i < p.n_lits; ++i) C.max_units = std::max<int64_t>(C.max_units, lits.len[i]);
+    return SPK_OK;
+}
+
+// Stage 4: every program array goes up in one packed copy into a buffer the context keeps (ctx->last_blob is
+// its host copy).  The device keeps the last blob: an unchanged program (every call of an EM run) is not re-sent.
+struct BlobOffsets {
+    size_t prog, wf, wn, wl, instr, ops, lu, loff, llen, lcp, stride, simple, complex_k, thr;
+};
+static int upload_program(spk_ctx *ctx, const Program &p, const Literals &lits, const ColumnPlan &cp, BlobOffsets *o,
+                          bool *fresh_blob) {
     std::vector<uint8_t> blob;
     auto put = [&](const auto *src, size_t n) -> size_t {
         const size_t off = (blob.size() + 15) & ~(size_t)15;
@@ -2787,321 +2843,331 @@ extern "C" int spk_gammas(spk_ctx *ctx, int n_cols, const spk_column_program *co
         if (n) std::memcpy(blob.data() + off, src, n * sizeof(*src));
         return off;
     };
-    const size_t o_prog = put(cols, (size_t)K), o_wf = put(when_first_instr, (size_t)n_when),
-                 o_wn = put(when_n_instr, (size_t)n_when), o_wl = put(when_level, (size_t)n_when),
-                 o_instr = put(instr, (size_t)n_instr), o_ops = put(operands, (size_t)n_operands),
-                 o_lu = put(lu.data(), lu.size()), o_loff = put(loff.data(), loff.size()),
-                 o_llen = put(llen.data(), llen.size()), o_lcp = put(lcp.data(), lcp.size()),
-                 o_stride = put(ctx->stride.data(), ctx->stride.size()), o_simple = put(simple.data(), simple.size()),
-                 o_complex = put(complex_k.data(), complex_k.size()), o_thr = put(thr_tab.data(), thr_tab.size());
-    // the device keeps the last blob: an unchanged program (every call of an EM run) is not re-sent
-    const bool fresh_blob = ctx->prog_blob.p && ctx->prog_blob.n >= blob.size() && ctx->last_blob == blob;
-    if (!fresh_blob || ctx->slow_key_pairs != ctx->pairs_epoch || ctx->slow_key_tables != ctx->table_epoch)
+    o->prog = put(p.cols, (size_t)p.n_cols);
+    o->wf = put(p.when_first_instr, (size_t)p.n_when);
+    o->wn = put(p.when_n_instr, (size_t)p.n_when);
+    o->wl = put(p.when_level, (size_t)p.n_when);
+    o->instr = put(p.instr, (size_t)p.n_instr);
+    o->ops = put(p.operands, (size_t)p.n_operands);
+    o->lu = put(lits.units.data(), lits.units.size());
+    o->loff = put(lits.off.data(), lits.off.size());
+    o->llen = put(lits.len.data(), lits.len.size());
+    o->lcp = put(lits.cplen.data(), lits.cplen.size());
+    o->stride = put(ctx->stride.data(), ctx->stride.size());
+    o->simple = put(cp.C.simple.data(), cp.C.simple.size());
+    o->complex_k = put(cp.complex_k.data(), cp.complex_k.size());
+    o->thr = put(cp.thr_tab.data(), cp.thr_tab.size());
+    *fresh_blob = ctx->prog_blob.p && ctx->prog_blob.n >= blob.size() && ctx->last_blob == blob;
+    if (!*fresh_blob || ctx->slow_key_pairs != ctx->pairs_epoch || ctx->slow_key_tables != ctx->table_epoch)
         ctx->slow_seen_valid = false;
     ctx->slow_key_pairs = ctx->pairs_epoch;
     ctx->slow_key_tables = ctx->table_epoch;
-    if (!fresh_blob) {
+    if (!*fresh_blob) {
         SPK_TRY(ctx->prog_blob.alloc(blob.size()));
         SPK_HIP(hipMemcpyAsync(ctx->prog_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, ctx->stream));
-        ctx->last_blob = blob;
+        ctx->last_blob = std::move(blob);
     }
-#ifdef SPK_HOST_TIMING
-    const auto ht2 = std::chrono::steady_clock::now();
-#endif
-    uint8_t *base = ctx->prog_blob.p;
-    auto at = [&](auto *&dst, size_t off) { dst = reinterpret_cast<std::remove_reference_t<decltype(dst)>>(base + off); };
-    const int64_t P = ctx->n_pairs;
-    // Ordinal windows: the filter's work lists and the exact / slow passes hold window-relative pair
-    // ordinals as int32 (and the filter walks them in uint32), so a pair set of more than ~2^31 pairs runs
-    // as consecutive windows of equal size.  Every window but the last is settled (list overflow, skipped
-    // slow lists, huge cells) before the next one reuses the lists; the last is left pending as usual.
+    return SPK_OK;
+}
+
+// Stage 5: the windows.  Ordinal windows: the filter's work lists and the exact / slow passes hold
+// window-relative pair ordinals as int32 (and the filter walks them in uint32), so a pair set of more than
+// ~2^31 pairs runs as consecutive windows of equal size.  Every window but the last is settled (list overflow,
+// skipped slow lists, huge cells) before the next one reuses the lists; the last is left pending as usual.
+// The two-stream split (spk_ctx::slot): two windows at once, one per stream.
+struct WindowLayout {
+    int64_t P = 0, W = 0, n_win = 1;  // pairs, pairs per window (window 0 is the largest), windows
+    bool split = false;
+    int64_t max_regions = 0;
+    int n_regions_max = 0;            // regions of window 0
+    // one filter workgroup per region of consecutive pair ordinals (a multiple of the wave size)
+    int regions_of(int64_t pw) const {
+        return (int)std::max<int64_t>(1, std::min<int64_t>(max_regions, (pw + F_THREADS - 1) / F_THREADS));
+    }
+};
+static WindowLayout layout_windows(const spk_ctx *ctx, bool long_exact) {
+    WindowLayout L;
+    const int64_t P = L.P = ctx->n_pairs;
     const int64_t WMAX = ((int64_t)1 << 31) - ((int64_t)1 << 22);
     const int64_t wcap = ctx->gamma_window > 0 ? std::min<int64_t>(ctx->gamma_window, WMAX) : WMAX;
     const int64_t n_win0 = std::max<int64_t>(1, (P + wcap - 1) / wcap);
-    // the two-stream split (spk_ctx::alt): two windows of half the pairs at once, one per stream
-    const bool split = ctx->gamma_streams >= 2 && ctx->gamma_window == 0 && n_win0 == 1 &&
-                       P >= std::max<int64_t>(ctx->split_min, 256);
+    L.split = ctx->gamma_streams >= 2 && ctx->gamma_window == 0 && n_win0 == 1 &&
+              P >= std::max<int64_t>(ctx->split_min, 256);
     // Window 0 (the context stream, which starts first and continues after the join) takes 60 % of the pairs, or half
     // when a free-text Levenshtein column's long exact and slow passes dominate the pass: measured best shares, cfg2
     // 0.966 -> 0.943 ms per step at 60 %, cfg5 best at 50 % (profiles/r6_ab_split_share.log)
-    bool long_exact = false;
-    for (const SimpleCol &sc : simple) {
-        const Column *a = t0.cols[sc.col], *b = t1.cols[sc.col];
-        long_exact = long_exact || (sc.cls == SC_LEV && a && b && a->planes_hi.n && b->planes_hi.n);
-    }
-    const int64_t W = split ? (P * (long_exact ? 500 : 600) / 1000 + 63) / 64 * 64
-                            : (n_win0 == 1 ? P : ((P + n_win0 - 1) / n_win0 + 63) / 64 * 64);  // pairs per window
+    L.W = L.split ? (P * (long_exact ? 500 : 600) / 1000 + 63) / 64 * 64
+                  : (n_win0 == 1 ? P : ((P + n_win0 - 1) / n_win0 + 63) / 64 * 64);
     // rounding W up to a multiple of 64 can leave trailing windows empty (small test windows): count the
     // windows from W itself
-    const int64_t n_win = split ? 2 : (n_win0 == 1 ? 1 : (P + W - 1) / W);
-    if (split && !ctx->split_ready) {
-        SPK_HIP(hipStreamCreateWithFlags(&ctx->alt.stream, hipStreamNonBlocking));
-        SPK_HIP(hipEventCreateWithFlags(&ctx->alt.ev_info, hipEventDisableTiming));
+    L.n_win = L.split ? 2 : (n_win0 == 1 ? 1 : (P + L.W - 1) / L.W);
+    // 20 regions (256-thread workgroups) per CU: four rounds of the 5 resident workgroups a CU holds
+    // at the filter's 96-VGPR cap, so the regions' uneven work evens out (measured best of 1280 ..
+    // 20480 on MI355X: 5120 regions 1.76 ms vs 2048 regions 1.86 ms for the cfg2 pass)
+    L.max_regions = 20 * (int64_t)ctx->n_cu;
+    L.n_regions_max = L.regions_of(L.W);
+    return L;
+}
+
+// Stage 6: the codes, and the buffers of every slot the call uses (slot 1's stream and events on the first split).
+// Work lists only for the columns whose filter can leave cells undecided: one list of W pair indices each.  Every
+// (column, region) count is written by the filter launch that covers the region, so region_count needs no memset.
+static int alloc_slots(spk_ctx *ctx, const WindowLayout &L, const GammaCols &C, int n_slots) {
+    if (L.split && !ctx->split_ready) {
+        SPK_HIP(hipStreamCreateWithFlags(&ctx->slot[1].stream, hipStreamNonBlocking));
+        SPK_HIP(hipEventCreateWithFlags(&ctx->slot[1].ev_info, hipEventDisableTiming));
         SPK_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
         SPK_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
         ctx->split_ready = true;
     }
-    // work lists only for the columns whose filter can leave cells undecided (a dictionary-id equality
-    // or numeric column never does): one slot of W pair indices each
-    std::vector<int32_t> wslot(K, 0);
-    int n_wslots = 0;
-    for (int k = 0; k < K; ++k) {
-        bool may = true;
-        for (const SimpleCol &sc : simple)
-            if (sc.k == k && (sc.kind == SK_NUM || sc.cls == SC_NUM || (sc.cls == SC_EQ && sc.has_ids))) may = false;
-        wslot[k] = may ? n_wslots++ : 0;
+    SPK_TRY(ctx->codes.alloc((size_t)(L.P + 1) * ctx->code_bytes));
+    int n_lists = 0;
+    for (int k = 0; k < C.K; ++k) n_lists += C.may_exact[k] ? 1 : 0;
+    for (int i = 0; i < n_slots; ++i) {
+        Slot &S = ctx->slot[i];
+        SPK_TRY(S.work.alloc((size_t)std::max(n_lists, 1) * (size_t)L.W + 1));
+        SPK_TRY(S.region_count.alloc((size_t)C.K * L.n_regions_max));
+        SPK_TRY(S.xinfo.alloc((size_t)C.n_all));
+        SPK_TRY(S.pinned_info((size_t)C.n_all));
+        SPK_TRY(S.xpref.alloc((size_t)C.K * (L.n_regions_max + 1)));
+        if (!S.gplan) S.gplan = new GammaPlan();
     }
-    SPK_TRY(ctx->codes.alloc((size_t)(P + 1) * ctx->code_bytes));
-    // one filter workgroup per region of consecutive pair ordinals (a multiple of the wave size)
-    // 20 regions (256-thread workgroups) per CU: four rounds of the 5 resident workgroups a CU holds
-    // at the filter's 96-VGPR cap, so the regions' uneven work evens out (measured best of 1280 ..
-    // 20480 on MI355X: 5120 regions 1.76 ms vs 2048 regions 1.86 ms for the cfg2 pass)
-    const int64_t max_regions = 20 * (int64_t)ctx->n_cu;
-    auto regions_of = [&](int64_t pw) {
-        return (int)std::max<int64_t>(1, std::min<int64_t>(max_regions, (pw + F_THREADS - 1) / F_THREADS));
-    };
-    const int n_regions_max = regions_of(W);  // (window 0 is the larger one)
-    // One device info block, read back with one copy: xinfo (k_prefix: list bases and counts, overflow,
-    // total), then the slow / rest / huge list lengths (3K uint32) and the error word, both zeroed per window.
-    const int n_info = 2 * K + 2;
-    const int n_cnt = (3 * K + 1) / 2;  // int64 slots of the 3K uint32 list lengths
-    const int n_all = n_info + n_cnt + 2;  // + the error word and k_prefix's completion counter
-    // the per-window buffers (of the alternate slot too when split): every (column, region) count is written
-    // by the filter launch that covers the region, so region_count needs no memset
-    auto alloc_slot = [&]() -> int {
-        SPK_TRY(ctx->work.alloc((size_t)std::max(n_wslots, 1) * (size_t)W + 1));
-        SPK_TRY(ctx->region_count.alloc((size_t)K * n_regions_max));
-        SPK_TRY(ctx->xinfo.alloc((size_t)n_all));
-        SPK_TRY(ctx->pinned_info((size_t)n_all));
-        SPK_TRY(ctx->xpref.alloc((size_t)K * (n_regions_max + 1)));
-        return SPK_OK;
-    };
-    SPK_TRY(alloc_slot());
-    if (split) {
-        ctx->swap_slot();
-        const int rc = alloc_slot();
-        ctx->swap_slot();
-        SPK_TRY(rc);
-    }
+    return SPK_OK;
+}
 
+// Stage 7: the arguments every window shares (its own in run_window).
+static GammaArgs gamma_args(const spk_ctx *ctx, const Table &t0, const Table &t1, const ColumnPlan &cp,
+                            const BlobOffsets &o) {
     GammaArgs A{};
+    uint8_t *base = ctx->prog_blob.p;
+    auto at = [&](auto *&dst, size_t off) { dst = reinterpret_cast<std::remove_reference_t<decltype(dst)>>(base + off); };
     A.cols0 = t0.d_desc.p;
     A.cols1 = t1.d_desc.p;
     A.pl = ctx->pl.p;
     A.pr = ctx->pr.p;
-    A.P = P;
-    A.K = K;
-    at(A.progs, o_prog);
-    at(A.when_first, o_wf);
-    at(A.when_n, o_wn);
-    at(A.when_level, o_wl);
-    at(A.instr, o_instr);
-    at(A.ops, o_ops);
-    at(A.lit_units, o_lu);
-    at(A.lit_off, o_loff);
-    at(A.lit_len, o_llen);
-    at(A.lit_cplen, o_lcp);
-    at(A.stride, o_stride);
-    at(A.simple, o_simple);
-    at(A.complex_k, o_complex);
-    at(A.thr, o_thr);
-    A.n_thr = (int)thr_tab.size();
+    A.P = ctx->n_pairs;
+    A.K = cp.C.K;
+    at(A.progs, o.prog);
+    at(A.when_first, o.wf);
+    at(A.when_n, o.wn);
+    at(A.when_level, o.wl);
+    at(A.instr, o.instr);
+    at(A.ops, o.ops);
+    at(A.lit_units, o.lu);
+    at(A.lit_off, o.loff);
+    at(A.lit_len, o.llen);
+    at(A.lit_cplen, o.lcp);
+    at(A.stride, o.stride);
+    at(A.simple, o.simple);
+    at(A.complex_k, o.complex_k);
+    at(A.thr, o.thr);
+    A.n_thr = (int)cp.thr_tab.size();
     A.codes = ctx->codes.p;
     A.code16 = ctx->code_bytes == 2;
-    for (int k = 0; k < K; ++k) A.wslot[k] = wslot[k];
-    A.n_simple = (int)simple.size();
-    A.n_complex = (int)complex_k.size();
-    ctx->last_simple = (int)simple.size();
+    for (int k = 0, n = 0; k < cp.C.K; ++k) A.wslot[k] = cp.C.may_exact[k] ? n++ : 0;
+    A.n_simple = (int)cp.C.simple.size();
+    A.n_complex = (int)cp.complex_k.size();
+    return A;
+}
 
-    // ---- the plan of the exact and slow passes (host decisions only; sized on the device by k_prefix).
-    // It is kept in the context: the lists' overflow and the huge pass are settled at the next sync
-    // (settle_gammas), not by a round trip inside this call.
-    if (!ctx->gplan) {
-        ctx->gplan = new GammaPlan();
-        ctx->gplan_free = [](GammaPlan *g) { delete g; };
-    }
-    GammaPlan &G = *ctx->gplan;
-    G.simple = simple;
-    G.simple_of.assign(K, -1);
-    for (size_t i = 0; i < simple.size(); ++i) G.simple_of[simple[i].k] = (int)i;
-    G.may_exact.assign(K, 1);  // columns whose filter can leave cells undecided
-    for (const SimpleCol &sc : simple)
-        if (sc.kind == SK_NUM || sc.cls == SC_NUM || (sc.cls == SC_EQ && sc.has_ids)) G.may_exact[sc.k] = 0;
-    G.free_text.assign(K, 0);  // simple columns with rows past 64 UTF-8 bytes on both sides (planes_hi)
-    G.bag.assign(K, 0);        // free-text Levenshtein columns with character-bag rows (k_compact_lev)
-    for (const SimpleCol &sc : simple) {
-        const Column *a = t0.cols[sc.col], *b = t1.cols[sc.col];
-        G.free_text[sc.k] = (a && b && a->planes_hi.n && b->planes_hi.n) ? 1 : 0;
-        G.bag[sc.k] = (G.free_text[sc.k] && sc.cls == SC_LEV && a->bag.n && b->bag.n && ctx->lev_bag) ? 1 : 0;
-    }
-    G.huge_in_slow.assign(K, 0);  // column k's huge list: slow-list region (Levenshtein) or exact-list region
-    for (int k = 0; k < K; ++k)
-        G.huge_in_slow[k] = (G.may_exact[k] && G.simple_of[k] >= 0 && simple[G.simple_of[k]].cls == SC_LEV) ? 1 : 0;
-    G.K = K;
-    G.n_info = n_info;
-    G.n_cnt = n_cnt;
-    G.n_all = n_all;
-    // every string a program can meet is a row of a loaded string column (UTF-8 bytes bound its UTF-16
-    // units), a substring of one, or a literal: the huge pass's scratch per lane
-    G.max_units = 1;
-    for (const Table *t : {&t0, &t1})
-        for (const Column *c : t->cols)
-            if (c && c->kind == COL_STR) G.max_units = std::max<int64_t>(G.max_units, c->max_bytes);
-    for (int i = 0; i < n_lits; ++i) G.max_units = std::max<int64_t>(G.max_units, llen[i]);
+// What the windows of one call run with.
+struct GammaRun {
+    const GammaArgs &A;
+    const WindowLayout &L;
+    const ViewLaunch *V;  // rule 1's view-ordered images, or null
+};
 
-    ctx->exact_carry.clear();
-    ctx->deferred_carry = 0;
-    ctx->last_windows = n_win;
-    ctx->last_split = split;
-    ctx->split_w = split ? W : 0;
-    SPK_TRY(ctx->begin(K_GAMMA));
-    // row images and rule-view images: kernels only when a table, the column layout or the pairs changed
-    ViewLaunch V{};
-    bool have_view = false;
+// Stage 8: graph replay -- everything the launches' arguments and decisions depend on.
+static std::vector<int64_t> graph_key(const spk_ctx *ctx, const GammaRun &R) {
+    auto ptr = [](const void *q) { return (int64_t)(uintptr_t)q; };
+    const WindowLayout &L = R.L;
+    std::vector<int64_t> key = {
+        L.P, L.n_win, L.split ? 1 : 0, L.W, R.A.K, ctx->code_bytes, (int64_t)ctx->pairs_epoch, (int64_t)ctx->table_epoch,
+        (int64_t)std::hash<std::string>()(std::string(ctx->last_blob.begin(), ctx->last_blob.end())), ctx->lev_kernel,
+        ctx->lev_bag ? 1 : 0, ctx->lev_bound, ctx->filter_mode, ctx->use_views, ctx->slow_force_skip ? 1 : 0,
+        R.V ? 1 : 0, ptr(ctx->codes.p), ptr(ctx->pl.p), ptr(ctx->pr.p), ptr(ctx->pvl.p), ptr(ctx->prog_blob.p),
+        ptr(ctx->img[0].p), ptr(ctx->img[1].p), ctx->slow_seen_valid ? 1 : 0, (int64_t)ctx->timing};
+    for (const Slot &S : ctx->slot)
+        key.insert(key.end(), {ptr(S.stream), ptr(S.work.p), ptr(S.xlist.p), ptr(S.xinfo.p), ptr(S.xpref.p),
+                               ptr(S.region_count.p), S.xcap});
+    for (uint8_t f : ctx->slow_seen) key.push_back(f);
+    for (int v = 0; v < MAX_VIEWS; ++v) key.push_back(ptr(ctx->vimg[v][0].p));
+    return key;
+}
+
+// Stage 9: window w, pairs [w W, min((w + 1) W, P)), enqueued on the slot's stream: filter, exact and slow passes.
+static int run_window(spk_ctx *ctx, const GammaRun &R, Slot &S, int64_t w) {
+    const GammaCols &C = *ctx->gcols;
+    GammaPlan &G = *S.gplan;
+    const int64_t b = w * R.L.W, Pw = std::min<int64_t>(R.L.W, R.L.P - b);
+    const int n_regions = R.L.regions_of(Pw);
+    const int64_t region_len = ((Pw + n_regions - 1) / n_regions + 63) / 64 * 64;
+    GammaArgs &AW = G.A = R.A;  // the window [b, b + Pw) as a pair set of its own
+    AW.err = reinterpret_cast<int *>(S.xinfo.p + C.n_info + C.n_cnt);
+    AW.work = S.work.p;
+    AW.region_count = S.region_count.p;
+    AW.slow_count = reinterpret_cast<unsigned int *>(S.xinfo.p + C.n_info);
+    AW.pl = ctx->pl.p + b;
+    AW.pr = ctx->pr.p + b;
+    AW.P = Pw;
+    AW.codes = ctx->codes.p + b * ctx->code_bytes;
+    AW.region_len = region_len;
+    AW.n_regions = n_regions;
+    std::vector<SimpleCol> sw = C.simple;  // implied ranges relative to the window
+    for (SimpleCol &sc : sw) {
+        sc.imp_lo = std::min<int64_t>(std::max<int64_t>(sc.imp_lo - b, 0), Pw);
+        sc.imp_hi = std::min<int64_t>(std::max<int64_t>(sc.imp_hi - b, 0), Pw);
+        if (sc.imp_hi <= sc.imp_lo) sc.imp_lo = sc.imp_hi = 0;
+    }
+    G.first = b;
+    G.n_regions = n_regions;
+    G.g_exact = std::max<int64_t>(1, std::min<int64_t>(8 * (int64_t)ctx->n_cu, (Pw + X_THREADS - 1) / X_THREADS));
+    G.xbase.assign((size_t)C.K, 0);
+    G.exact.assign((size_t)C.K, 0);
+    G.slow_seen.assign((size_t)C.K, 0);
+    G.deferred = 0;
+    SPK_HIP(hipMemsetAsync(S.xinfo.p + C.n_info, 0, (size_t)(C.n_cnt + 2) * 8, S.stream));
+    int64_t va = n_regions, vb = n_regions;  // regions over rule 1's view-ordered image: [va, vb)
+    if (Pw > 0) {
+        if (R.V) {  // regions [i L, min((i + 1) L, Pw)) inside the window's part of [V.lo, V.hi)
+            const int64_t lo = std::min<int64_t>(std::max<int64_t>(R.V->lo - b, 0), Pw);
+            const int64_t hi = std::min<int64_t>(std::max<int64_t>(R.V->hi - b, 0), Pw);
+            va = std::min<int64_t>(n_regions, (lo + region_len - 1) / region_len);
+            vb = hi >= Pw ? n_regions : std::min<int64_t>(n_regions, hi / region_len);
+            vb = hi > lo ? std::max<int64_t>(va, vb) : va;
+        }
+        ctx->last_view_regions += vb - va;
+        // the filter pass (the interpreter's columns add to the codes the template filter sets)
+        if (sw.empty()) SPK_HIP(hipMemsetAsync(AW.codes, 0, (size_t)Pw * ctx->code_bytes, S.stream));
+        if (!sw.empty()) {
+            SPK_TRY(launch_template_filter(S.stream, AW, sw, 0, va));
+            if (vb > va) {
+                GammaArgs VA = AW;
+                VA.pl = ctx->pvl.p - ctx->pv_base + b;  // pl[p] = view position of pair b + p (>= pv_base)
+                VA.pr = ctx->pvr.p - ctx->pv_base + b;
+                VA.img0 = R.V->img0;
+                VA.img1 = R.V->img1;
+                SPK_TRY(launch_template_filter(S.stream, VA, sw, va, vb));
+            }
+            SPK_TRY(launch_template_filter(S.stream, AW, sw, vb, n_regions));
+        }
+        if (AW.n_complex) {
+            k_gamma_filter<<<(unsigned)n_regions, F_THREADS, 0, S.stream>>>(AW);
+            SPK_HIP(hipGetLastError());
+        }
+    }
+    const int64_t cap = std::max<int64_t>(S.xcap, std::max<int64_t>(Pw, 1 << 16));
+    return enqueue_phase(ctx, S, cap, /*skip=*/true);
+}
+
+// Once slot 1's stream has forked from the context stream, every way out joins it back: without the join a later
+// call could rewrite the codes while window 1's kernels of a failed call still run.
+struct SplitJoin {
+    spk_ctx *ctx;
+    bool recorded = false, waited = false;
+    int record() {  // what slot 1's stream holds so far ...
+        recorded = true;
+        SPK_HIP(hipEventRecord(ctx->ev_join, ctx->slot[1].stream));
+        return SPK_OK;
+    }
+    int wait() {  // ... is what the context stream waits for
+        waited = true;
+        SPK_HIP(hipStreamWaitEvent(ctx->slot[0].stream, ctx->ev_join, 0));
+        return SPK_OK;
+    }
+    ~SplitJoin() {
+        if (!recorded) (void)record();
+        if (!waited) (void)wait();
+    }
+};
+
+// The exact lists of the window just settled in S, behind those of the call's earlier windows (ctx->list_carry):
+// the next window overwrites the slot's lists, and spk_gammas_exact_list reports the whole call's.  Device-to-device
+// copies on the slot's stream, ahead of the next window's launches.
+static int carry_lists(spk_ctx *ctx, Slot &S) {
+    const GammaPlan &G = *S.gplan;
+    int64_t need = ctx->xcarry_used;
+    for (int64_t n : G.exact) need += n;
+    if (need > (int64_t)ctx->xcarry.n) {
+        DevBuf<int32_t> grown;
+        SPK_TRY(grown.alloc((size_t)std::max<int64_t>(need, 2 * (int64_t)ctx->xcarry.n)));
+        if (ctx->xcarry_used) {
+            SPK_HIP(hipMemcpyAsync(grown.p, ctx->xcarry.p, (size_t)ctx->xcarry_used * 4, hipMemcpyDeviceToDevice, S.stream));
+            SPK_HIP(hipStreamSynchronize(S.stream));  // before the old buffer is freed
+        }
+        ctx->xcarry = std::move(grown);
+    }
+    for (int k = 0; k < (int)G.exact.size(); ++k) {
+        if (G.exact[k] <= 0) continue;
+        SPK_HIP(hipMemcpyAsync(ctx->xcarry.p + ctx->xcarry_used, S.xlist.p + G.xbase[k], (size_t)G.exact[k] * 4,
+                               hipMemcpyDeviceToDevice, S.stream));
+        ctx->list_carry.push_back({k, G.first, ctx->xcarry_used, G.exact[k]});
+        ctx->xcarry_used += G.exact[k];
+    }
+    return SPK_OK;
+}
+
+// Stage 10a: the call's windows.  in_graph: under stream capture, which takes no readback (the caller reads the
+// info blocks behind the graph).
+static int run_windows(spk_ctx *ctx, const GammaRun &R, bool in_graph) {
     ctx->last_view_regions = 0;
-    if (P > 0) {
-        SPK_TRY(build_images(ctx, t0, t1, A, img_stride, simple));
-        // regions wholly inside rule 1's pairs read its view-ordered image (view launch); the others, and a
-        // region straddling a rule boundary, the table image (table launches).  Only when the image
-        // outgrows the caches: at 1M rows (80 MB, held by the 256 MB Infinity Cache) the second launch's
-        // tail cost 4 % (1.41 vs 1.34 ms, cfg2); at 20M rows (1.6 GB) the view launch took the pass from
-        // 31.1 to 22.8 ms (profiles/archive/r2_ab_views.log).
-        const bool big = (A.img_rows0 + A.img_rows1) * img_stride > VIEW_MIN_IMAGE_BYTES;
-        if ((ctx->use_views == 1 && big) || ctx->use_views == 2) SPK_TRY(build_view_images(ctx, A, img_stride, &V, &have_view));
-    }
-    // ---- graph replay: everything the launches' arguments and decisions depend on
-    std::vector<int64_t> gkey;
-    {
-        auto ptr = [](const void *q) { return (int64_t)(uintptr_t)q; };
-        gkey = {P, n_win, split ? 1 : 0, W, K, ctx->code_bytes, (int64_t)ctx->pairs_epoch, (int64_t)ctx->table_epoch,
-                (int64_t)std::hash<std::string>()(std::string(blob.begin(), blob.end())), ctx->lev_kernel,
-                ctx->lev_bag ? 1 : 0, ctx->lev_bound, ctx->filter_mode, ctx->use_views, ctx->slow_force_skip ? 1 : 0,
-                have_view ? 1 : 0, ptr(ctx->stream), ptr(ctx->codes.p), ptr(ctx->pl.p), ptr(ctx->pr.p), ptr(ctx->pvl.p),
-                ptr(ctx->prog_blob.p), ptr(ctx->img[0].p), ptr(ctx->img[1].p), ptr(ctx->work.p), ptr(ctx->xlist.p),
-                ptr(ctx->xinfo.p), ptr(ctx->xpref.p), ptr(ctx->region_count.p), ctx->xcap, ptr(ctx->alt.work.p),
-                ptr(ctx->alt.xlist.p), ptr(ctx->alt.xinfo.p), ptr(ctx->alt.xpref.p), ptr(ctx->alt.region_count.p),
-                ctx->alt.xcap, ptr(ctx->alt.stream), ctx->slow_seen_valid ? 1 : 0, (int64_t)ctx->timing};
-        for (uint8_t f : ctx->slow_seen) gkey.push_back(f);
-        for (int v = 0; v < MAX_VIEWS; ++v) gkey.push_back(ptr(ctx->vimg[v][0].p));
-    }
-    const bool graphable = ctx->use_graph && !ctx->timing_exact && P > 0 && fresh_blob && (split || n_win == 1);
-    const bool replay = graphable && ctx->gexec && gkey == ctx->gkey;
-    const bool capture = graphable && !replay && gkey == ctx->gkey_prev;  // the second call with this key
-    ctx->gkey_prev = gkey;
-    if (split && !replay) {  // window 1's plan: the same program, its own window arguments
-        if (!ctx->alt.gplan) ctx->alt.gplan = new GammaPlan();
-        *ctx->alt.gplan = G;
-    }
-    bool via_graph = replay;
-    if (replay) {
-        // the plans as the captured call left them; the slow-list launches it skipped
-        ctx->gplan->slow_skipped = ctx->gskip0;
-        if (split) ctx->alt.gplan->slow_skipped = ctx->gskip1;
-        ctx->last_view_regions = ctx->gview_regions;
-        SPK_HIP(hipGraphLaunch(ctx->gexec, ctx->stream));
-        ++ctx->graph_launches;
-    } else {
-    auto run_windows = [&](bool in_graph) -> int {
-    if (split) {
+    ctx->list_carry.clear();
+    ctx->xcarry_used = 0;
+    if (R.L.split) {
         // window 1's stream starts after everything queued so far (images, program blob, earlier reads of the
         // codes), together with window 0.  Starting it after window 0's filter instead (so that its filter runs
         // beside window 0's exact passes) measured slower: the short JW launch then waited behind the second
         // filter's workgroups (cfg2 0.99 -> 1.02 ms per step, profiles/r6_ab_gamma_streams.log).
-        SPK_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-        SPK_HIP(hipStreamWaitEvent(ctx->alt.stream, ctx->ev_fork, 0));
+        SPK_HIP(hipEventRecord(ctx->ev_fork, ctx->slot[0].stream));
+        SPK_HIP(hipStreamWaitEvent(ctx->slot[1].stream, ctx->ev_fork, 0));
+        SplitJoin fork{ctx};
+        // each window's info block on its own stream (window 0's not behind the join); the join is recorded right
+        // after window 1's last kernel, so the context stream waits for nothing else of it, and waited for after the
+        // readback is enqueued
+        SPK_TRY(run_window(ctx, R, ctx->slot[0], 0));
+        if (!in_graph) SPK_TRY(read_info(ctx, ctx->slot[0], ctx->slot[0].stream));
+        SPK_TRY(run_window(ctx, R, ctx->slot[1], 1));
+        SPK_TRY(fork.record());
+        if (!in_graph) SPK_TRY(read_info(ctx, ctx->slot[1], ctx->slot[1].stream));
+        return fork.wait();
     }
-    for (int64_t w = 0; w < n_win; ++w) {
-        if (split && w == 1) ctx->swap_slot();  // window 1: the alternate buffers, plan and stream
-        GammaPlan &G = *ctx->gplan;
-        const int64_t b = w * W, Pw = std::min<int64_t>(W, P - b);
-        const int n_regions = regions_of(Pw);
-        const int64_t region_len = ((Pw + n_regions - 1) / n_regions + 63) / 64 * 64;
-        GammaArgs AW = A;  // the window [b, b + Pw) as a pair set of its own
-        AW.err = reinterpret_cast<int *>(ctx->xinfo.p + n_info + n_cnt);
-        AW.work = ctx->work.p;
-        AW.region_count = ctx->region_count.p;
-        AW.slow_count = reinterpret_cast<unsigned int *>(ctx->xinfo.p + n_info);
-        AW.pl = ctx->pl.p + b;
-        AW.pr = ctx->pr.p + b;
-        AW.P = Pw;
-        AW.codes = ctx->codes.p + b * ctx->code_bytes;
-        AW.region_len = region_len;
-        AW.n_regions = n_regions;
-        std::vector<SimpleCol> sw = simple;  // implied ranges relative to the window
-        for (SimpleCol &sc : sw) {
-            sc.imp_lo = std::min<int64_t>(std::max<int64_t>(sc.imp_lo - b, 0), Pw);
-            sc.imp_hi = std::min<int64_t>(std::max<int64_t>(sc.imp_hi - b, 0), Pw);
-            if (sc.imp_hi <= sc.imp_lo) sc.imp_lo = sc.imp_hi = 0;
-        }
-        G.n_regions = n_regions;
-        G.g_exact = std::max<int64_t>(1, std::min<int64_t>(8 * (int64_t)ctx->n_cu, (Pw + X_THREADS - 1) / X_THREADS));
-        SPK_HIP(hipMemsetAsync(ctx->xinfo.p + n_info, 0, (size_t)(n_cnt + 2) * 8, ctx->stream));
-        int64_t va = n_regions, vb = n_regions;  // regions over rule 1's view-ordered image: [va, vb)
-        if (Pw > 0) {
-            if (have_view) {  // regions [i L, min((i + 1) L, Pw)) inside the window's part of [V.lo, V.hi)
-                const int64_t lo = std::min<int64_t>(std::max<int64_t>(V.lo - b, 0), Pw);
-                const int64_t hi = std::min<int64_t>(std::max<int64_t>(V.hi - b, 0), Pw);
-                va = std::min<int64_t>(n_regions, (lo + region_len - 1) / region_len);
-                vb = hi >= Pw ? n_regions : std::min<int64_t>(n_regions, hi / region_len);
-                vb = hi > lo ? std::max<int64_t>(va, vb) : va;
-            }
-            ctx->last_view_regions += vb - va;
-            // the filter pass (the interpreter's columns add to the codes the template filter sets)
-            if (sw.empty())
-                SPK_HIP(hipMemsetAsync(AW.codes, 0, (size_t)Pw * ctx->code_bytes, ctx->stream));
-            if (!sw.empty()) {
-                SPK_TRY(launch_template_filter(ctx->stream, AW, sw, 0, va));
-                if (vb > va) {
-                    GammaArgs VA = AW;
-                    VA.pl = ctx->pvl.p - ctx->pv_base + b;  // pl[p] = view position of pair b + p (>= pv_base)
-                    VA.pr = ctx->pvr.p - ctx->pv_base + b;
-                    VA.img0 = V.img0;
-                    VA.img1 = V.img1;
-                    SPK_TRY(launch_template_filter(ctx->stream, VA, sw, va, vb));
-                }
-                SPK_TRY(launch_template_filter(ctx->stream, AW, sw, vb, n_regions));
-            }
-            if (AW.n_complex) {
-                k_gamma_filter<<<(unsigned)n_regions, F_THREADS, 0, ctx->stream>>>(AW);
-                SPK_HIP(hipGetLastError());
-            }
-        }
-        G.A = AW;
-        const int64_t cap = std::max<int64_t>(ctx->xcap, std::max<int64_t>(Pw, 1 << 16));
-        SPK_TRY(enqueue_phase(ctx, G, cap, /*skip=*/true));
-        if (split) {
-            if (w == 0) {  // window 0's info block, on its own stream (not behind the join; a graph reads it after)
-                if (!in_graph) {
-                    SPK_HIP(hipMemcpyAsync(ctx->h_info, ctx->xinfo.p, (size_t)n_all * 8, hipMemcpyDeviceToHost, ctx->stream));
-                    SPK_HIP(hipEventRecord(ctx->ev_info, ctx->stream));
-                }
-                continue;
-            }
-            // window 1: the join right after its last kernel (the context stream waits for nothing else of it), then
-            // its info block, and the own slot back
-            SPK_HIP(hipEventRecord(ctx->ev_join, ctx->stream));
-            if (!in_graph) {
-                SPK_HIP(hipMemcpyAsync(ctx->h_info, ctx->xinfo.p, (size_t)n_all * 8, hipMemcpyDeviceToHost, ctx->stream));
-                SPK_HIP(hipEventRecord(ctx->ev_info, ctx->stream));
-            }
-            ctx->gamma_pending = true;
-            ctx->swap_slot();
-            SPK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-            break;
-        }
-        if (w + 1 == n_win) break;
+    Slot &S = ctx->slot[0];
+    for (int64_t w = 0; w < R.L.n_win; ++w) {
+        SPK_TRY(run_window(ctx, R, S, w));
+        if (w + 1 == R.L.n_win) break;
         // settle this window before the next one reuses the lists
-        SPK_HIP(hipMemcpyAsync(ctx->h_info, ctx->xinfo.p, (size_t)n_all * 8, hipMemcpyDeviceToHost, ctx->stream));
-        SPK_HIP(hipEventRecord(ctx->ev_info, ctx->stream));
-        ctx->gamma_pending = true;
+        SPK_TRY(read_info(ctx, S, S.stream));
+        S.gamma_pending = true;
         ctx->codes_valid = true;
-        SPK_TRY(settle_info(ctx, nullptr));
+        const int rc = settle_info(ctx, nullptr);
+        ctx->codes_valid = false;  // (the call is not through)
+        SPK_TRY(rc);
         ctx->exact_carry = ctx->last_exact;
         ctx->deferred_carry = ctx->last_deferred;
+        SPK_TRY(carry_lists(ctx, S));
     }
+    return SPK_OK;
+}
+
+// Stage 10b: the windows enqueued directly, captured into a graph (the second call with a key) or replayed from it
+// (later calls with that key).  *via_graph: the pass ran as a graph launch.
+static int run_pass(spk_ctx *ctx, const GammaRun &R, bool fresh_blob, bool *via_graph) {
+    *via_graph = false;
+    const int n_slots = R.L.split ? 2 : 1;
+    const std::vector<int64_t> gkey = graph_key(ctx, R);
+    const bool graphable = ctx->use_graph && !ctx->timing_exact && R.L.P > 0 && fresh_blob && (R.L.split || R.L.n_win == 1);
+    const bool replay = graphable && ctx->gexec && gkey == ctx->gkey;
+    bool cap = graphable && !replay && gkey == ctx->gkey_prev;  // the second call with this key
+    ctx->gkey_prev = gkey;
+    *via_graph = replay;
+    if (replay) {
+        // the slots' plans as the captured call left them; the slow-list launches it skipped
+        for (int i = 0; i < n_slots; ++i) ctx->slot[i].gplan->slow_skipped = ctx->gskip[i];
+        ctx->last_view_regions = ctx->gview_regions;
+        SPK_HIP(hipGraphLaunch(ctx->gexec, ctx->stream));
+        ++ctx->graph_launches;
         return SPK_OK;
-    };
-    bool cap = capture;
+    }
     if (cap) {
         if (ctx->gexec) (void)hipGraphExecDestroy(ctx->gexec);
         if (ctx->graph) (void)hipGraphDestroy(ctx->graph);
@@ -3114,7 +3180,7 @@ extern "C" int spk_gammas(spk_ctx *ctx, int n_cols, const spk_column_program *co
             ctx->use_graph = false;
         }
     }
-    int rc = run_windows(cap);
+    int rc = run_windows(ctx, R, cap);
     if (cap) {
         hipGraph_t g = nullptr;
         hipError_t e = hipStreamEndCapture(ctx->stream, &g);
@@ -3122,8 +3188,7 @@ extern "C" int spk_gammas(spk_ctx *ctx, int n_cols, const spk_column_program *co
         if (rc == SPK_OK && e == hipSuccess) {
             ctx->graph = g;
             ctx->gkey = gkey;
-            ctx->gskip0 = ctx->gplan->slow_skipped;
-            if (split) ctx->gskip1 = ctx->alt.gplan->slow_skipped;
+            for (int i = 0; i < n_slots; ++i) ctx->gskip[i] = ctx->slot[i].gplan->slow_skipped;
             ctx->gview_regions = ctx->last_view_regions;
             rc = hipGraphLaunch(ctx->gexec, ctx->stream) == hipSuccess ? SPK_OK : SPK_E_HIP;
         } else {
@@ -3133,30 +3198,88 @@ extern "C" int spk_gammas(spk_ctx *ctx, int n_cols, const spk_column_program *co
             (void)hipGetLastError();
             ctx->use_graph = false;
             cap = false;
-            if (rc == SPK_OK) rc = run_windows(false);
+            if (rc == SPK_OK) rc = run_windows(ctx, R, false);
         }
     }
-    SPK_TRY(rc);
-    via_graph = cap;
-    }  // (not a replay)
+    *via_graph = cap;
+    return rc;
+}
+
+extern "C" int spk_gammas(spk_ctx *ctx, int n_cols, const spk_column_program *cols, int n_when,
+                          const int32_t *when_first_instr, const int32_t *when_n_instr, const int32_t *when_level,
+                          int n_instr, const spk_instr *instr, int n_operands, const spk_operand *operands, int n_lits,
+                          const int64_t *lit_offsets, const uint8_t *lit_utf8) {
+    SPK_REQUIRE(ctx && cols && n_cols >= 1, SPK_E_INVALID, "spk_gammas: bad args");
+    SPK_REQUIRE(ctx->pairs_valid, SPK_E_STATE, "spk_gammas: no pairs");
+    SPK_REQUIRE(n_operands < 4096 && n_instr >= 0 && n_when >= 0, SPK_E_LIMIT, "spk_gammas: program too large");
+    SPK_HIP(hipSetDevice(ctx->device));
+    ctx->slot[0].stream = ctx->stream;  // (spk_ctx_set_stream may have changed it since the last call)
+#ifdef SPK_HOST_TIMING
+    const auto ht0 = std::chrono::steady_clock::now();
+#endif
+    SPK_TRY(settle_gammas(ctx, nullptr));  // the previous call's capacity feedback (its codes are replaced)
+#ifdef SPK_HOST_TIMING
+    const auto ht1 = std::chrono::steady_clock::now();
+#endif
+    const Program prog{n_cols, cols, n_when, when_first_instr, when_n_instr, when_level, n_instr, instr, n_operands,
+                       operands, n_lits, lit_offsets, lit_utf8};
+    Table &t0 = ctx->table[0];
+    Table &t1 = ctx->side_table(1);
+    std::vector<int32_t> nlev;
+    SPK_TRY(validate_program(prog, t0, t1, &nlev));
+    ctx->codes_valid = false;  // codes are rewritten in place below
+    SPK_TRY(set_pattern_space(ctx, n_cols, nlev.data()));
+    const Literals lits = literals_utf16(prog);
+    ColumnPlan cp;
+    SPK_TRY(plan_columns(ctx, prog, lits, t0, t1, &cp));
+    BlobOffsets offs{};
+    bool fresh_blob = false;
+    SPK_TRY(upload_program(ctx, prog, lits, cp, &offs, &fresh_blob));
+#ifdef SPK_HOST_TIMING
+    const auto ht2 = std::chrono::steady_clock::now();
+#endif
+    const WindowLayout L = layout_windows(ctx, cp.long_exact);
+    const int n_slots = L.split ? 2 : 1;
+    SPK_TRY(alloc_slots(ctx, L, cp.C, n_slots));
+    GammaArgs A = gamma_args(ctx, t0, t1, cp, offs);
+    const int64_t img_stride = cp.img_stride;
+    if (!ctx->gcols) ctx->gcols = new GammaCols();
+    *ctx->gcols = std::move(cp.C);  // kept for the settlement (settle_gammas), which may come after this call
+    const GammaCols &C = *ctx->gcols;
+    ctx->last_simple = (int)C.simple.size();
+    ctx->exact_carry.clear();
+    ctx->deferred_carry = 0;
+    ctx->last_windows = L.n_win;
+    ctx->last_slots = n_slots;
+    SPK_TRY(ctx->begin(K_GAMMA));
+    // row images and rule-view images: kernels only when a table, the column layout or the pairs changed
+    ViewLaunch V{};
+    bool have_view = false;
+    if (L.P > 0) {
+        SPK_TRY(build_images(ctx, t0, t1, A, img_stride, C.simple));
+        // regions wholly inside rule 1's pairs read its view-ordered image (view launch); the others, and a
+        // region straddling a rule boundary, the table image (table launches).  Only when the image
+        // outgrows the caches: at 1M rows (80 MB, held by the 256 MB Infinity Cache) the second launch's
+        // tail cost 4 % (1.41 vs 1.34 ms, cfg2); at 20M rows (1.6 GB) the view launch took the pass from
+        // 31.1 to 22.8 ms (profiles/archive/r2_ab_views.log).
+        const bool big = (A.img_rows0 + A.img_rows1) * img_stride > VIEW_MIN_IMAGE_BYTES;
+        if ((ctx->use_views == 1 && big) || ctx->use_views == 2) SPK_TRY(build_view_images(ctx, A, img_stride, &V, &have_view));
+    }
+    const GammaRun R{A, L, have_view ? &V : nullptr};
+    bool via_graph = false;
+    SPK_TRY(run_pass(ctx, R, fresh_blob, &via_graph));
     SPK_TRY(ctx->end(K_GAMMA));
-    if (!split || via_graph) {
-        // the info blocks on the context stream behind the pass (a split call without a graph read window 0's back
-        // in the loop, window 1's on its own stream)
-        SPK_HIP(hipMemcpyAsync(ctx->h_info, ctx->xinfo.p, (size_t)n_all * 8, hipMemcpyDeviceToHost, ctx->stream));
-        SPK_HIP(hipEventRecord(ctx->ev_info, ctx->stream));
-        if (split) {
-            SPK_HIP(hipMemcpyAsync(ctx->alt.h_info, ctx->alt.xinfo.p, (size_t)n_all * 8, hipMemcpyDeviceToHost, ctx->stream));
-            SPK_HIP(hipEventRecord(ctx->alt.ev_info, ctx->stream));
-            ctx->alt.gamma_pending = true;
-        }
+    for (int i = 0; i < n_slots; ++i) {
+        // the info blocks on the context stream behind the pass (a split call without a graph read each window's
+        // back on its own stream)
+        if (!L.split || via_graph) SPK_TRY(read_info(ctx, ctx->slot[i], ctx->stream));
+        ctx->slot[i].gamma_pending = true;
     }
     ++ctx->gamma_seq;
-    ctx->gamma_pending = true;
     ctx->codes_valid = true;
     ctx->mpat_valid = false;
-    ctx->last_implied.assign((size_t)K, 0);
-    for (const SimpleCol &sc : simple) ctx->last_implied[sc.k] = sc.imp_hi - sc.imp_lo;
+    ctx->last_implied.assign((size_t)C.K, 0);
+    for (const SimpleCol &sc : C.simple) ctx->last_implied[sc.k] = sc.imp_hi - sc.imp_lo;
 #ifdef SPK_HOST_TIMING
     {  // diagnostic build only: host time per spk_gammas phase (settle wait, program preparation, enqueue)
         static double acc[3] = {0, 0, 0};
@@ -3198,8 +3321,7 @@ extern "C" int spk_gammas_load(spk_ctx *ctx, int n_cols, const int32_t *n_levels
     }
     SPK_HIP(hipStreamSynchronize(ctx->stream));
     ctx->n_pairs = n;
-    ctx->gamma_pending = false;
-    ctx->alt.gamma_pending = false;
+    for (Slot &S : ctx->slot) S.gamma_pending = false;
     ++ctx->gamma_seq;
     ctx->codes_valid = true;
     return SPK_OK;
@@ -3368,18 +3490,14 @@ extern "C" int spk_gammas_exact_ms(spk_ctx *ctx, double *out, int n) {
     SPK_HIP(hipSetDevice(ctx->device));
     SPK_TRY(settle_gammas(ctx, nullptr));
     SPK_HIP(hipStreamSynchronize(ctx->stream));
-    // a two-stream split timed each window's launch on its own stream: the sum of both
-    const bool two = ctx->last_windows == 2 && ctx->split_ready && ctx->alt.xev_used.size();
+    // every window of the call timed its launch on its own stream: the sum over the slots the call used
     for (int k = 0; k < n; ++k) {
         out[k] = -1.0;
-        if (k < (int)ctx->xev_used.size() && ctx->xev_used[k]) {
+        for (int i = 0; i < ctx->last_slots; ++i) {
+            const Slot &S = ctx->slot[i];
+            if (k >= (int)S.xev_used.size() || !S.xev_used[k]) continue;
             float ms = 0.f;
-            SPK_HIP(hipEventElapsedTime(&ms, ctx->xev0[k], ctx->xev1[k]));
-            out[k] = (double)ms;
-        }
-        if (two && k < (int)ctx->alt.xev_used.size() && ctx->alt.xev_used[k]) {
-            float ms = 0.f;
-            SPK_HIP(hipEventElapsedTime(&ms, ctx->alt.xev0[k], ctx->alt.xev1[k]));
+            SPK_HIP(hipEventElapsedTime(&ms, S.xev0[k], S.xev1[k]));
             out[k] = (out[k] < 0 ? 0.0 : out[k]) + (double)ms;
         }
     }
@@ -3398,20 +3516,24 @@ extern "C" int spk_gammas_exact_list(spk_ctx *ctx, int k, int32_t *out, int64_t 
     SPK_TRY(settle_gammas(ctx, nullptr));
     SPK_REQUIRE(out && k >= 0 && k < (int)ctx->last_exact.size() && n >= 0, SPK_E_INVALID,
                 "spk_gammas_exact_list: bad args");
-    const int64_t m = std::min<int64_t>(n, ctx->last_exact[k]);
-    if (!ctx->last_split) {
-        if (m > 0)
-            SPK_HIP(hipMemcpy(out, ctx->xlist.p + ctx->last_xbase[k], (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+    // the lists carried from the windows settled during the call, then each slot the call used: its window's list;
+    // the window-relative ordinals made global
+    int64_t done = 0;
+    auto take = [&](const int32_t *list, int64_t count, int64_t first) -> int {
+        const int64_t m = std::min<int64_t>(n - done, count);
+        if (m <= 0) return SPK_OK;
+        SPK_HIP(hipMemcpy(out + done, list, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int64_t j = done; j < done + m; ++j)
+            if (out[j] >= 0) out[j] += (int32_t)first;
+        done += m;
         return SPK_OK;
-    }
-    // a split call: window 0's list, then window 1's with its window-relative ordinals made global
-    const int64_t m0 = std::min<int64_t>(m, ctx->split_first[k]), m1 = m - m0;
-    if (m0 > 0)
-        SPK_HIP(hipMemcpy(out, ctx->xlist.p + ctx->last_xbase[k], (size_t)m0 * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (m1 > 0) {
-        SPK_HIP(hipMemcpy(out + m0, ctx->alt.xlist.p + ctx->alt_xbase[k], (size_t)m1 * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (int64_t i = m0; i < m; ++i)
-            if (out[i] >= 0) out[i] += (int32_t)ctx->split_w;
+    };
+    for (const spk_ctx::ListSeg &g : ctx->list_carry)
+        if (g.k == k) SPK_TRY(take(ctx->xcarry.p + g.off, g.n, g.first));
+    for (int i = 0; i < ctx->last_slots; ++i) {
+        const Slot &S = ctx->slot[i];
+        const GammaPlan &G = *S.gplan;
+        if (k < (int)G.exact.size()) SPK_TRY(take(S.xlist.p + G.xbase[k], G.exact[k], G.first));
     }
     return SPK_OK;
 }
@@ -3462,8 +3584,8 @@ extern "C" int spk_ctx_memory(spk_ctx *ctx, int64_t *out8) {
     m[3] = b(ctx->pl) + b(ctx->pr) + b(ctx->pvl) + b(ctx->pvr);
     for (int v = 0; v < MAX_VIEWS; ++v) m[3] += b(ctx->views[v].rowsL) + b(ctx->views[v].rowsR);
     m[4] = b(ctx->codes);
-    m[5] = b(ctx->work) + b(ctx->xlist) + b(ctx->xpref) + b(ctx->xinfo) + b(ctx->region_count) + b(ctx->prog_blob) +
-           b(ctx->alt.work) + b(ctx->alt.xlist) + b(ctx->alt.xpref) + b(ctx->alt.xinfo) + b(ctx->alt.region_count);
+    m[5] = b(ctx->prog_blob) + b(ctx->xcarry);
+    for (const Slot &S : ctx->slot) m[5] += b(S.work) + b(S.xlist) + b(S.xpref) + b(S.xinfo) + b(S.region_count);
     m[6] = b(ctx->hist) + b(ctx->mpat) + b(ctx->llpat) + b(ctx->cpat) + b(ctx->stats) + b(ctx->mu) + b(ctx->em_ticket) +
            b(ctx->em_row) + b(ctx->em_hot) + b(ctx->mp) + b(ctx->mpat_score) + b(ctx->tf_uniq) + b(ctx->tf_runs) +
            b(ctx->tf_nruns) + b(ctx->tf_mp) + b(ctx->tf_hist) +

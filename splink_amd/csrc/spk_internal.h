@@ -279,7 +279,8 @@ struct Components {
     void clear() { *this = Components(); }
 };
 
-struct GammaPlan;
+struct GammaCols;  // spk_gamma.hip: a call's column decisions
+struct GammaPlan;  // spk_gamma.hip: one window's plan
 enum Kern { K_BLOCK = 0, K_GAMMA = 1, K_EMHIST = 2, K_EMFIN = 3, K_SCORE = 4, K_COUNT = 5 };
 
 }  // namespace spk
@@ -327,7 +328,6 @@ struct spk_ctx {
     bool codes_valid = false;
     int64_t last_deferred = 0;
     std::vector<int64_t> last_exact;  // per column: pairs the last spk_gammas evaluated exactly
-    std::vector<int64_t> last_xbase;  // per column: start of its exact list in xlist (diagnostics)
     std::vector<int64_t> last_implied;  // per column: pairs whose level the blocking key implied
     int filter_mode = 1;              // 1: template-shaped columns through the filter kernel (spk_filter.hip),
                                       // 0: every column through the interpreter (spk_gammas_set_simple)
@@ -342,28 +342,17 @@ struct spk_ctx {
     int64_t last_windows = 0;             // windows the last spk_gammas ran
     std::vector<int64_t> exact_carry;     // exact-pass cells of the windows settled before the last one
     int64_t deferred_carry = 0;           // their slow-list cells
+    // their exact lists (spk_gammas_exact_list), copied behind each other into xcarry when a window is settled:
+    // the next window reuses the slot's list buffer
+    struct ListSeg {
+        int k;                 // column
+        int64_t first, off, n; // the window's first pair ordinal; the list's place in xcarry and its length
+    };
+    std::vector<ListSeg> list_carry;
+    spk::DevBuf<int32_t> xcarry;
+    int64_t xcarry_used = 0;
 
-    // comparison-vector work buffers (reused across calls)
-    spk::DevBuf<int32_t> work;
-    spk::DevBuf<int32_t> xlist;       // [2 x xcap]: compacted exact-pass lists, column after column | slow lists
-    spk::DevBuf<int64_t> xpref;       // [K][regions + 1] offsets of each region's list in its column's list
-    spk::DevBuf<int64_t> xinfo;       // [col_base K | col_count K | overflow | total] (k_prefix)
-    int64_t xcap = 0;
-    int64_t *h_info = nullptr;        // pinned readback of xinfo + slow counts
-    size_t h_info_n = 0;
-    int pinned_info(size_t n) {
-        if (n <= h_info_n) return SPK_OK;
-        if (h_info) (void)hipHostFree(h_info);
-        h_info = nullptr;
-        h_info_n = 0;
-        if (hipHostMalloc(reinterpret_cast<void **>(&h_info), n * 8, hipHostMallocDefault) != hipSuccess) {
-            h_info = nullptr;
-            spk::set_error("hipHostMalloc failed");
-            return SPK_E_OOM;
-        }
-        h_info_n = n;
-        return SPK_OK;
-    }
+    // comparison-vector buffers shared by every window (reused across calls)
     spk::DevBuf<uint8_t> img[2];      // filter row images of table 0 / table 1
     std::vector<int64_t> img_key[2];  // what img[s] was built from: table version, rows, column layout
     spk::DevBuf<uint8_t> vimg[spk::MAX_VIEWS][2];  // row images in rule-view order (views[r])
@@ -371,11 +360,6 @@ struct spk_ctx {
     uint64_t table_epoch = 0;
     spk::DevBuf<uint8_t> prog_blob;   // comparison programs, literals, strides (uploaded when they change)
     std::vector<uint8_t> last_blob;   // host copy of what prog_blob holds
-    // the last spk_gammas: the plan its exact / huge passes ran with, and whether its info block still
-    // has to be read (settle_gammas, at the next synchronisation of a consumer)
-    spk::GammaPlan *gplan = nullptr;
-    void (*gplan_free)(spk::GammaPlan *) = nullptr;
-    bool gamma_pending = false;
     // per column: whether the last settled spk_gammas found cells on its slow list; with the same pairs,
     // tables and program the next call does not launch the slow-list kernels of columns that had none
     // (settle_gammas runs them if the list is not empty after all)
@@ -388,31 +372,53 @@ struct spk_ctx {
                                    // sketch (two-segment bound), 0 key, lengths and whole-string sketch (spk_gammas_set_lev_bound)
     bool slow_force_skip = false;  // tests: leave every slow-list launch to settle_gammas
     uint64_t slow_key_pairs = 0, slow_key_tables = 0;
-    spk::DevBuf<unsigned int> region_count;  // [K][regions] filter work-list lengths
 
-    // Two-stream split (spk_gammas_set_streams): a pair set that fits one ordinal window but holds at least
-    // split_min pairs runs as two windows at once, window 0 on `stream`, window 1 on alt.stream, so one
-    // window's filter (texture-address bound) shares the CUs with the other's exact passes (VALU bound).  `alt`
-    // is a second set of the per-window state; swap_slot() exchanges it with the members above, so the phase,
-    // slow-list and settle functions run unchanged on either window.
+    // The state of one ordinal window of spk_gammas: its list buffers, info block and pinned readback, plan, the
+    // stream it runs on and the events on that stream.  Consecutive windows reuse slot[0], each settled before the
+    // next.  A two-stream split (spk_gammas_set_streams: a pair set that fits one window but holds at least
+    // split_min pairs) runs window 0 in slot[0] and window 1 in slot[1] at once, so one window's filter (texture-
+    // address bound) shares the CUs with the other's exact passes (VALU bound).  slot[0].stream is the context
+    // stream, taken at the start of each call (spk_ctx_set_stream can change it); slot[1] owns its stream.  The
+    // phase, slow-list and settle functions take the slot they work on; nothing is exchanged during a call.
     struct Slot {
-        spk::DevBuf<int32_t> work, xlist;
-        spk::DevBuf<int64_t> xpref, xinfo;
-        spk::DevBuf<unsigned int> region_count;
+        spk::DevBuf<int32_t> work;
+        spk::DevBuf<int32_t> xlist;       // [2 x xcap]: compacted exact-pass lists, column after column | slow lists
+        spk::DevBuf<int64_t> xpref;       // [K][regions + 1] offsets of each region's list in its column's list
+        spk::DevBuf<int64_t> xinfo;       // [col_base K | col_count K | overflow | total] (k_prefix)
+        spk::DevBuf<unsigned int> region_count;  // [K][regions] filter work-list lengths
         int64_t xcap = 0;
-        int64_t *h_info = nullptr;
+        int64_t *h_info = nullptr;        // pinned readback of xinfo + slow counts
         size_t h_info_n = 0;
-        hipEvent_t ev_info = nullptr;
+        int pinned_info(size_t n) {
+            if (n <= h_info_n) return SPK_OK;
+            if (h_info) (void)hipHostFree(h_info);
+            h_info = nullptr;
+            h_info_n = 0;
+            if (hipHostMalloc(reinterpret_cast<void **>(&h_info), n * 8, hipHostMallocDefault) != hipSuccess) {
+                h_info = nullptr;
+                spk::set_error("hipHostMalloc failed");
+                return SPK_E_OOM;
+            }
+            h_info_n = n;
+            return SPK_OK;
+        }
+        hipEvent_t ev_info = nullptr;     // after the info-block readback
+        // the window's plan (its arguments, what its settlement read), and whether its info block still has to be
+        // read (settle_gammas, at the next synchronisation of a consumer)
         spk::GammaPlan *gplan = nullptr;
         bool gamma_pending = false;
         hipStream_t stream = nullptr;
+        // per comparison column: HIP events around its exact-pass launch in this window (timing on; the fused
+        // Jaro-Winkler launch is shared by its columns)
         std::vector<hipEvent_t> xev0, xev1;
         std::vector<char> xev_used;
-    } alt;
+    } slot[2];
+    int last_slots = 0;        // slots the last spk_gammas used (2: it ran split)
+    spk::GammaCols *gcols = nullptr;  // the last spk_gammas' column decisions, shared by its windows
     int gamma_streams = 2;
     int64_t split_min = (int64_t)1 << 22;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool split_ready = false;  // alt.stream and the events exist
+    bool split_ready = false;  // slot[1]'s stream and the events exist
     // The pass's launches as a captured HIP graph (spk_gammas_set_graph, off by default): a call whose key -- program,
     // pairs, tables, buffers, window layout, slow-list decisions -- equals the previous call's is captured, later
     // calls with that key replay it (one launch instead of ~25 API calls).  Measured slower than direct launches
@@ -421,13 +427,9 @@ struct spk_ctx {
     hipGraph_t graph = nullptr;
     hipGraphExec_t gexec = nullptr;
     std::vector<int64_t> gkey, gkey_prev;
-    std::vector<char> gskip0, gskip1;  // the slots' slow_skipped at capture
+    std::vector<char> gskip[2];        // the slots' slow_skipped at capture
     int64_t gview_regions = 0;
     int64_t graph_launches = 0;        // replays so far (diagnostics)
-    bool last_split = false;   // the last spk_gammas ran split: window 1 = pairs [split_w, P)
-    int64_t split_w = 0;
-    std::vector<int64_t> split_first, alt_xbase;  // per column: window 0's exact cells; window 1's list base
-    void swap_slot();
 
     // EM state
     spk::DevBuf<uint64_t> hist;
@@ -463,11 +465,7 @@ struct spk_ctx {
     // launch rewrites mpat with its iteration's parameters
     spk::DevBuf<double> mpat_score;
     std::vector<spk::RawCol *> raw;  // device copies of the input columns (spk_raw_*)
-    ~spk_ctx() {
-        for (spk::RawCol *r : raw) delete r;
-        if (gplan && gplan_free) gplan_free(gplan);
-        if (alt.gplan && gplan_free) gplan_free(alt.gplan);
-    }
+    ~spk_ctx();  // spk_gamma.hip, where the plans are complete types
     bool mpat_valid = false;  // mpat_score holds the mp per pattern of the current codes' last spk_score
     uint64_t score_seq = 0;   // spk_score calls so far (the tf runs depend on their mp per pattern)
     // spk_select: the last selection's survivors, the HIP events around its kernels (created on first use with
@@ -513,7 +511,6 @@ struct spk_ctx {
     int em_n_stats = 0;
     int em_kind = 0;                  // 0: one-launch iteration (re-enqueued on a code fix), 1: finalize of a
                                       // caller's (all-reduced) histogram, whose codes were settled before
-    hipEvent_t ev_info = nullptr;     // after spk_gammas' info-block readback
     hipEvent_t ev_stats = nullptr;    // after the EM statistics readback
 
     // timing: two event pairs per kind, alternating, so the last completed launch of a kind can be read
@@ -524,12 +521,9 @@ struct spk_ctx {
     bool ev_used[2][spk::K_COUNT] = {};
     int ev_slot[spk::K_COUNT] = {};
 
-    // per comparison column: HIP events around its exact-pass launch in the last spk_gammas (timing on;
-    // the fused Jaro-Winkler launch is shared by its columns)
-    std::vector<hipEvent_t> xev0, xev1;
-    std::vector<char> xev_used;
-    int xbegin(int k);
-    int xend(int k);
+    // HIP events around column k's exact-pass launch in a window (timing_exact)
+    int xbegin(Slot &s, int k);
+    int xend(Slot &s, int k);
 
     int begin(spk::Kern k);
     int end(spk::Kern k);

@@ -177,6 +177,54 @@ def test_graph_replay_gives_identical_codes(dedupe_job, streams, mode):
         job.ctx.gammas_set_simple(1)
 
 
+@pytest.mark.parametrize("pending", [False, True])
+def test_slot_configurations_in_sequence(dedupe_job, pending):
+    """One context through the slot configurations in sequence: split, three consecutive windows (which do not
+    split, while the second slot still holds the previous call's state), split again, one stream.  After every
+    read the codes, the exact-pass cell counts, the Levenshtein column's exact list and the window count equal the
+    one-stream pass; pending: calls 1 -> 2 and 2 -> 3 back to back, the earlier one unread when the next starts.
+    (Consecutive windows reuse one slot's list buffers: the three-window call's list is whole because the lists of
+    the windows settled during the call are carried, spk_ctx::list_carry.)"""
+    job, st, ref = dedupe_job
+    P = job.n_pairs
+    seen = []
+
+    def read():
+        got = job.gammas_host()
+        exact = job.ctx.gammas_exact_counts(len(COLS))
+        seen.append((got, exact, np.sort(job.ctx.gammas_exact_list(4, exact[4])), job.ctx.gammas_windows()))
+
+    try:
+        job.ctx.gammas_set_window(0)
+        job.ctx.gammas_set_streams(1)
+        job.gammas(st)
+        read()
+        _, exact_one, list_one, _ = seen.pop()
+        job.ctx.gammas_set_streams(2, 0)
+        job.gammas(st)  # 1: split
+        if not pending:
+            read()
+        job.ctx.gammas_set_window(P // 3 + 1)
+        job.gammas(st)  # 2: three windows in the first slot
+        if not pending:
+            read()
+        job.ctx.gammas_set_window(0)
+        job.gammas(st)  # 3: split again
+        read()
+        job.ctx.gammas_set_streams(1)
+        job.gammas(st)  # 4: one stream
+        read()
+    finally:
+        job.ctx.gammas_set_window(0)
+        job.ctx.gammas_set_streams(2)
+    assert [s[3] for s in seen] == ([2, 1] if pending else [2, 3, 2, 1])
+    for got, exact, _, _ in seen:
+        assert (got == ref).all(), np.nonzero((got != ref).any(axis=1))[0][:10]
+        assert exact == exact_one
+    for _, _, lst, n_win in seen:
+        assert np.array_equal(lst, list_one), n_win
+
+
 def test_two_stream_split_exact_ms(dedupe_job):
     """The split pass reports an exact launch's time as the sum of its two windows' launches (spk_gammas_exact_ms),
     the one-stream pass as its one launch."""
