@@ -6,9 +6,10 @@ of spk_block.hip, compared as an ordered sequence."""
 import numpy as np
 import pytest
 
+from ordinal_common import DEDUPE, LINK_ONLY, expected_pairs  # the contract, restated (brute force)
+
 pytestmark = pytest.mark.gpu
 
-DEDUPE, LINK_ONLY = 0, 1
 CHUNK = 2048  # spk_block.hip EN_CHUNK
 
 
@@ -18,37 +19,6 @@ def native():
     if _native.device_count() == 0:
         pytest.fail("no HIP device visible: the -m gpu tests need an MI355X")
     return _native
-
-
-# ---- the contract, restated ---------------------------------------------------------------------------------
-def expected_pairs(link_type, keys_l, keys_r, rank):
-    """keys_l[r] / keys_r[r]: rule r's key per row of the l / r table (-1 NULL); rank: per row of the one table
-    (dedupe) or None (link_only).  Returns the (l, r) sequence and the candidate count: rule after rule, blocks
-    by ascending key, rows inside a block in stable (key, rank) order (r side of a bipartite rule: (key, row)),
-    ordinals l-major, then the rank predicate and the earlier-rule exclusion."""
-    out, n_cand = [], 0
-    for r, (kl, kr) in enumerate(zip(keys_l, keys_r)):
-        def view(k, rk):
-            rows = np.nonzero(k >= 0)[0]
-            return rows[np.lexsort((rows, rk[rows], k[rows]))]
-        zl, zr = np.zeros(len(kl), np.int64), np.zeros(len(kr), np.int64)
-        vl = view(kl, zl if rank is None else rank)
-        vr = view(kr, zr)
-        for key in np.unique(kl[vl]):
-            bl = vl[kl[vl] == key]
-            if link_type == DEDUPE:
-                cand = [(x, y) for a, x in enumerate(bl) for y in bl[a + 1:]]
-            else:
-                br = vr[kr[vr] == key]
-                cand = [(x, y) for x in bl for y in br]
-            n_cand += len(cand)
-            for x, y in cand:
-                if rank is not None and rank[x] == rank[y]:
-                    continue
-                if any(keys_l[j][x] >= 0 and keys_l[j][x] == keys_r[j][y] for j in range(r)):
-                    continue
-                out.append((int(x), int(y)))
-    return np.array(out, dtype=np.int64).reshape(-1, 2), n_cand
 
 
 def load(native, link_type, keys_l, keys_r, rank):
