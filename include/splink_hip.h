@@ -294,6 +294,61 @@ int spk_block_residual(spk_ctx *ctx, int link_type, int n_rules, const int32_t *
  * each rule's count kernel and scan and around the emit kernels; the host round trips between them (survivor
  * counts, buffer allocation) are not in it. */
 int spk_block_residual_info(spk_ctx *ctx, int64_t *out_enumerated, double *out_filter_ms);
+
+/* ---- blocking-rule profile (comparison_evaluation.py:12-35 and beyond): what the rules would cost, without
+ *      building the pair set ------------------------------------------------------------------------------------ */
+typedef struct {
+    int64_t rows_l, rows_r;       /* rows with a non-NULL key of the rule as the join's l- / r-side
+                                     (symmetric self-join: equal) */
+    int64_t blocks;               /* distinct l-side key values among them */
+    int64_t candidates;           /* the rule's candidate ordinals: sum over blocks of n(n-1)/2 or nL*nR */
+    int64_t largest_candidates;   /* of one block */
+    int64_t enumerated;           /* pairs the count pass keeps in this shard's ordinals of the rule,
+                                     or -1: not enumerated */
+} spk_rule_profile;
+
+typedef struct {
+    int64_t rows_l, rows_r, candidates;
+    int32_t row_l;                /* table-0 device row of the block's first l-view position */
+    int32_t pad;
+} spk_block_entry;
+
+#define SPK_PROFILE_BINS 64
+#define SPK_LARGEST_BY_CANDIDATES 0
+#define SPK_LARGEST_BY_ROWS_L 1
+
+/* Profiles rules 0..n_rules-1 (keys set as for spk_block) from the tables' keys and ranks alone.  Nothing else of the
+ * context is read or written: the pair set, views, codes, selection, labels, scores and the context's link type stay,
+ * and every buffer of the call is freed before it returns; nothing it allocates is sized by a pair or candidate count.
+ *
+ * Key-level figures (the same for every shard, O(rows) after the key sort): out_rules' rows_*, blocks, candidates
+ * (their sum over the rules is spk_block's out_n_candidates_total) and largest_candidates; the histogram, whose bin i
+ * holds the blocks whose candidate count has bit length i (bin 0: a block without a candidate) as
+ * out_hist[(r * SPK_PROFILE_BINS + i) * 2 + 0] blocks and [.. + 1] the sum of their candidates; and the first
+ * min(limit, blocks) blocks of each rule in descending order of largest_by (candidates or l-side rows), ties by
+ * ascending block index in the rule's key order, as out_largest[r * limit + ..] with their number in out_n_largest[r].
+ *
+ * Enumeration: rule r's ordinals in this shard -- cut as spk_block cuts them -- go through spk_block's count pass when
+ * max_enumerate < 0 or the range is at most max_enumerate long (0: never); `enumerated` is then the pairs that pass
+ * keeps (the link-type predicate with the NULL-unique-id rule, exclusion on the keys of the earlier rules without a
+ * program), else -1.  With rule_program = NULL the sum over the rules is spk_block's out_n_pairs of that shard; with
+ * programs (only their sign is read) it is spk_block_residual_info's out_enumerated: residual predicates themselves
+ * are not evaluated.  The pass runs in slabs of at most 2^31 ordinals, each reduced to one count on the device.
+ *
+ * SPK_E_STATE: keys not set for every rule, tables not loaded, no rank under dedupe_only / link_and_dedupe.
+ * SPK_E_INVALID: limit < 0, limit > 0 with out_largest or out_n_largest NULL, an unknown largest_by, a bad shard, link
+ * type or rule count.  A failing call leaves the outputs unspecified and the context as it was. */
+int spk_block_profile(spk_ctx *ctx, int link_type, int n_rules, const int32_t *rule_symmetric,
+                      const int32_t *rule_program, int shard, int n_shards, int64_t max_enumerate, int largest_by,
+                      int limit, spk_rule_profile *out_rules, int64_t *out_hist, spk_block_entry *out_largest,
+                      int32_t *out_n_largest);
+/* The last spk_block_profile: with timing on (spk_ctx_enable_timing) the HIP-event milliseconds of its key-level part
+ * (sorts, block statistics, largest blocks) and of its enumeration, -1 each otherwise; and the ordinals its count pass
+ * went through (-1: no call yet, or the last one failed). */
+int spk_block_profile_info(spk_ctx *ctx, double *out_key_ms, double *out_enum_ms, int64_t *out_ordinals_enumerated);
+/* Measurement switch: on = 0 makes the largest-blocks step sort every block of a rule instead of only those in the
+ * top histogram bins (the default, 1).  The results are the same. */
+int spk_block_profile_set_cut(spk_ctx *ctx, int on);
 /* Decode codes to int8 gamma columns, [count x K] row-major. */
 int spk_gammas_copy(spk_ctx *ctx, int64_t start, int64_t count, int8_t *out);
 /* Use a caller-provided gamma matrix (int8 [n x K], values -1..L_k-1). */

@@ -16,6 +16,8 @@ from typing import Callable
 from .blocking import block_using_rules
 from .case_statements import _check_jaro_registered
 from .check_types import check_types
+from .comparison_evaluation import (DEFAULT_MAX_ENUMERATE, BlockingProfile, get_largest_blocks,
+                                    profile_blocking_rules)
 from .expectation_step import run_expectation_step
 from .frames import BestMatchFrame, ClusterFrame, FilteredFrame, SplinkDataFrame
 from .gammas import add_gammas
@@ -31,7 +33,8 @@ from .validate import validate_settings
 __all__ = ["Splink", "load_from_json", "AmdSession", "session", "Params", "block_using_rules", "add_gammas",
            "iterate", "run_expectation_step", "make_adjustment_for_term_frequencies", "complete_settings_dict",
            "ClusterFrame", "FilteredFrame", "BestMatchFrame", "LabelCounts", "estimate_from_labels",
-           "estimate_u_using_random_sampling", "random_pairs"]
+           "estimate_u_using_random_sampling", "random_pairs", "get_largest_blocks", "profile_blocking_rules",
+           "BlockingProfile"]
 
 
 def _is_frame(x):
@@ -96,6 +99,14 @@ class Splink:
         the (gamma column, level) table of counts and u (sampling.estimate_u_using_random_sampling)."""
         return estimate_u_using_random_sampling(self.settings, self.params, self.spark, max_pairs, seed=seed,
                                                 fix=fix, df_l=self.df_l, df_r=self.df_r, df=self.df)
+
+    def profile_blocking_rules(self, limit: int = 5, max_enumerate: int = DEFAULT_MAX_ENUMERATE):
+        """What the settings' blocking rules would cost on the linker's own tables, computed on the device without
+        generating a pair: per rule the rows with a key, blocks, candidate pairs, the largest blocks with their key
+        values and, for rules whose candidate range is at most `max_enumerate` long, the pairs they would emit
+        (comparison_evaluation.profile_blocking_rules).  Returns a BlockingProfile."""
+        return profile_blocking_rules(self.settings, self.spark, df_l=self.df_l, df_r=self.df_r, df=self.df,
+                                      limit=limit, max_enumerate=max_enumerate)
 
     def make_term_frequency_adjustments(self, df_e: SplinkDataFrame):
         return make_adjustment_for_term_frequencies(df_e, self.params, self.settings, retain_adjustment_columns=True,

@@ -77,7 +77,16 @@ EXPORTS = [
     "spk_components", "spk_components_edges", "spk_components_copy", "spk_components_info", "spk_components_release",
     "spk_label_histogram", "spk_label_info",
     "spk_pairs_sample", "spk_pairs_sample_info",
+    "spk_block_profile", "spk_block_profile_info", "spk_block_profile_set_cut",
 ]
+# spk_rule_profile / spk_block_entry: the per-rule figures and one of a rule's largest blocks (spk_block_profile)
+RULE_PROFILE_DTYPE = np.dtype([("rows_l", "<i8"), ("rows_r", "<i8"), ("blocks", "<i8"), ("candidates", "<i8"),
+                               ("largest_candidates", "<i8"), ("enumerated", "<i8")], align=True)
+BLOCK_ENTRY_DTYPE = np.dtype([("rows_l", "<i8"), ("rows_r", "<i8"), ("candidates", "<i8"), ("row_l", "<i4"),
+                              ("pad", "<i4")], align=True)
+assert RULE_PROFILE_DTYPE.itemsize == 48 and BLOCK_ENTRY_DTYPE.itemsize == 32
+PROFILE_BINS = 64  # SPK_PROFILE_BINS
+LARGEST_BY_CANDIDATES, LARGEST_BY_ROWS_L = 0, 1  # SPK_LARGEST_BY_*
 # Draws per workgroup of spk_pairs_sample's kernel (256 threads x 8 consecutive draws).  Mirrored from SM_CHUNK in
 # csrc/spk_sample.hip; only the tests' edge sizes depend on it.
 SAMPLE_CHUNK = 2048
@@ -330,6 +339,40 @@ class Context:
         ms = ctypes.c_double(-1.0)
         check(self._lib.spk_block_residual_info(self._h, ctypes.byref(n), ctypes.byref(ms)), "spk_block_residual_info")
         return n.value, ms.value
+
+    def block_profile(self, link_type: int, symmetric, rule_program=None, shard: int = 0, n_shards: int = 1,
+                      max_enumerate: int = 0, largest_by: int = LARGEST_BY_CANDIDATES, limit: int = 5):
+        """spk_block_profile over the rules whose keys are set: (rules [n_rules] of RULE_PROFILE_DTYPE, histogram
+        int64 [n_rules, PROFILE_BINS, 2] of (blocks, candidates) per bit length of a block's candidate count, and per
+        rule its largest blocks as an array of BLOCK_ENTRY_DTYPE).  The pair set and the rest of the context stay."""
+        sym = np.ascontiguousarray(symmetric, dtype=np.int32)
+        prog = None if rule_program is None else np.ascontiguousarray(rule_program, dtype=np.int32)
+        assert prog is None or len(prog) == len(sym)
+        n, limit = len(sym), int(limit)
+        rules = np.zeros(max(n, 1), dtype=RULE_PROFILE_DTYPE)
+        hist = np.zeros((max(n, 1), PROFILE_BINS, 2), dtype=np.int64)
+        largest = np.zeros((max(n, 1), max(limit, 1)), dtype=BLOCK_ENTRY_DTYPE)
+        n_largest = np.zeros(max(n, 1), dtype=np.int32)
+        check(self._lib.spk_block_profile(self._h, ctypes.c_int(link_type), ctypes.c_int(n), _ptr(sym), _ptr(prog),
+                                          ctypes.c_int(shard), ctypes.c_int(n_shards),
+                                          ctypes.c_int64(int(max_enumerate)), ctypes.c_int(int(largest_by)),
+                                          ctypes.c_int(limit), _ptr(rules), _ptr(hist), _ptr(largest),
+                                          _ptr(n_largest)), "spk_block_profile")
+        return rules[:n], hist[:n], [largest[r, :int(n_largest[r])].copy() for r in range(n)]
+
+    def block_profile_info(self):
+        """(ms of the last block_profile's key-level part, ms of its enumeration -- HIP events, timing on, else -1 --
+        and the ordinals its count pass went through, -1: none yet or the last call failed)."""
+        key_ms = ctypes.c_double(-1.0)
+        enum_ms = ctypes.c_double(-1.0)
+        n = ctypes.c_int64(-1)
+        check(self._lib.spk_block_profile_info(self._h, ctypes.byref(key_ms), ctypes.byref(enum_ms), ctypes.byref(n)),
+              "spk_block_profile_info")
+        return key_ms.value, enum_ms.value, n.value
+
+    def block_profile_set_cut(self, on: bool = True):
+        """Measurement switch: False sorts every block in the largest-blocks step instead of the top bins' only."""
+        check(self._lib.spk_block_profile_set_cut(self._h, ctypes.c_int(1 if on else 0)), "spk_block_profile_set_cut")
 
     def pairs_count(self) -> int:
         n = ctypes.c_int64(0)

@@ -472,6 +472,94 @@ __global__ __launch_bounds__(RF_THREADS) void k_residual_filter(ResidualFilterAr
     }
 }
 
+// ---- rule profile (spk_block_profile): block statistics and the largest blocks of a planned rule --------------
+static constexpr int PS_THREADS = 256;
+static constexpr int PS_WAVES = PS_THREADS / 64;
+static constexpr int64_t PROFILE_SLAB = (int64_t)1 << 31;  // ordinals per count-pass launch (a multiple of EN_CHUNK)
+
+struct ProfileStats {
+    unsigned long long hist[SPK_PROFILE_BINS][2];      // by bit length of the candidate count: blocks, candidates
+    unsigned long long rows_bins[SPK_PROFILE_BINS];    // by bit length of the l-side row count: blocks
+    unsigned long long largest;                        // candidates of the largest block
+};
+
+__device__ inline int bit_length(int64_t v) { return v > 0 ? 64 - __clzll((long long)v) : 0; }
+
+// One pass over the per-block candidate counts.  A workgroup bins into LDS counters and adds each non-empty one to
+// the global counters once; the largest count goes through a wave reduction and one atomicMax per workgroup.  Every
+// counter is an integer, so the result does not depend on the launch shape.
+__global__ __launch_bounds__(PS_THREADS) void k_block_stats(int64_t B, const int64_t *__restrict__ cand,
+                                                            const int64_t *__restrict__ bstart,
+                                                            ProfileStats *__restrict__ out) {
+    __shared__ unsigned long long s_bins[SPK_PROFILE_BINS][3];
+    __shared__ long long s_max[PS_WAVES];
+    if (threadIdx.x < SPK_PROFILE_BINS) s_bins[threadIdx.x][0] = s_bins[threadIdx.x][1] = s_bins[threadIdx.x][2] = 0;
+    __syncthreads();
+    long long mx = 0;
+    for (int64_t b = (int64_t)blockIdx.x * PS_THREADS + threadIdx.x; b < B; b += (int64_t)gridDim.x * PS_THREADS) {
+        const int64_t c = cand[b];
+        const int i = bit_length(c);
+        atomicAdd(&s_bins[i][0], 1ull);
+        if (c > 0) atomicAdd(&s_bins[i][1], (unsigned long long)c);
+        atomicAdd(&s_bins[bit_length(bstart[b + 1] - bstart[b])][2], 1ull);
+        mx = c > mx ? c : mx;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const long long o = __shfl_xor(mx, off, 64);
+        mx = o > mx ? o : mx;
+    }
+    if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long m = 0;
+        for (int w = 0; w < PS_WAVES; ++w) m = s_max[w] > m ? s_max[w] : m;
+        if (m > 0) atomicMax(&out->largest, (unsigned long long)m);
+    }
+    if (threadIdx.x < SPK_PROFILE_BINS) {
+        const int i = threadIdx.x;
+        if (s_bins[i][0]) atomicAdd(&out->hist[i][0], s_bins[i][0]);
+        if (s_bins[i][1]) atomicAdd(&out->hist[i][1], s_bins[i][1]);
+        if (s_bins[i][2]) atomicAdd(&out->rows_bins[i], s_bins[i][2]);
+    }
+}
+
+// What the largest blocks are ordered by: the candidate count, or the l-side rows.
+__device__ inline int64_t block_metric(int by_rows, const int64_t *cand, const int64_t *bstart, int64_t b) {
+    return by_rows ? bstart[b + 1] - bstart[b] : cand[b];
+}
+
+// Blocks whose metric lies in the bins >= min_bin, compacted in block order (count, scan, emit): the sort key is the
+// complement of the metric, so an ascending stable sort gives descending metric with ties in ascending block index.
+__global__ void k_top_flag(int64_t B, const int64_t *__restrict__ cand, const int64_t *__restrict__ bstart, int by_rows,
+                           int min_bin, int64_t *__restrict__ flag) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) flag[b] = bit_length(block_metric(by_rows, cand, bstart, b)) >= min_bin ? 1 : 0;
+}
+
+__global__ void k_top_emit(int64_t B, const int64_t *__restrict__ cand, const int64_t *__restrict__ bstart, int by_rows,
+                           const int64_t *__restrict__ flag, const int64_t *__restrict__ off,
+                           uint64_t *__restrict__ keys, int32_t *__restrict__ index) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B || !flag[b]) return;
+    keys[off[b]] = ~(uint64_t)block_metric(by_rows, cand, bstart, b);
+    index[off[b]] = (int32_t)b;
+}
+
+__global__ void k_top_entries(int m, const int32_t *__restrict__ index, const int64_t *__restrict__ cand,
+                              const int64_t *__restrict__ bstart, const int64_t *__restrict__ bnR, int tri,
+                              const int32_t *__restrict__ rowsL, spk_block_entry *__restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const int64_t b = index[i];
+    spk_block_entry e;
+    e.rows_l = bstart[b + 1] - bstart[b];
+    e.rows_r = tri ? e.rows_l : bnR[b];
+    e.candidates = cand[b];
+    e.row_l = rowsL[bstart[b]];
+    e.pad = 0;
+    out[i] = e;
+}
+
 }  // namespace spk
 
 using namespace spk;
@@ -755,6 +843,242 @@ extern "C" int spk_block_residual(spk_ctx *ctx, int link_type, int n_rules, cons
     ctx->set_rule_ranges(new_base, n_out);
     commit.done = true;
     if (out_n_pairs) *out_n_pairs = n_out;
+    return SPK_OK;
+}
+
+namespace {
+// spk_block_profile plans and enumerates under its own link type (plan_rule, build_by_position and enum_args read
+// the context's) and hands the context's back on every way out.
+struct LinkTypeLease {
+    spk_ctx *ctx;
+    int saved;
+    LinkTypeLease(spk_ctx *c, int link_type) : ctx(c), saved(c->link_type) { c->link_type = link_type; }
+    ~LinkTypeLease() { ctx->link_type = saved; }
+};
+
+// The call's two HIP events (timing on), destroyed when it returns.
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~EventPair() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+
+// The first min(limit, B) blocks of a planned rule by descending metric into out[0 .. *n_out).  `bins`: blocks per
+// bit length of the metric (k_block_stats).  With the cut, only the blocks in the bins >= j are sorted, j the highest
+// bin with at least `limit` blocks at or above it (0 when the rule has fewer blocks).
+int largest_blocks(spk_ctx *ctx, const RulePlan &P, int by_rows, const unsigned long long *bins, int limit,
+                   spk_block_entry *out, int32_t *n_out, DevBuf<uint8_t> &tmp) {
+    *n_out = 0;
+    const int64_t B = P.B;
+    if (B == 0 || limit == 0) return SPK_OK;
+    int min_bin = 0;
+    if (ctx->profile_cut) {
+        unsigned long long above = 0;
+        for (int j = SPK_PROFILE_BINS - 1; j > 0; --j) {
+            above += bins[j];
+            if (above >= (unsigned long long)limit) {
+                min_bin = j;
+                break;
+            }
+        }
+    }
+    CountScan pick;
+    SPK_TRY(pick.alloc(ctx, B));
+    const unsigned g = (unsigned)((B + 255) / 256);
+    k_top_flag<<<g, 256, 0, ctx->stream>>>(B, P.cand.count.p, P.bstart.p, by_rows, min_bin, pick.count.p);
+    SPK_HIP(hipGetLastError());
+    SPK_TRY(scan_total(ctx, pick, tmp));
+    const int64_t n = pick.total;
+    SPK_REQUIRE(n >= std::min<int64_t>(limit, B) && n <= B, SPK_E_STATE, "spk_block_profile: largest-blocks cut");
+    DevBuf<uint64_t> k_in, k_out;
+    DevBuf<int32_t> i_in, i_out;
+    SPK_TRY(k_in.alloc((size_t)n));
+    SPK_TRY(k_out.alloc((size_t)n));
+    SPK_TRY(i_in.alloc((size_t)n));
+    SPK_TRY(i_out.alloc((size_t)n));
+    k_top_emit<<<g, 256, 0, ctx->stream>>>(B, P.cand.count.p, P.bstart.p, by_rows, pick.count.p, pick.off.p, k_in.p,
+                                           i_in.p);
+    SPK_HIP(hipGetLastError());
+    SPK_TRY(sort_pairs_u64(ctx->stream, tmp, k_in.p, k_out.p, i_in.p, i_out.p, n));
+    const int m = (int)std::min<int64_t>(limit, n);
+    DevBuf<spk_block_entry> d_out;
+    SPK_TRY(d_out.alloc((size_t)m));
+    k_top_entries<<<(unsigned)((m + 255) / 256), 256, 0, ctx->stream>>>(m, i_out.p, P.cand.count.p, P.bstart.p,
+                                                                        P.bnR.p, P.tri, P.L.rows.p, d_out.p);
+    SPK_HIP(hipGetLastError());
+    SPK_HIP(hipMemcpyAsync(out, d_out.p, (size_t)m * sizeof(spk_block_entry), hipMemcpyDeviceToHost, ctx->stream));
+    SPK_HIP(hipStreamSynchronize(ctx->stream));
+    *n_out = m;
+    return SPK_OK;
+}
+
+// Pairs spk_block's count pass keeps among the ordinals [lo, hi) of a rule whose by-position copies are built: one
+// k_enum<false> launch per PROFILE_SLAB ordinals into the same chunk array, each reduced to one count on the device.
+int count_ordinals(spk_ctx *ctx, const RulePlan &P, int64_t lo, int64_t hi, DevBuf<int64_t> &chunks,
+                   DevBuf<uint8_t> &tmp, int64_t *out) {
+    *out = 0;
+    const int64_t n_slabs = (hi - lo + PROFILE_SLAB - 1) / PROFILE_SLAB;
+    if (n_slabs <= 0) return SPK_OK;
+    DevBuf<int64_t> d_sum;
+    SPK_TRY(d_sum.alloc((size_t)n_slabs));
+    SPK_TRY(chunks.alloc((size_t)(std::min(hi - lo, PROFILE_SLAB) + EN_CHUNK - 1) / EN_CHUNK));
+    for (int64_t s = 0; s < n_slabs; ++s) {
+        const int64_t q0 = lo + s * PROFILE_SLAB, q1 = std::min(q0 + PROFILE_SLAB, hi);
+        const int64_t n_chunks = (q1 - q0 + EN_CHUNK - 1) / EN_CHUNK;
+        EnumArgs A = enum_args(ctx, P, q0, q1);
+        A.chunk_count = chunks.p;
+        k_enum<false><<<(unsigned)n_chunks, EN_THREADS, 0, ctx->stream>>>(A);
+        SPK_HIP(hipGetLastError());
+        SPK_TRY(reduce_sum(ctx->stream, tmp, chunks.p, d_sum.p + s, n_chunks));
+    }
+    std::vector<int64_t> h((size_t)n_slabs);
+    SPK_HIP(hipMemcpyAsync(h.data(), d_sum.p, (size_t)n_slabs * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SPK_HIP(hipStreamSynchronize(ctx->stream));
+    for (int64_t v : h) *out += v;
+    return SPK_OK;
+}
+}  // namespace
+
+extern "C" int spk_block_profile(spk_ctx *ctx, int link_type, int n_rules, const int32_t *rule_symmetric,
+                                 const int32_t *rule_program, int shard, int n_shards, int64_t max_enumerate,
+                                 int largest_by, int limit, spk_rule_profile *out_rules, int64_t *out_hist,
+                                 spk_block_entry *out_largest, int32_t *out_n_largest) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "null ctx");
+    ctx->profile_ordinals = -1;
+    ctx->profile_key_ms = ctx->profile_enum_ms = -1.0;
+    SPK_REQUIRE(n_rules >= 1 && n_rules <= MAX_RULES && rule_symmetric && out_rules, SPK_E_INVALID,
+                "spk_block_profile: need 1..32 rules");
+    SPK_REQUIRE(link_type >= 0 && link_type <= 2, SPK_E_INVALID, "spk_block_profile: bad link_type");
+    SPK_REQUIRE(n_shards >= 1 && shard >= 0 && shard < n_shards, SPK_E_INVALID, "spk_block_profile: bad shard");
+    SPK_REQUIRE(largest_by == SPK_LARGEST_BY_CANDIDATES || largest_by == SPK_LARGEST_BY_ROWS_L, SPK_E_INVALID,
+                "spk_block_profile: unknown largest_by");
+    SPK_REQUIRE(limit >= 0, SPK_E_INVALID, "spk_block_profile: negative limit");
+    SPK_REQUIRE(limit == 0 || (out_largest && out_n_largest), SPK_E_INVALID,
+                "spk_block_profile: limit > 0 needs out_largest and out_n_largest");
+    SPK_HIP(hipSetDevice(ctx->device));
+    LinkTypeLease lease(ctx, link_type);
+    Table &tl = ctx->table[0];
+    Table &tr = ctx->side_table(1);
+    SPK_REQUIRE(tl.n >= 0 && tr.n >= 0, SPK_E_STATE, "spk_block_profile: tables not loaded");
+    const bool link_only = link_type == SPK_LINK_ONLY;
+    SPK_REQUIRE(link_only || tl.rank.p || tl.n == 0, SPK_E_STATE, "spk_block_profile: rank not set");
+    for (int r = 0; r < n_rules; ++r) {
+        SPK_REQUIRE((int)tl.key[0].size() > r && tl.key[0][r]->p && (int)tr.key[1].size() > r && tr.key[1][r]->p,
+                    SPK_E_STATE, "spk_block_profile: keys not set for every rule");
+    }
+    EventPair ev;
+    if (ctx->timing) {
+        SPK_HIP(hipEventCreate(&ev.e0));
+        SPK_HIP(hipEventCreate(&ev.e1));
+    }
+    auto elapsed = [&](double *ms) -> int {  // the stream is synchronised
+        if (!ctx->timing) return SPK_OK;
+        float f = 0.f;
+        SPK_HIP(hipEventElapsedTime(&f, ev.e0, ev.e1));
+        *ms = (double)f;
+        return SPK_OK;
+    };
+    // ---- key level: per rule the plan (sorted views, blocks, candidates per block and their scan), the block
+    // statistics and the largest blocks.  A plan is kept only while its rule may still be enumerated.
+    double key_ms = -1.0, enum_ms = -1.0;
+    DevBuf<uint8_t> tmp;
+    DevBuf<ProfileStats> d_stats;
+    SPK_TRY(d_stats.alloc(1));
+    std::vector<RulePlan> plans(n_rules);
+    int64_t total = 0;
+    if (ctx->timing) SPK_HIP(hipEventRecord(ev.e0, ctx->stream));
+    for (int r = 0; r < n_rules; ++r) {
+        RulePlan &P = plans[r];
+        SPK_TRY(plan_rule(ctx, r, rule_symmetric[r] != 0, P, tmp));
+        ProfileStats st;
+        std::memset(&st, 0, sizeof(st));
+        if (P.B > 0) {
+            SPK_HIP(hipMemsetAsync(d_stats.p, 0, sizeof(ProfileStats), ctx->stream));
+            const unsigned g = (unsigned)std::min<int64_t>((P.B + PS_THREADS - 1) / PS_THREADS, 4 * (int64_t)ctx->n_cu);
+            k_block_stats<<<g, PS_THREADS, 0, ctx->stream>>>(P.B, P.cand.count.p, P.bstart.p, d_stats.p);
+            SPK_HIP(hipGetLastError());
+            SPK_HIP(hipMemcpyAsync(&st, d_stats.p, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
+            SPK_HIP(hipStreamSynchronize(ctx->stream));
+        }
+        spk_rule_profile &o = out_rules[r];
+        o.rows_l = P.L.n_valid;
+        o.rows_r = P.tri ? P.L.n_valid : P.R.n_valid;
+        o.blocks = P.B;
+        o.candidates = P.cand.total;
+        o.largest_candidates = (int64_t)st.largest;
+        o.enumerated = -1;
+        total += P.cand.total;
+        if (out_hist)
+            for (int i = 0; i < SPK_PROFILE_BINS; ++i) {
+                out_hist[((size_t)r * SPK_PROFILE_BINS + i) * 2 + 0] = (int64_t)st.hist[i][0];
+                out_hist[((size_t)r * SPK_PROFILE_BINS + i) * 2 + 1] = (int64_t)st.hist[i][1];
+            }
+        if (limit > 0) {
+            const bool by_rows = largest_by == SPK_LARGEST_BY_ROWS_L;
+            unsigned long long bins[SPK_PROFILE_BINS];
+            for (int i = 0; i < SPK_PROFILE_BINS; ++i) bins[i] = by_rows ? st.rows_bins[i] : st.hist[i][0];
+            SPK_TRY(largest_blocks(ctx, P, by_rows ? 1 : 0, bins, limit, out_largest + (size_t)r * limit,
+                                   out_n_largest + r, tmp));
+        }
+        if (max_enumerate == 0) P = RulePlan();
+    }
+    if (ctx->timing) {
+        SPK_HIP(hipEventRecord(ev.e1, ctx->stream));
+        SPK_HIP(hipStreamSynchronize(ctx->stream));
+        SPK_TRY(elapsed(&key_ms));
+    }
+    // ---- enumeration: this shard's ordinals of each rule, cut as block_rules cuts them
+    const int64_t g_lo = (int64_t)((__int128)total * shard / n_shards);
+    const int64_t g_hi = (int64_t)((__int128)total * (shard + 1) / n_shards);
+    int64_t acc = 0, ordinals = 0;
+    DevBuf<int64_t> chunks;
+    if (ctx->timing) SPK_HIP(hipEventRecord(ev.e0, ctx->stream));
+    for (int r = 0; r < n_rules && max_enumerate != 0; ++r) {
+        RulePlan &P = plans[r];
+        const int64_t lo = std::max<int64_t>(g_lo - acc, 0), hi = std::min<int64_t>(g_hi - acc, P.cand.total);
+        acc += P.cand.total;
+        const int64_t len = std::max<int64_t>(hi - lo, 0);
+        if (max_enumerate > 0 && len > max_enumerate) {
+            P = RulePlan();
+            continue;
+        }
+        if (len > 0) {
+            std::vector<int> excl;
+            for (int j = 0; j < r; ++j)
+                if (!rule_program || rule_program[j] < 0) excl.push_back(j);
+            SPK_TRY(build_by_position(ctx, excl, P));
+            SPK_TRY(count_ordinals(ctx, P, lo, hi, chunks, tmp, &out_rules[r].enumerated));
+            ordinals += len;
+        } else {
+            out_rules[r].enumerated = 0;
+        }
+        P = RulePlan();  // the rule's views, blocks and by-position copies
+    }
+    if (ctx->timing) {
+        SPK_HIP(hipEventRecord(ev.e1, ctx->stream));
+        SPK_HIP(hipStreamSynchronize(ctx->stream));
+        SPK_TRY(elapsed(&enum_ms));
+    }
+    ctx->profile_key_ms = key_ms;
+    ctx->profile_enum_ms = enum_ms;
+    ctx->profile_ordinals = ordinals;
+    return SPK_OK;
+}
+
+extern "C" int spk_block_profile_info(spk_ctx *ctx, double *out_key_ms, double *out_enum_ms,
+                                      int64_t *out_ordinals_enumerated) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "null ctx");
+    if (out_key_ms) *out_key_ms = ctx->profile_key_ms;
+    if (out_enum_ms) *out_enum_ms = ctx->profile_enum_ms;
+    if (out_ordinals_enumerated) *out_ordinals_enumerated = ctx->profile_ordinals;
+    return SPK_OK;
+}
+
+extern "C" int spk_block_profile_set_cut(spk_ctx *ctx, int on) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "null ctx");
+    ctx->profile_cut = on != 0;
     return SPK_OK;
 }
 

@@ -489,6 +489,12 @@ struct spk_ctx {
     int64_t sample_draws = -1, sample_kept = -1;
     double sample_ms = -1.0;
     hipEvent_t smp_ev0 = nullptr, smp_ev1 = nullptr;
+    // the last spk_block_profile (spk_block.hip): ordinals its count pass enumerated (-1: none, or it failed), HIP-event
+    // milliseconds of its key-level part and of its enumeration (timing on, else -1); its buffers and events live for
+    // the call only.  profile_cut: the largest-blocks step sorts only the blocks of the top bins (0: every block)
+    int64_t profile_ordinals = -1;
+    double profile_key_ms = -1.0, profile_enum_ms = -1.0;
+    bool profile_cut = true;
     // the (value, pattern) runs of the last tf scale pass over a device-id column, reused by its sum pass
     spk::DevBuf<unsigned long long> tf_uniq;
     spk::DevBuf<unsigned int> tf_runs, tf_nruns;

@@ -432,22 +432,39 @@ class Job:
         raw_r = -1 if same_raw else self.raw_i64(("key", r, i, "r"), codes[1], codes[1] >= 0)
         return (raw_l, raw_r, 0, -1, 0, -1)
 
-    def block(self, rules: List[str]):
-        import time
-        t_start = time.perf_counter()
+    def _set_rule_keys(self, specs):
+        """The blocking keys of the compiled rules `specs` on the device (no rules: one constant key, the
+        cartesian block); returns each rule's symmetric flag."""
         n0, nr = len(self.inputs[0]), len(self.inputs[self.r_side()])
         symmetric = []
-        if not rules:
+        if not specs:
             self.ctx.table_set_key(0, 0, 0, np.zeros(n0, dtype=np.int64))
             self.ctx.table_set_key(self.r_side(), 0, 1, np.zeros(nr, dtype=np.int64))
             symmetric = [1]
-        # rules with a residual predicate (`l.a = r.a and abs(l.x - r.x) < 5`): the whole rule as a hidden device
-        # program per such rule (compiler.compile_rules); none: today's spk_block path
-        specs, rule_program, hidden = compile_rules(list(rules), self.schema)
         for r, spec in enumerate(specs):
             terms = [self._term(r, i, lexpr, rexpr, lexpr == rexpr) for i, (lexpr, rexpr) in enumerate(spec.terms)]
             self.ctx.key_build(r, terms)
             symmetric.append(1 if spec.symmetric else 0)
+        return symmetric
+
+    def profile_rules(self, specs, max_enumerate: int = 0, largest_by: int = N.LARGEST_BY_CANDIDATES, limit: int = 5):
+        """Context.block_profile over the compiled rules `specs` (compiler.compile_rule; none: the cartesian block),
+        whose keys are built here: what blocking on them would cost, without a pair set.  A rule with a residual
+        predicate is profiled on its key terms; like spk_block_residual's enumeration it does not exclude later
+        rules' candidates.  Always the whole job (shard 0 of 1)."""
+        symmetric = self._set_rule_keys(specs)
+        rule_program = [0 if s.residual is not None else -1 for s in specs] or [-1]
+        return self.ctx.block_profile(N.LINK_TYPES[self.link_type], symmetric, rule_program, 0, 1, max_enumerate,
+                                      largest_by, limit)
+
+    def block(self, rules: List[str]):
+        import time
+        t_start = time.perf_counter()
+        n0 = len(self.inputs[0])
+        # rules with a residual predicate (`l.a = r.a and abs(l.x - r.x) < 5`): the whole rule as a hidden device
+        # program per such rule (compiler.compile_rules); none: today's spk_block path
+        specs, rule_program, hidden = compile_rules(list(rules), self.schema)
+        symmetric = self._set_rule_keys(specs)
         if rules and self.cluster:
             # rows of a block become contiguous: the comparison pass reads a block's records from a few
             # cache lines.  The pair set and its ordinal order do not change (blocking sorts by key, rank).
