@@ -68,7 +68,7 @@ int spk_ctx_lds_per_block(spk_ctx *ctx, int *out);
  * numeric values; row permutations, ranks, blocking keys), [2] filter row images, [3] candidate pairs (row
  * indices, rule-view positions and rows), [4] comparison codes, [5] comparison work lists (filter lists,
  * exact / slow lists, region counts), [6] EM, scoring and tf state, the last selection (spk_select, spk_select_best) and the last
- * components' labels (spk_components*), [7] the sum.  For sizing a share of a
+ * components' labels (spk_components*), the last sweep with its metrics (spk_components_sweep*), [7] the sum.  For sizing a share of a
  * job against a device's memory (there is no reference counterpart: Spark spills). */
 int spk_ctx_memory(spk_ctx *ctx, int64_t *out8);
 
@@ -610,6 +610,69 @@ int spk_components_copy(spk_ctx *ctx, int64_t start, int64_t count, uint32_t *ou
  * launches, the cluster count; the host round trip after each round is not in it), -1 otherwise. */
 int spk_components_info(spk_ctx *ctx, int64_t *out_n_nodes, int64_t *out_n_edges, int *out_rounds, double *out_ms);
 int spk_components_release(spk_ctx *ctx);
+
+/* ---- clusters at several thresholds in one pass, and their metrics (no counterpart in the reference release, whose
+ *      users loop connectedComponents over df_e.filter(...) and groupBy the result; later releases:
+ *      cluster_pairwise_predictions_at_multiple_thresholds, compute_graph_metrics) ---- */
+#define SPK_SEL_ALL (-1)            /* every survivor of the selection, whatever its score */
+#define SPK_SWEEP_MAX_LEVELS 32
+/* L = n_thresholds levels of labels over the survivors of the last spk_select*: level k's edges are the survivors
+ * whose score -- `field`: SPK_SEL_MP (the selection's match_probability) or SPK_SEL_TF_MP (its
+ * tf_adjusted_match_prob) -- is > thresholds[k], the strict test of SPK_SEL_GT on the same doubles; a NaN score is in
+ * no level.  field SPK_SEL_ALL: n_thresholds must be 0, L = 1 and every survivor is an edge.  thresholds are strictly
+ * descending and not NaN (+-inf are legal), 1..SPK_SWEEP_MAX_LEVELS of them: anything else is SPK_E_INVALID.
+ * label_k[v] is the smallest node id of v's component at level k, node ids as spk_components defines them, so level
+ * k equals, bit for bit, what spk_select(score > thresholds[k]) followed by spk_components gives; it does not depend
+ * on the algorithm, the edge order, the launch shape or the arrival order of the atomics.  The edge sets are nested,
+ * so each level starts from the previous level's labels and hooks only the edges that are new at it (plus, per node,
+ * the edge to its previous label).  out_n_edges[k] is cumulative (the edges of level k), out_n_clusters[k] counts the
+ * nodes with label_k[v] == v, out_rounds[k] the rounds level k ran (0: no new edge).  SPK_E_STATE: the cases of
+ * spk_components; SPK_SEL_MP on a selection made without m / u; SPK_SEL_TF_MP on one not made by spk_select_tf*.
+ * SPK_E_LIMIT: as spk_components, per level.  The sweep is a value of its own: it holds L x n_nodes labels and the
+ * edges bucketed by level (8 bytes each, kept for spk_cluster_metrics), counted under [6] of spk_ctx_memory; it
+ * needs the selection only while it is built, and stays until the next spk_components_sweep*, its release, or a
+ * change of the tables (spk_table_create, spk_cluster).  spk_components* and the sweep do not disturb each other's
+ * result; a failing call leaves no sweep.  Reads the selection and the tables' permutations only: scores, tf state,
+ * EM state, the selection and the labels of spk_components are not touched. */
+int spk_components_sweep(spk_ctx *ctx, int field /* SPK_SEL_MP | SPK_SEL_TF_MP | SPK_SEL_ALL */, int n_thresholds,
+                         const double *thresholds, int64_t *out_n_nodes, int64_t *out_n_edges /* [L] */,
+                         int64_t *out_n_clusters /* [L] */, int *out_rounds /* [L] */);
+/* The same over host edges u[i] -- v[i] with ids in [0, n_nodes) and a score each (n_thresholds = 0: as SPK_SEL_ALL,
+ * score may be NULL, a NaN score is then an edge too).  Self-loops, repeated edges and both orientations are legal; an
+ * id >= n_nodes in an edge of some level is SPK_E_INVALID. */
+int spk_components_sweep_edges(spk_ctx *ctx, int64_t n_nodes, int64_t n_edges, const uint32_t *u, const uint32_t *v,
+                               const double *score, int n_thresholds, const double *thresholds,
+                               int64_t *out_n_edges /* [L] */, int64_t *out_n_clusters /* [L] */,
+                               int *out_rounds /* [L] */);
+/* Labels of nodes [start, start + count) at `level` of the last sweep (SPK_E_STATE: none; SPK_E_INVALID: a level or
+ * range outside it). */
+int spk_components_sweep_copy(spk_ctx *ctx, int level, int64_t start, int64_t count, uint32_t *out_label);
+/* The last sweep: levels, nodes, edges of its last level (-1 each: none), and with timing on the device milliseconds
+ * of its kernels (edge build, level assignment and bucketing, every level's label copy, rounds and cluster count; the
+ * host round trip after each round is not in it), -1 otherwise. */
+int spk_components_sweep_info(spk_ctx *ctx, int *out_levels, int64_t *out_n_nodes, int64_t *out_n_edges, double *out_ms);
+int spk_components_sweep_release(spk_ctx *ctx);
+/* Which edges a level's rounds hook (both give the same labels; for A/B runs): 0 (default) the edges that are new at
+ * the level, plus for every node the edge to its label at the previous level; 1 every edge of the level. */
+int spk_components_sweep_set_mode(spk_ctx *ctx, int mode);
+
+/* Metrics of one level of the last sweep, integer counting on the device, exact and repeatable.  degree[v] counts
+ * the level's edges incident to v: an edge u -- v adds 1 to each end, a self-loop of host edges 2, a repeated edge
+ * counts each time (a selection has neither).  The per-cluster arrays are indexed by node id, meaningful at the roots
+ * (label[v] == v) and 0 elsewhere: size = nodes of the cluster, degree_sum = the sum of its degrees (twice its
+ * edges), max_degree = its largest degree.  out3 = clusters of >= 2 nodes, nodes in them, the largest cluster's
+ * nodes (0 without nodes).  The arrays (20 bytes per node, under [6] of spk_ctx_memory) describe one level at a time:
+ * they are recomputed by every call and freed with the sweep.  SPK_E_STATE without a sweep, SPK_E_INVALID for a
+ * level outside it. */
+int spk_cluster_metrics(spk_ctx *ctx, int level, int64_t *out3);
+/* Nodes [start, start + count) of the last spk_cluster_metrics; any out may be NULL. */
+int spk_cluster_metrics_copy(spk_ctx *ctx, int64_t start, int64_t count, uint32_t *out_degree, uint32_t *out_size,
+                             uint64_t *out_degree_sum, uint32_t *out_max_degree);
+/* The edge pass of spk_cluster_metrics (both give the same counts; for A/B runs): 1 (default) the lanes of a wave that
+ * share the first lane's end are counted in the wave and issue one add; 0 one add per edge end. */
+int spk_cluster_metrics_set_mode(spk_ctx *ctx, int mode);
+/* The level of the last spk_cluster_metrics (-1: none) and, with timing on, the milliseconds of its kernels. */
+int spk_cluster_metrics_info(spk_ctx *ctx, int *out_level, double *out_ms);
 
 /* ---- pairs against labels (no counterpart in the reference release; later releases:
  *      truth_space_table_from_labels_column, estimate_m_from_label_column) ---- */

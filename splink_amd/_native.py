@@ -39,6 +39,8 @@ SELECT_TERM_DTYPE = np.dtype([("field", "<i4"), ("col", "<i4"), ("op", "<i4"), (
 assert SELECT_TERM_DTYPE.itemsize == 24
 SEL_MP, SEL_GAMMA = 0, 1  # SPK_SEL_MP, SPK_SEL_GAMMA
 SEL_TF_MP = 2  # SPK_SEL_TF_MP: tf_adjusted_match_prob (select_tf / select_tf_columns only)
+SEL_ALL = -1  # SPK_SEL_ALL: every survivor, whatever its score (components_sweep only)
+SWEEP_MAX_LEVELS = 32  # SPK_SWEEP_MAX_LEVELS
 SEL_OP = {"<": 0, "<=": 1, ">": 2, ">=": 3, "=": 4, "!=": 5, "is null": 6, "is not null": 7}  # SPK_SEL_LT ..
 SELECT_MAX_TERMS = 8  # SPK_SELECT_MAX_TERMS
 BEST_L, BEST_R, BEST_EITHER, BEST_MUTUAL = 0, 1, 2, 3  # SPK_BEST_L .. SPK_BEST_MUTUAL (select_best's modes)
@@ -75,6 +77,10 @@ EXPORTS = [
     "spk_select_tf", "spk_select_tf_columns", "spk_select_copy_tf",
     "spk_select_best", "spk_select_best_info",
     "spk_components", "spk_components_edges", "spk_components_copy", "spk_components_info", "spk_components_release",
+    "spk_components_sweep", "spk_components_sweep_edges", "spk_components_sweep_copy", "spk_components_sweep_info",
+    "spk_components_sweep_release", "spk_components_sweep_set_mode",
+    "spk_cluster_metrics", "spk_cluster_metrics_copy", "spk_cluster_metrics_info",
+    "spk_cluster_metrics_set_mode",
     "spk_label_histogram", "spk_label_info",
     "spk_pairs_sample", "spk_pairs_sample_info",
     "spk_block_profile", "spk_block_profile_info", "spk_block_profile_set_cut",
@@ -775,6 +781,99 @@ class Context:
 
     def components_release(self):
         check(self._lib.spk_components_release(self._h), "spk_components_release")
+
+    # ---- clusters at several thresholds, and their metrics ------------------------------------
+    @staticmethod
+    def _sweep_thresholds(thresholds):
+        return np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)  # the library validates them
+
+    def components_sweep(self, field: int, thresholds):
+        """spk_components_sweep over the last select's survivors: labels at every threshold (strictly descending) of
+        the score `field` (SEL_MP, SEL_TF_MP; SEL_ALL with no thresholds: one level of every survivor).  Returns
+        (n_nodes, n_edges int64 [L] cumulative, n_clusters int64 [L], rounds int32 [L])."""
+        t = self._sweep_thresholds(thresholds)
+        L = max(len(t), 1)
+        n = ctypes.c_int64(0)
+        e, c, r = np.zeros(L, dtype=np.int64), np.zeros(L, dtype=np.int64), np.zeros(L, dtype=np.int32)
+        check(self._lib.spk_components_sweep(self._h, ctypes.c_int(int(field)), ctypes.c_int(len(t)),
+                                             _ptr(t) if len(t) else ctypes.c_void_p(0), ctypes.byref(n), _ptr(e),
+                                             _ptr(c), _ptr(r)), "spk_components_sweep")
+        return n.value, e, c, r
+
+    def components_sweep_edges(self, n_nodes: int, u, v, score, thresholds):
+        """spk_components_sweep_edges: the same over host edges u[i] -- v[i] with a score each; no thresholds (score
+        may be None): one level of every edge.  Returns (n_edges [L], n_clusters [L], rounds [L])."""
+        u = np.ascontiguousarray(u, dtype=np.uint32)
+        v = np.ascontiguousarray(v, dtype=np.uint32)
+        t = self._sweep_thresholds(thresholds)
+        if u.shape != v.shape or u.ndim != 1:
+            raise ValueError("components_sweep_edges: u and v must be one-dimensional and of one length")
+        if score is not None:
+            score = np.ascontiguousarray(score, dtype=np.float64)
+            if score.shape != u.shape:
+                raise ValueError("components_sweep_edges: one score per edge")
+        elif len(t):
+            raise ValueError("components_sweep_edges: thresholds need scores")
+        L = max(len(t), 1)
+        e, c, r = np.zeros(L, dtype=np.int64), np.zeros(L, dtype=np.int64), np.zeros(L, dtype=np.int32)
+        nul = ctypes.c_void_p(0)
+        check(self._lib.spk_components_sweep_edges(
+            self._h, ctypes.c_int64(n_nodes), ctypes.c_int64(len(u)), _ptr(u) if len(u) else nul,
+            _ptr(v) if len(v) else nul, _ptr(score) if score is not None and len(u) else nul, ctypes.c_int(len(t)),
+            _ptr(t) if len(t) else nul, _ptr(e), _ptr(c), _ptr(r)), "spk_components_sweep_edges")
+        return e, c, r
+
+    def components_sweep_copy(self, level: int, start: int, count: int) -> np.ndarray:
+        """Labels (uint32) of nodes [start, start + count) at `level` of the last sweep."""
+        out = np.empty(max(count, 0), dtype=np.uint32)
+        check(self._lib.spk_components_sweep_copy(self._h, ctypes.c_int(level), ctypes.c_int64(start),
+                                                  ctypes.c_int64(count), _ptr(out) if count > 0 else ctypes.c_void_p(0)),
+              "spk_components_sweep_copy")
+        return out
+
+    def components_sweep_info(self):
+        """(levels, nodes, edges of the last level of the last sweep or -1 each, ms of its kernels with timing on or -1)."""
+        lv = ctypes.c_int(-1)
+        n = ctypes.c_int64(-1)
+        e = ctypes.c_int64(-1)
+        ms = ctypes.c_double(-1.0)
+        check(self._lib.spk_components_sweep_info(self._h, ctypes.byref(lv), ctypes.byref(n), ctypes.byref(e),
+                                                  ctypes.byref(ms)), "spk_components_sweep_info")
+        return lv.value, n.value, e.value, ms.value
+
+    def components_sweep_release(self):
+        check(self._lib.spk_components_sweep_release(self._h), "spk_components_sweep_release")
+
+    def components_sweep_set_mode(self, mode: int):
+        """0 (default): a level hooks its new edges and a star edge per node; 1: every edge up to the level (A/B)."""
+        check(self._lib.spk_components_sweep_set_mode(self._h, ctypes.c_int(int(mode))), "spk_components_sweep_set_mode")
+
+    def cluster_metrics(self, level: int):
+        """spk_cluster_metrics of one level of the last sweep: (clusters of >= 2 nodes, nodes in them, largest cluster)."""
+        out = np.zeros(3, dtype=np.int64)
+        check(self._lib.spk_cluster_metrics(self._h, ctypes.c_int(int(level)), _ptr(out)), "spk_cluster_metrics")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def cluster_metrics_copy(self, start: int, count: int):
+        """Nodes [start, start + count) of the last cluster_metrics: (degree uint32, size uint32, degree_sum uint64,
+        max_degree uint32); the last three are per cluster, at its root (label[v] == v), 0 elsewhere."""
+        k = max(count, 0)
+        d, s, m = np.empty(k, dtype=np.uint32), np.empty(k, dtype=np.uint32), np.empty(k, dtype=np.uint32)
+        ds = np.empty(k, dtype=np.uint64)
+        check(self._lib.spk_cluster_metrics_copy(self._h, ctypes.c_int64(start), ctypes.c_int64(count), _ptr(d), _ptr(s),
+                                                 _ptr(ds), _ptr(m)), "spk_cluster_metrics_copy")
+        return d, s, ds, m
+
+    def cluster_metrics_set_mode(self, mode: int):
+        """1 (default): the edge pass counts the lanes sharing the wave's first end; 0: one add per edge end (A/B)."""
+        check(self._lib.spk_cluster_metrics_set_mode(self._h, ctypes.c_int(int(mode))), "spk_cluster_metrics_set_mode")
+
+    def cluster_metrics_info(self):
+        """(level of the last cluster_metrics or -1, ms of its kernels with timing on or -1)."""
+        lv = ctypes.c_int(-1)
+        ms = ctypes.c_double(-1.0)
+        check(self._lib.spk_cluster_metrics_info(self._h, ctypes.byref(lv), ctypes.byref(ms)), "spk_cluster_metrics_info")
+        return lv.value, ms.value
 
     # ---- pairs against labels -----------------------------------------------------------------
     def label_histogram(self, ids0, ids1=None, lam=None, one_minus=None, m=None, u=None):

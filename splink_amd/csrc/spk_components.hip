@@ -30,6 +30,28 @@
 // same label is skipped after two loads, and before the atomic the target word is read again past the L1 (an
 // agent-scope load) and the atomic is left out when the word is already as low.  Rounds on the test graphs, emulated
 // on the host with every load as stale as it can be (tools/emulate_components.py): DESIGN.md.
+//
+// Labels at several thresholds (spk_components_sweep*; the reference release has no counterpart, later releases have
+// cluster_pairwise_predictions_at_multiple_thresholds and compute_graph_metrics).  With descending thresholds the
+// edge sets are nested, so level k's components are unions of level k - 1's.  The edges are given a level each
+// (k_sw_level) and bucketed by it (k_sw_scatter), every level's range starting at a multiple of 4 edges -- k_cc_hook
+// loads 16 bytes per lane from the start of the range it is given -- and padded with the self-loop (0, 0), which
+// cc_hook_edge skips.  Level k then copies level k - 1's final labels into its own array (level 0: k_cc_init) and
+// runs the round loop above over an edge set E_k = the edges that are new at level k, plus for every node v the star
+// edge (v, label_{k-1}[v]), hooked by the jump launch, which visits every node anyway (k_cc_jump_star).  The argument
+// above applies word for word:
+//   start state: label_{k-1}[v] is written by a copy in which nothing else touches the word, it is an id of v's
+//                level-(k-1) component, which lies inside v's level-k component, and label_{k-1}[v] <= v: invariants
+//                (1) and (2) hold at the start as they do after k_cc_init;
+//   spanning:    the star edges connect every level-(k-1) component (each node to its smallest id), and the new edges
+//                connect those components into level k's, so E_k spans every component of level k;
+//   quiet round: it wrote nothing, so every load saw the final array: every edge of E_k joins nodes with one common
+//                label, hence all nodes of a level-k component carry one label; every label is a root, a root is <=
+//                every node that carries it and is a member, so it is the component's smallest id.
+// The other variant (spk_components_sweep_set_mode 1) hooks every edge up to the level with the plain jump; it is
+// correct by the same argument with E_k = all edges of level k.  Measured against each other: DESIGN.md.
+// A level without new edges runs no round.  The order of the edges inside a level's range depends on the arrival
+// order of k_sw_scatter's atomics and varies from run to run; nothing observable depends on it.
 #include <algorithm>
 
 #include "spk_internal.h"
@@ -240,6 +262,344 @@ static int cc_events(spk_ctx *ctx) {
     return SPK_OK;
 }
 
+// ---- the sweep: labels at several thresholds ------------------------------------------------------------------------
+constexpr int SW_BUCKETS = SPK_SWEEP_MAX_LEVELS + 1;  // the levels, and "in no level"
+
+// lev[i] = the first level whose threshold edge i's score exceeds (the thresholds descend, so the edge is in every
+// later level too), L for an edge of no level (a NaN, or a score <= every threshold); hist[b] += the edges of bucket b.
+// The score is mpat[code[i]] (a selection's match_probability), score[i], or absent (L = 1, every edge in level 0).
+__global__ __launch_bounds__(CC_THREADS) void k_sw_level(int64_t n_edges, const uint32_t *__restrict__ code,
+                                                         const double *__restrict__ mpat,
+                                                         const double *__restrict__ score, int L,
+                                                         const double *__restrict__ thr, uint8_t *__restrict__ lev,
+                                                         unsigned long long *hist) {
+    __shared__ unsigned long long s_cnt[SW_BUCKETS];
+    if (threadIdx.x < SW_BUCKETS) s_cnt[threadIdx.x] = 0ull;
+    __syncthreads();
+    const int64_t step = (int64_t)gridDim.x * CC_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x; i < n_edges; i += step) {
+        int b = 0;
+        if (mpat || score) {
+            // code[i] < n_patterns without a guard here: spk_select* keeps only pairs whose code its pattern pass
+            // checked, and spk_select_best copies those codes (k_select_decode reads mpat the same way)
+            const double s = mpat ? mpat[code[i]] : score[i];
+            b = L;
+            for (int k = L - 1; k >= 0; --k)
+                if (s > thr[k]) b = k;
+        }
+        lev[i] = (uint8_t)b;
+        (void)atomicAdd(&s_cnt[b], 1ull);
+    }
+    __syncthreads();
+    if (threadIdx.x < SW_BUCKETS && s_cnt[threadIdx.x])
+        (void)__hip_atomic_fetch_add(hist + threadIdx.x, s_cnt[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Edge i goes to the next free place of its level's range: cursor[b] starts at the range's first place, a workgroup
+// takes the places of its 256 edges with one add per level, and the edges rank themselves inside that in LDS.  The
+// order inside a range therefore varies from run to run; nothing observable depends on it (labels and metrics are
+// functions of the edge multiset).  An edge of no level is dropped.  Every place written lies in [off[b], off[b] +
+// cnt[b]): the counts come from the same lev array.
+__global__ __launch_bounds__(CC_THREADS) void k_sw_scatter(int64_t n_edges, int L, const uint8_t *__restrict__ lev,
+                                                           const uint32_t *__restrict__ u, const uint32_t *__restrict__ v,
+                                                           unsigned long long *cursor, uint32_t *__restrict__ ou,
+                                                           uint32_t *__restrict__ ov) {
+    __shared__ unsigned int s_cnt[SW_BUCKETS];
+    __shared__ unsigned long long s_base[SW_BUCKETS];
+    const int64_t n_chunks = (n_edges + CC_THREADS - 1) / CC_THREADS;
+    for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        const int64_t i = c * CC_THREADS + threadIdx.x;
+        const int b = i < n_edges ? (int)lev[i] : L;
+        if (threadIdx.x < SW_BUCKETS) s_cnt[threadIdx.x] = 0u;
+        __syncthreads();
+        const unsigned int rank = b < L ? atomicAdd(&s_cnt[b], 1u) : 0u;
+        __syncthreads();
+        if ((int)threadIdx.x < L && s_cnt[threadIdx.x])
+            s_base[threadIdx.x] = __hip_atomic_fetch_add(cursor + threadIdx.x, (unsigned long long)s_cnt[threadIdx.x],
+                                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (b < L) {
+            const size_t q = (size_t)(s_base[b] + rank);
+            ou[q] = u[i];
+            ov[q] = v[i];
+        }
+        __syncthreads();  // s_cnt and s_base are rewritten by the next chunk
+    }
+}
+
+// k_cc_jump of a level k > 0, which also hooks, for every node v, the star edge (v, prev[v]), prev = the final labels
+// of level k - 1 (read only here).
+__global__ __launch_bounds__(CC_THREADS) void k_cc_jump_star(int64_t n_nodes, uint32_t *label,
+                                                             const uint32_t *__restrict__ prev, unsigned int *flags) {
+    bool changed = false, bad = false;
+    const int64_t step = (int64_t)gridDim.x * CC_THREADS;
+    for (int64_t v = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x; v < n_nodes; v += step) {
+        const uint32_t p = label[v];
+        if ((int64_t)p != v) {
+            const uint32_t r = cc_climb(label, p);
+            if (r < p) {
+                changed = true;
+                (void)__hip_atomic_fetch_min(label + v, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        cc_hook_edge<false>(label, n_nodes, (uint32_t)v, prev[v], changed, bad);
+    }
+    cc_raise(flags, changed, false);
+}
+
+// ---- metrics of one level ------------------------------------------------------------------------------------------
+// degree[x] += 1 for one end x per active lane.  AGG: the lanes whose end equals that of the wave's first active lane
+// issue one add of their count (the lowest of them does); the others add on their own.
+template <bool AGG>
+__device__ inline void cm_degree_add(uint32_t *degree, uint32_t x) {
+    if (AGG) {
+        const uint32_t x0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)x);
+        const unsigned long long same = __ballot(x == x0);
+        if (x == x0) {
+            if ((int)(threadIdx.x & 63) == __ffsll((long long)same) - 1)
+                (void)__hip_atomic_fetch_add(degree + (size_t)x0, (uint32_t)__popcll(same), __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT);
+            return;
+        }
+    }
+    (void)__hip_atomic_fetch_add(degree + (size_t)x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Two adds per edge.  AGG (the default; spk_cluster_metrics_set_mode 0 turns it off) counts the lanes that share the
+// first lane's end inside the wave before the add: 0.27 -> 0.18 ms for the whole call on the hub graph, 11.6 -> 0.41 ms
+// on one star of 10^6 leaves, no difference on the random graph.
+template <bool AGG>
+__global__ __launch_bounds__(CC_THREADS) void k_cm_degree(int64_t n_edges, const uint32_t *__restrict__ eu,
+                                                          const uint32_t *__restrict__ ev, uint32_t *degree) {
+    const int64_t step = (int64_t)gridDim.x * CC_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x; i < n_edges; i += step) {
+        cm_degree_add<AGG>(degree, eu[i]);
+        cm_degree_add<AGG>(degree, ev[i]);
+    }
+}
+
+// Per node v: size[label[v]] += 1, degree_sum[label[v]] += degree[v], max_degree[label[v]] = max(., degree[v]).
+// Consecutive nodes often share a label (one cluster of 10^6 records would put 3 x 10^6 atomics on three words), so
+// the lanes whose label equals that of the wave's first node are reduced in the wave and their leader issues the three
+// atomics; the other lanes issue their own.  Every trip of the loop is taken by the whole wave (the shuffles need it).
+__global__ __launch_bounds__(CC_THREADS) void k_cm_nodes(int64_t n_nodes, const uint32_t *__restrict__ label,
+                                                         const uint32_t *__restrict__ degree, uint32_t *size,
+                                                         unsigned long long *degree_sum, uint32_t *max_degree) {
+    const int64_t step = (int64_t)gridDim.x * CC_THREADS;
+    const int lane = threadIdx.x & 63;
+    for (int64_t base = (int64_t)blockIdx.x * CC_THREADS + (threadIdx.x & ~63); base < n_nodes; base += step) {
+        const int64_t v = base + lane;
+        const bool valid = v < n_nodes;  // lane 0 always is
+        const uint32_t l = valid ? label[v] : 0u, d = valid ? degree[v] : 0u;
+        const uint32_t l0 = (uint32_t)__shfl((int)l, 0, 64);
+        const bool with_first = valid && l == l0;
+        unsigned int cnt = with_first ? 1u : 0u, mx = with_first ? d : 0u;
+        unsigned long long sum = with_first ? (unsigned long long)d : 0ull;
+        for (int off = 32; off > 0; off >>= 1) {
+            cnt += __shfl_down(cnt, off, 64);
+            sum += __shfl_down(sum, off, 64);
+            const unsigned int o = __shfl_down(mx, off, 64);
+            mx = o > mx ? o : mx;
+        }
+        if (lane == 0) {
+            (void)__hip_atomic_fetch_add(size + (size_t)l0, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (sum) (void)__hip_atomic_fetch_add(degree_sum + (size_t)l0, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (mx) (void)__hip_atomic_fetch_max(max_degree + (size_t)l0, mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else if (valid && !with_first) {
+            (void)__hip_atomic_fetch_add(size + (size_t)l, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (d) {
+                (void)__hip_atomic_fetch_add(degree_sum + (size_t)l, (unsigned long long)d, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT);
+                (void)__hip_atomic_fetch_max(max_degree + (size_t)l, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
+
+// out[0] += the roots with size >= 2, out[1] += their sizes, out[2] = max(out[2], size) over every root
+__global__ __launch_bounds__(CC_THREADS) void k_cm_scalars(int64_t n_nodes, const uint32_t *__restrict__ label,
+                                                           const uint32_t *__restrict__ size, unsigned long long *out) {
+    unsigned long long multi = 0, nodes = 0, largest = 0;
+    const int64_t step = (int64_t)gridDim.x * CC_THREADS;
+    for (int64_t v = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x; v < n_nodes; v += step) {
+        if ((int64_t)label[v] != v) continue;
+        const unsigned long long s = size[v];
+        largest = s > largest ? s : largest;
+        if (s >= 2) {
+            ++multi;
+            nodes += s;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        multi += __shfl_down(multi, off, 64);
+        nodes += __shfl_down(nodes, off, 64);
+        const unsigned long long o = __shfl_down(largest, off, 64);
+        largest = o > largest ? o : largest;
+    }
+    if ((threadIdx.x & 63) == 0 && largest) {
+        if (multi) (void)__hip_atomic_fetch_add(out, multi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (nodes) (void)__hip_atomic_fetch_add(out + 1, nodes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_max(out + 2, largest, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// HIP-event time of the launches between open() and close(), summed; close() also synchronises the stream.
+struct CcTimer {
+    spk_ctx *ctx;
+    double ms = 0.0;
+    bool is_open = false;
+    int open() {
+        if (ctx->timing && !is_open) {
+            SPK_HIP(hipEventRecord(ctx->cc_ev0, ctx->stream));
+            is_open = true;
+        }
+        return SPK_OK;
+    }
+    int close() {
+        if (is_open) SPK_HIP(hipEventRecord(ctx->cc_ev1, ctx->stream));
+        SPK_HIP(hipStreamSynchronize(ctx->stream));
+        if (is_open) {
+            float t = 0.f;
+            SPK_HIP(hipEventElapsedTime(&t, ctx->cc_ev0, ctx->cc_ev1));
+            ms += (double)t;
+            is_open = false;
+        }
+        return SPK_OK;
+    }
+};
+
+// L and the thresholds of a sweep call; `all`: the call has no scores (SPK_SEL_ALL, or host edges without thresholds)
+static int sweep_thresholds(const char *who, bool all, int n_thresholds, const double *thresholds, int *out_levels) {
+    const std::string w(who);
+    if (all) {
+        SPK_REQUIRE(n_thresholds == 0, SPK_E_INVALID, w + ": SPK_SEL_ALL takes no thresholds");
+        *out_levels = 1;
+        return SPK_OK;
+    }
+    SPK_REQUIRE(n_thresholds >= 1 && n_thresholds <= SPK_SWEEP_MAX_LEVELS, SPK_E_INVALID, w + ": 1 to 32 thresholds");
+    SPK_REQUIRE(thresholds, SPK_E_INVALID, w + ": null thresholds");
+    for (int k = 0; k < n_thresholds; ++k) {
+        SPK_REQUIRE(thresholds[k] == thresholds[k], SPK_E_INVALID, w + ": a threshold is NaN");
+        SPK_REQUIRE(k == 0 || thresholds[k] < thresholds[k - 1], SPK_E_INVALID,
+                    w + ": the thresholds must be strictly descending");
+    }
+    *out_levels = n_thresholds;
+    return SPK_OK;
+}
+
+// The sweep of the graph (eu0, ev0) [n_raw] over n_nodes nodes into S, a local of the caller.  The edges' scores are
+// mpat[code[i]], score[i], or absent (L = 1; thresholds is not read then).  T: an event pair, possibly open around the
+// caller's edge build.
+static int build_sweep(spk_ctx *ctx, int64_t n_nodes, int64_t n_raw, const uint32_t *eu0, const uint32_t *ev0,
+                       const uint32_t *code, const double *mpat, const double *score, int L, const double *thresholds,
+                       int bad_code, const char *bad_msg, CcTimer &T, ComponentSweep &S) {
+    hipStream_t st = ctx->stream;
+    DevBuf<uint8_t> lev;
+    DevBuf<unsigned long long> hist;  // [SW_BUCKETS] counts | [SW_BUCKETS] cursors | 1 cluster count
+    DevBuf<double> thr;
+    DevBuf<unsigned int> flags;       // [changed, bad]
+    SPK_TRY(lev.alloc((size_t)n_raw + 1));
+    SPK_TRY(hist.alloc(2 * SW_BUCKETS + 1));
+    SPK_TRY(thr.alloc(SPK_SWEEP_MAX_LEVELS));
+    SPK_TRY(flags.alloc(2));
+    unsigned long long *cursor = hist.p + SW_BUCKETS, *count = hist.p + 2 * SW_BUCKETS;
+    const unsigned raw_grid = cc_grid(ctx, n_raw, CC_THREADS), node_grid = cc_grid(ctx, n_nodes, CC_THREADS);
+    // ---- a level per edge, the levels' counts, their padded ranges
+    unsigned long long h[SW_BUCKETS] = {};
+    if (n_raw > 0) {
+        SPK_TRY(T.open());
+        if (mpat || score) SPK_HIP(hipMemcpyAsync(thr.p, thresholds, (size_t)L * 8, hipMemcpyHostToDevice, st));
+        SPK_HIP(hipMemsetAsync(hist.p, 0, SW_BUCKETS * sizeof(unsigned long long), st));
+        k_sw_level<<<raw_grid, CC_THREADS, 0, st>>>(n_raw, code, mpat, score, L, thr.p, lev.p, hist.p);
+        SPK_HIP(hipGetLastError());
+        SPK_HIP(hipMemcpyAsync(h, hist.p, sizeof(h), hipMemcpyDeviceToHost, st));
+    }
+    SPK_TRY(T.close());  // the thresholds are the caller's: done with them
+    S.levels = L;
+    S.n_nodes = n_nodes;
+    S.off.assign(L + 1, 0);
+    S.cnt.assign(L, 0);
+    S.n_edges.assign(L, 0);
+    S.n_clusters.assign(L, 0);
+    S.rounds.assign(L, 0);
+    unsigned long long start[SW_BUCKETS] = {};
+    for (int k = 0; k < L; ++k) {
+        S.cnt[k] = (int64_t)h[k];
+        S.n_edges[k] = (k ? S.n_edges[k - 1] : 0) + S.cnt[k];
+        S.off[k + 1] = (S.off[k] + S.cnt[k] + CC_VEC - 1) / CC_VEC * CC_VEC;  // k_cc_hook's 16-byte loads start here
+        start[k] = (unsigned long long)S.off[k];
+    }
+    const int64_t n_kept = S.n_edges[L - 1], padded = S.off[L];
+    SPK_TRY(S.eu.alloc((size_t)padded + CC_VEC));
+    SPK_TRY(S.ev.alloc((size_t)padded + CC_VEC));
+    SPK_TRY(S.label.alloc((size_t)L * (size_t)n_nodes + 1));
+    if (n_kept > 0) {
+        SPK_TRY(T.open());
+        // the padding is the self-loop (0, 0), which cc_hook_edge skips (n_kept > 0 with n_nodes = 0 fails its check)
+        SPK_HIP(hipMemsetAsync(S.eu.p, 0, (size_t)padded * 4, st));
+        SPK_HIP(hipMemsetAsync(S.ev.p, 0, (size_t)padded * 4, st));
+        SPK_HIP(hipMemcpyAsync(cursor, start, sizeof(start), hipMemcpyHostToDevice, st));
+        k_sw_scatter<<<raw_grid, CC_THREADS, 0, st>>>(n_raw, L, lev.p, eu0, ev0, cursor, S.eu.p, S.ev.p);
+        SPK_HIP(hipGetLastError());
+        SPK_TRY(T.close());  // `start` is a local: done with it
+    }
+    // ---- level after level
+    const bool prefix = ctx->sweep_mode == 1;
+    for (int k = 0; k < L; ++k) {
+        uint32_t *lab = S.label.p + (size_t)k * (size_t)n_nodes;
+        const uint32_t *prev = k ? lab - (size_t)n_nodes : nullptr;
+        const uint32_t *hu = S.eu.p + (prefix ? 0 : S.off[k]), *hv = S.ev.p + (prefix ? 0 : S.off[k]);
+        const int64_t hn = prefix ? S.off[k] + S.cnt[k] : S.cnt[k];
+        const unsigned hook_grid = cc_grid(ctx, hn, CC_CHUNK);
+        SPK_TRY(T.open());
+        if (!prev) {
+            k_cc_init<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab);
+            SPK_HIP(hipGetLastError());
+        } else if (n_nodes > 0) {
+            SPK_HIP(hipMemcpyAsync(lab, prev, (size_t)n_nodes * 4, hipMemcpyDeviceToDevice, st));
+        }
+        int rounds = 0;
+        bool quiet = S.cnt[k] == 0;  // no new edge: the previous level's labels are this level's
+        while (!quiet) {
+            SPK_REQUIRE(rounds < CC_MAX_ROUNDS, SPK_E_LIMIT, "spk_components_sweep: no fixed point within 256 rounds");
+            SPK_TRY(T.open());
+            SPK_HIP(hipMemsetAsync(flags.p, 0, 2 * sizeof(unsigned int), st));
+            if (rounds == 0) k_cc_hook<true><<<hook_grid, CC_THREADS, 0, st>>>(n_nodes, hn, hu, hv, lab, flags.p);
+            else k_cc_hook<false><<<hook_grid, CC_THREADS, 0, st>>>(n_nodes, hn, hu, hv, lab, flags.p);
+            SPK_HIP(hipGetLastError());
+            if (prev && !prefix) k_cc_jump_star<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab, prev, flags.p);
+            else k_cc_jump<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab, flags.p);
+            SPK_HIP(hipGetLastError());
+            unsigned int f[2] = {0u, 0u};
+            SPK_HIP(hipMemcpyAsync(f, flags.p, sizeof(f), hipMemcpyDeviceToHost, st));
+            SPK_TRY(T.close());
+            ++rounds;
+            SPK_REQUIRE(f[1] == 0u, bad_code, bad_msg);
+            quiet = f[0] == 0u;
+        }
+        SPK_TRY(T.open());
+        SPK_HIP(hipMemsetAsync(count, 0, sizeof(unsigned long long), st));
+        k_cc_count<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab, count);
+        SPK_HIP(hipGetLastError());
+        unsigned long long n_clusters = 0;
+        SPK_HIP(hipMemcpyAsync(&n_clusters, count, sizeof(n_clusters), hipMemcpyDeviceToHost, st));
+        SPK_TRY(T.close());
+        S.n_clusters[k] = (int64_t)n_clusters;
+        S.rounds[k] = rounds;
+    }
+    S.ms = ctx->timing ? T.ms : -1.0;
+    S.valid = true;
+    return SPK_OK;
+}
+
+static void sweep_outputs(const ComponentSweep &S, int64_t *out_n_edges, int64_t *out_n_clusters, int *out_rounds) {
+    for (int k = 0; k < S.levels; ++k) {
+        if (out_n_edges) out_n_edges[k] = S.n_edges[k];
+        if (out_n_clusters) out_n_clusters[k] = S.n_clusters[k];
+        if (out_rounds) out_rounds[k] = S.rounds[k];
+    }
+}
+
 }  // namespace spk
 
 using namespace spk;
@@ -344,5 +704,221 @@ extern "C" int spk_components_release(spk_ctx *ctx) {
     SPK_HIP(hipSetDevice(ctx->device));
     SPK_HIP(hipStreamSynchronize(ctx->stream));
     ctx->comp.clear();
+    return SPK_OK;
+}
+
+// ---- the sweep -------------------------------------------------------------------------------------------------------
+extern "C" int spk_components_sweep(spk_ctx *ctx, int field, int n_thresholds, const double *thresholds,
+                                    int64_t *out_n_nodes, int64_t *out_n_edges, int64_t *out_n_clusters,
+                                    int *out_rounds) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_components_sweep: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    ctx->sweep.clear();  // whatever happens below, the previous sweep is gone
+    SPK_REQUIRE(field == SPK_SEL_MP || field == SPK_SEL_TF_MP || field == SPK_SEL_ALL, SPK_E_INVALID,
+                "spk_components_sweep: field is SPK_SEL_MP, SPK_SEL_TF_MP or SPK_SEL_ALL");
+    int L = 0;
+    SPK_TRY(sweep_thresholds("spk_components_sweep", field == SPK_SEL_ALL, n_thresholds, thresholds, &L));
+    const Selection &S = ctx->sel;
+    SPK_REQUIRE(S.valid, SPK_E_STATE, "spk_components_sweep: no selection (run spk_select)");
+    SPK_REQUIRE(ctx->codes_valid && S.pairs_epoch == ctx->pairs_epoch && S.gamma_seq == ctx->gamma_seq &&
+                    S.fix_seq == ctx->codes_fix_seq,
+                SPK_E_STATE, "spk_components_sweep: the pairs or codes changed since spk_select");
+    SPK_REQUIRE(S.has_rows, SPK_E_STATE, "spk_components_sweep: no pair rows (a loaded gamma table)");
+    SPK_REQUIRE(field != SPK_SEL_MP || S.has_mp, SPK_E_STATE, "spk_components_sweep: spk_select got no m / u");
+    SPK_REQUIRE(field != SPK_SEL_TF_MP || S.has_tf, SPK_E_STATE,
+                "spk_components_sweep: the selection was made without tf tables (spk_select)");
+    const bool two = ctx->link_type == SPK_LINK_ONLY;
+    const Table &t0 = ctx->table[0], &t1 = ctx->table[two ? 1 : 0];
+    SPK_REQUIRE(t0.n >= 0 && t1.n >= 0, SPK_E_STATE, "spk_components_sweep: no tables");
+    const int64_t n_nodes = t0.n + (two ? t1.n : 0), n_edges = S.n;
+    SPK_REQUIRE(n_nodes <= (int64_t)UINT32_MAX, SPK_E_LIMIT, "spk_components_sweep: more than 2^32 - 1 nodes");
+    SPK_TRY(cc_events(ctx));
+    ComponentSweep W;
+    CcTimer T{ctx};
+    DevBuf<uint32_t> eu, ev;
+    SPK_TRY(eu.alloc((size_t)n_edges + 1));
+    SPK_TRY(ev.alloc((size_t)n_edges + 1));
+    if (n_edges > 0) {
+        SPK_TRY(T.open());
+        EdgeArgs A{};
+        A.n_edges = n_edges;
+        A.l = S.l.p;
+        A.r = S.r.p;
+        A.perm0 = t0.perm.p;
+        A.perm1 = t1.perm.p;
+        A.n0 = t0.n;
+        A.n1 = t1.n;
+        A.r_base = two ? (uint32_t)t0.n : 0u;
+        A.u = eu.p;
+        A.v = ev.p;
+        k_cc_edges<<<cc_grid(ctx, n_edges, CC_THREADS), CC_THREADS, 0, ctx->stream>>>(A);
+        SPK_HIP(hipGetLastError());
+    }
+    SPK_TRY(build_sweep(ctx, n_nodes, n_edges, eu.p, ev.p, S.code.p, field == SPK_SEL_MP ? S.mpat.p : nullptr,
+                        field == SPK_SEL_TF_MP ? S.tf_mp.p : nullptr, L, thresholds, SPK_E_STATE,
+                        "spk_components_sweep: a selected pair names a row outside its table", T, W));
+    ctx->sweep = std::move(W);
+    if (out_n_nodes) *out_n_nodes = ctx->sweep.n_nodes;
+    sweep_outputs(ctx->sweep, out_n_edges, out_n_clusters, out_rounds);
+    return SPK_OK;
+}
+
+extern "C" int spk_components_sweep_edges(spk_ctx *ctx, int64_t n_nodes, int64_t n_edges, const uint32_t *u,
+                                          const uint32_t *v, const double *score, int n_thresholds,
+                                          const double *thresholds, int64_t *out_n_edges, int64_t *out_n_clusters,
+                                          int *out_rounds) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_components_sweep_edges: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    ctx->sweep.clear();
+    SPK_REQUIRE(n_nodes >= 0 && n_edges >= 0, SPK_E_INVALID, "spk_components_sweep_edges: negative count");
+    SPK_REQUIRE(n_edges == 0 || (u && v), SPK_E_INVALID, "spk_components_sweep_edges: null edges");
+    SPK_REQUIRE(n_thresholds == 0 || n_edges == 0 || score, SPK_E_INVALID, "spk_components_sweep_edges: null scores");
+    SPK_REQUIRE(n_nodes <= (int64_t)UINT32_MAX, SPK_E_LIMIT, "spk_components_sweep_edges: more than 2^32 - 1 nodes");
+    int L = 0;
+    SPK_TRY(sweep_thresholds("spk_components_sweep_edges", n_thresholds == 0, n_thresholds, thresholds, &L));
+    SPK_TRY(cc_events(ctx));
+    ComponentSweep W;
+    CcTimer T{ctx};
+    DevBuf<uint32_t> eu, ev;
+    DevBuf<double> sc;
+    const bool scored = n_thresholds > 0;
+    SPK_TRY(eu.alloc((size_t)n_edges + 1));
+    SPK_TRY(ev.alloc((size_t)n_edges + 1));
+    SPK_TRY(sc.alloc((size_t)n_edges + 1));
+    if (n_edges > 0) {
+        SPK_HIP(hipMemcpyAsync(eu.p, u, (size_t)n_edges * 4, hipMemcpyHostToDevice, ctx->stream));
+        SPK_HIP(hipMemcpyAsync(ev.p, v, (size_t)n_edges * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (scored) SPK_HIP(hipMemcpyAsync(sc.p, score, (size_t)n_edges * 8, hipMemcpyHostToDevice, ctx->stream));
+        SPK_HIP(hipStreamSynchronize(ctx->stream));  // u / v / score are the caller's: done with them
+    }
+    SPK_TRY(build_sweep(ctx, n_nodes, n_edges, eu.p, ev.p, nullptr, nullptr, scored ? sc.p : nullptr, L, thresholds,
+                        SPK_E_INVALID, "spk_components_sweep_edges: a node id is >= n_nodes", T, W));
+    ctx->sweep = std::move(W);
+    sweep_outputs(ctx->sweep, out_n_edges, out_n_clusters, out_rounds);
+    return SPK_OK;
+}
+
+extern "C" int spk_components_sweep_copy(spk_ctx *ctx, int level, int64_t start, int64_t count, uint32_t *out_label) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_components_sweep_copy: null ctx");
+    const ComponentSweep &W = ctx->sweep;
+    SPK_REQUIRE(W.valid, SPK_E_STATE, "spk_components_sweep_copy: no sweep (run spk_components_sweep)");
+    SPK_REQUIRE(level >= 0 && level < W.levels, SPK_E_INVALID, "spk_components_sweep_copy: level");
+    SPK_REQUIRE(start >= 0 && count >= 0 && start <= W.n_nodes && count <= W.n_nodes - start, SPK_E_INVALID,
+                "spk_components_sweep_copy: range");
+    SPK_REQUIRE(count == 0 || out_label, SPK_E_INVALID, "spk_components_sweep_copy: null out");
+    if (!count) return SPK_OK;
+    SPK_HIP(hipSetDevice(ctx->device));
+    SPK_HIP(hipMemcpyAsync(out_label, W.label.p + (size_t)level * (size_t)W.n_nodes + (size_t)start, (size_t)count * 4,
+                           hipMemcpyDeviceToHost, ctx->stream));
+    SPK_HIP(hipStreamSynchronize(ctx->stream));
+    return SPK_OK;
+}
+
+extern "C" int spk_components_sweep_info(spk_ctx *ctx, int *out_levels, int64_t *out_n_nodes, int64_t *out_n_edges,
+                                         double *out_ms) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_components_sweep_info: null ctx");
+    const ComponentSweep &W = ctx->sweep;
+    if (out_levels) *out_levels = W.valid ? W.levels : -1;
+    if (out_n_nodes) *out_n_nodes = W.valid ? W.n_nodes : -1;
+    if (out_n_edges) *out_n_edges = W.valid ? W.n_edges[W.levels - 1] : -1;
+    if (out_ms) *out_ms = W.valid ? W.ms : -1.0;
+    return SPK_OK;
+}
+
+extern "C" int spk_components_sweep_release(spk_ctx *ctx) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_components_sweep_release: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    SPK_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->sweep.clear();
+    return SPK_OK;
+}
+
+extern "C" int spk_components_sweep_set_mode(spk_ctx *ctx, int mode) {
+    SPK_REQUIRE(ctx && (mode == 0 || mode == 1), SPK_E_INVALID, "spk_components_sweep_set_mode: mode 0 or 1");
+    ctx->sweep_mode = mode;
+    return SPK_OK;
+}
+
+// ---- metrics of one level --------------------------------------------------------------------------------------------
+extern "C" int spk_cluster_metrics(spk_ctx *ctx, int level, int64_t *out3) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_cluster_metrics: null ctx");
+    ComponentSweep &W = ctx->sweep;
+    SPK_REQUIRE(W.valid, SPK_E_STATE, "spk_cluster_metrics: no sweep (run spk_components_sweep)");
+    SPK_REQUIRE(level >= 0 && level < W.levels, SPK_E_INVALID, "spk_cluster_metrics: level");
+    SPK_HIP(hipSetDevice(ctx->device));
+    W.m_level = -1;  // whatever happens below, the previous level's metrics are gone
+    W.m_ms = -1.0;
+    SPK_TRY(cc_events(ctx));
+    hipStream_t st = ctx->stream;
+    const int64_t n = W.n_nodes;
+    DevBuf<unsigned long long> out;
+    SPK_TRY(out.alloc(3));
+    SPK_TRY(W.degree.alloc((size_t)n + 1));
+    SPK_TRY(W.size.alloc((size_t)n + 1));
+    SPK_TRY(W.max_degree.alloc((size_t)n + 1));
+    SPK_TRY(W.degree_sum.alloc((size_t)n + 1));
+    CcTimer T{ctx};
+    SPK_TRY(T.open());
+    SPK_HIP(hipMemsetAsync(out.p, 0, 3 * sizeof(unsigned long long), st));
+    SPK_HIP(hipMemsetAsync(W.degree.p, 0, ((size_t)n + 1) * 4, st));
+    SPK_HIP(hipMemsetAsync(W.size.p, 0, ((size_t)n + 1) * 4, st));
+    SPK_HIP(hipMemsetAsync(W.max_degree.p, 0, ((size_t)n + 1) * 4, st));
+    SPK_HIP(hipMemsetAsync(W.degree_sum.p, 0, ((size_t)n + 1) * 8, st));
+    for (int k = 0; k <= level; ++k) {  // a level's range without its padding, whose (0, 0) would count for node 0
+        if (!W.cnt[k]) continue;
+        const unsigned g = cc_grid(ctx, W.cnt[k], CC_THREADS);
+        const uint32_t *eu = W.eu.p + W.off[k], *ev = W.ev.p + W.off[k];
+        if (ctx->metrics_edge_agg) k_cm_degree<true><<<g, CC_THREADS, 0, st>>>(W.cnt[k], eu, ev, W.degree.p);
+        else k_cm_degree<false><<<g, CC_THREADS, 0, st>>>(W.cnt[k], eu, ev, W.degree.p);
+        SPK_HIP(hipGetLastError());
+    }
+    const uint32_t *lab = W.label.p + (size_t)level * (size_t)n;
+    const unsigned node_grid = cc_grid(ctx, n, CC_THREADS);
+    if (n > 0) {
+        k_cm_nodes<<<node_grid, CC_THREADS, 0, st>>>(n, lab, W.degree.p, W.size.p, W.degree_sum.p, W.max_degree.p);
+        SPK_HIP(hipGetLastError());
+        k_cm_scalars<<<node_grid, CC_THREADS, 0, st>>>(n, lab, W.size.p, out.p);
+        SPK_HIP(hipGetLastError());
+    }
+    unsigned long long h[3] = {0, 0, 0};
+    SPK_HIP(hipMemcpyAsync(h, out.p, sizeof(h), hipMemcpyDeviceToHost, st));
+    SPK_TRY(T.close());
+    W.m_level = level;
+    W.m_ms = ctx->timing ? T.ms : -1.0;
+    if (out3)
+        for (int i = 0; i < 3; ++i) out3[i] = (int64_t)h[i];
+    return SPK_OK;
+}
+
+extern "C" int spk_cluster_metrics_copy(spk_ctx *ctx, int64_t start, int64_t count, uint32_t *out_degree,
+                                        uint32_t *out_size, uint64_t *out_degree_sum, uint32_t *out_max_degree) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_cluster_metrics_copy: null ctx");
+    const ComponentSweep &W = ctx->sweep;
+    SPK_REQUIRE(W.valid && W.m_level >= 0, SPK_E_STATE, "spk_cluster_metrics_copy: no metrics (run spk_cluster_metrics)");
+    SPK_REQUIRE(start >= 0 && count >= 0 && start <= W.n_nodes && count <= W.n_nodes - start, SPK_E_INVALID,
+                "spk_cluster_metrics_copy: range");
+    if (!count) return SPK_OK;
+    SPK_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t s = (size_t)start, c = (size_t)count;
+    if (out_degree) SPK_HIP(hipMemcpyAsync(out_degree, W.degree.p + s, c * 4, hipMemcpyDeviceToHost, st));
+    if (out_size) SPK_HIP(hipMemcpyAsync(out_size, W.size.p + s, c * 4, hipMemcpyDeviceToHost, st));
+    if (out_degree_sum) SPK_HIP(hipMemcpyAsync(out_degree_sum, W.degree_sum.p + s, c * 8, hipMemcpyDeviceToHost, st));
+    if (out_max_degree) SPK_HIP(hipMemcpyAsync(out_max_degree, W.max_degree.p + s, c * 4, hipMemcpyDeviceToHost, st));
+    SPK_HIP(hipStreamSynchronize(st));
+    return SPK_OK;
+}
+
+extern "C" int spk_cluster_metrics_set_mode(spk_ctx *ctx, int mode) {
+    SPK_REQUIRE(ctx && (mode == 0 || mode == 1), SPK_E_INVALID, "spk_cluster_metrics_set_mode: mode 0 or 1");
+    ctx->metrics_edge_agg = mode == 1;
+    return SPK_OK;
+}
+
+extern "C" int spk_cluster_metrics_info(spk_ctx *ctx, int *out_level, double *out_ms) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_cluster_metrics_info: null ctx");
+    const ComponentSweep &W = ctx->sweep;
+    if (out_level) *out_level = W.valid ? W.m_level : -1;
+    if (out_ms) *out_ms = W.valid && W.m_level >= 0 ? W.m_ms : -1.0;
     return SPK_OK;
 }

@@ -607,6 +607,7 @@ int spk_table_create(spk_ctx *ctx, int side, int64_t n_rows, int n_cols) {
     t.version = ++ctx->table_epoch;
     ctx->pairs_dropped();
     ctx->comp.clear();  // its node ids named the old tables' rows
+    ctx->sweep.clear();
     return SPK_OK;
 }
 

@@ -3592,7 +3592,9 @@ extern "C" int spk_ctx_memory(spk_ctx *ctx, int64_t *out8) {
            b(ctx->tf_sort) +
            b(ctx->sel.ord) + b(ctx->sel.l) + b(ctx->sel.r) + b(ctx->sel.code) + b(ctx->sel.mpat) +
            b(ctx->sel.tf_mp) + b(ctx->sel.adj) +
-           b(ctx->comp.label);
+           b(ctx->comp.label) +
+           b(ctx->sweep.label) + b(ctx->sweep.eu) + b(ctx->sweep.ev) + b(ctx->sweep.degree) + b(ctx->sweep.size) +
+           b(ctx->sweep.max_degree) + b(ctx->sweep.degree_sum);
     for (int i = 0; i < 7; ++i) m[7] += m[i];
     for (int i = 0; i < 8; ++i) out8[i] = m[i];
     return SPK_OK;

@@ -758,6 +758,7 @@ int spk_cluster(spk_ctx *ctx, int32_t *out_perm0, int32_t *out_perm1) {
     }
     ctx->pairs_dropped();
     ctx->comp.clear();  // spk_table_create's reason: the job's tables changed
+    ctx->sweep.clear();
     return SPK_OK;
 }
 

@@ -279,6 +279,31 @@ struct Components {
     void clear() { *this = Components(); }
 };
 
+// The labels of the last spk_components_sweep* (spk_components.hip): level k's labels are those of the graph whose edges
+// are the selection's survivors (or the host edges) with score > thresholds[k].  A value of its own, independent of
+// `Components`: built in a local and moved into the context, so a failing call leaves none.  It keeps the edges
+// bucketed by level (8 bytes per edge), so spk_cluster_metrics can run later without the selection; the metrics of
+// one level at a time live in it too (recomputed per call, freed with it).
+struct ComponentSweep {
+    bool valid = false;
+    int levels = 0;
+    int64_t n_nodes = 0;
+    std::vector<int64_t> off;         // [levels + 1] start of each level's range in eu / ev, every one a multiple of 4
+    std::vector<int64_t> cnt;         // [levels] edges of the level; [off[k] + cnt[k], off[k + 1]) is (0, 0) padding
+    std::vector<int64_t> n_edges;     // [levels] cumulative: edges with score > thresholds[k]
+    std::vector<int64_t> n_clusters;  // [levels]
+    std::vector<int> rounds;          // [levels]
+    DevBuf<uint32_t> label;           // [levels x n_nodes], level-major; offsets into it are size_t
+    DevBuf<uint32_t> eu, ev;          // the edges, bucketed by level
+    double ms = -1.0;                 // device milliseconds of its kernels (timing on), -1 = none
+    // spk_cluster_metrics: the level they describe (-1: none), by node id
+    int m_level = -1;
+    double m_ms = -1.0;
+    DevBuf<uint32_t> degree, size, max_degree;
+    DevBuf<unsigned long long> degree_sum;
+    void clear() { *this = ComponentSweep(); }
+};
+
 struct GammaCols;  // spk_gamma.hip: a call's column decisions
 struct GammaPlan;  // spk_gamma.hip: one window's plan
 enum Kern { K_BLOCK = 0, K_GAMMA = 1, K_EMHIST = 2, K_EMFIN = 3, K_SCORE = 4, K_COUNT = 5 };
@@ -479,6 +504,11 @@ struct spk_ctx {
     // spk_components*: the last labels and the HIP events around its launches (created on first use with timing on)
     spk::Components comp;
     hipEvent_t cc_ev0 = nullptr, cc_ev1 = nullptr;
+    // spk_components_sweep*: the last sweep (it shares the components' events), and which edges a level's rounds
+    // hook: 0 the level's new edges plus a star edge per node, 1 every edge up to the level (spk_components_sweep_set_mode)
+    spk::ComponentSweep sweep;
+    int sweep_mode = 0;
+    bool metrics_edge_agg = true;  // spk_cluster_metrics' edge pass counts inside the wave (spk_cluster_metrics_set_mode 0: off)
     // the last spk_label_histogram (spk_labels.hip): pairs counted (-1: none, or it failed), device milliseconds, and
     // the HIP events around its launches (created on first use with timing on); its buffers live for the call only
     int64_t label_pairs = -1;

@@ -140,6 +140,7 @@ class Job:
         # (frames.py) selects again when either moved on since its last spk_select
         self.codes_seq = 0
         self.selection_owner = None
+        self.sweep_owner = None  # the frame whose sweep (spk_components_sweep) the context holds
         self.code_meta = None
         self.timings = {}
         self.force_reduce = False  # tests: the multi-GPU EM path (histogram -> all-reduce -> finalize) at one rank

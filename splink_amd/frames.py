@@ -341,6 +341,11 @@ class ExpectationFrame(SplinkDataFrame):
         """Shorthand for filter(f"match_probability > {threshold!r}").clusters()."""
         return self.filter(f"match_probability > {threshold!r}").clusters()
 
+    def clusters_at_thresholds(self, thresholds):
+        """Shorthand for filter(f"match_probability > {min(thresholds)!r}").clusters_at_thresholds(thresholds)."""
+        given, _, _ = sweep_thresholds(thresholds)
+        return self.filter(f"match_probability > {min(given)!r}").clusters_at_thresholds(given)
+
     def best_matches(self, threshold=None, per="l", ties="first"):
         """Shorthand for filter(f"match_probability > {threshold!r}").best_matches(per, ties); threshold=None: the
         best match among every pair."""
@@ -465,6 +470,12 @@ class FilteredFrame(SplinkDataFrame):
         connectedComponents on the reference's filtered frame), computed on the device: a `ClusterFrame`."""
         return ClusterFrame(self)
 
+    def clusters_at_thresholds(self, thresholds, by=None):
+        """The clusters of this frame's pairs with score > t for each of 1 to 32 thresholds t (any order), from one
+        selection and one nested pass on the device: a `ClusterSweepFrame` with a cluster_id_{t!r} column per
+        threshold, a summary() per threshold and metrics(t).  by: the score, the frame's first by default."""
+        return ClusterSweepFrame(self, thresholds, by)
+
     # the scores best_matches() can rank by, the default first
     _best_by = ("match_probability",)
 
@@ -585,6 +596,21 @@ class ClusterFrame(SplinkDataFrame):
         self._run()
         return self._info[2]
 
+    def metrics(self):
+        """Cluster and node metrics of these clusters (a `ClusterMetrics`): a one-level sweep over every pair of the
+        frame's own selection, whatever its score, so clusters of pairs with NULL scores are covered too.  The sweep's
+        labels are this frame's (the same definition over the same pairs): a frame that has none yet takes them, and
+        one that has them does not copy them again."""
+        from ._native import SEL_ALL
+        job = self.job
+        job.sweep_owner = None
+        self.filtered._select()
+        n_nodes, _, n_clusters, rounds = job.ctx.components_sweep(SEL_ALL, [])
+        if self._labels is None:
+            self._labels = _copy_in_ranges(lambda s, c: job.ctx.components_sweep_copy(0, s, c), int(n_nodes), np.uint32)
+            self._info = (int(n_nodes), int(n_clusters[0]), int(rounds[0]))
+        return ClusterMetrics(self, self._labels, job.ctx, 0)
+
     def toPandas(self, singletons=True):
         job = self.job
         uid = self.settings["unique_id_column_name"]
@@ -602,6 +628,201 @@ class ClusterFrame(SplinkDataFrame):
         return out
 
 
+def sweep_thresholds(thresholds):
+    """clusters_at_thresholds' argument: 1 to 32 distinct floats, none NaN, in any order.  Returns (the thresholds as
+    given, as floats; the same in descending order, as the device takes them; the level of each given one)."""
+    from ._native import SWEEP_MAX_LEVELS
+    try:
+        given = [float(t) for t in thresholds]
+    except TypeError:
+        raise ValueError("clusters_at_thresholds: thresholds is a sequence of numbers") from None
+    if not 1 <= len(given) <= SWEEP_MAX_LEVELS:
+        raise ValueError(f"clusters_at_thresholds: 1 to {SWEEP_MAX_LEVELS} thresholds, not {len(given)}")
+    if any(t != t for t in given):
+        raise ValueError("clusters_at_thresholds: a threshold is NaN")
+    if len(set(given)) != len(given):
+        raise ValueError("clusters_at_thresholds: a threshold is repeated")
+    desc = sorted(given, reverse=True)
+    return given, np.array(desc, dtype=np.float64), [desc.index(t) for t in given]
+
+
+def sweep_column_names(given):
+    """One label column per threshold, in the order given: cluster_id_0.9 for 0.9 (the threshold's repr)."""
+    return [f"cluster_id_{t!r}" for t in given]
+
+
+def cluster_metric_columns(n_nodes, degree_sum, max_degree):
+    """(n_edges, density, cluster_centralisation) per cluster from its node count, the sum of its degrees and its
+    largest degree.  density = 2E / (n (n - 1)), NaN for n = 1; cluster_centralisation = (n max_degree - degree_sum) /
+    ((n - 1)(n - 2)), NaN for n <= 2 (1 for a star, 0 for a clique or a cycle)."""
+    n = np.asarray(n_nodes, dtype=np.float64)
+    ds = np.asarray(degree_sum, dtype=np.float64)
+    mx = np.asarray(max_degree, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        density = np.where(n > 1, ds / (n * (n - 1)), np.nan)
+        central = np.where(n > 2, (n * mx - ds) / ((n - 1) * (n - 2)), np.nan)
+    return np.asarray(degree_sum, dtype=np.int64) // 2, density, central
+
+
+def _copy_in_ranges(copy, n_nodes, dtype):
+    parts = [copy(s, min(COPY_NODES, n_nodes - s)) for s in range(0, n_nodes, COPY_NODES)]
+    return np.concatenate(parts) if parts else np.empty(0, dtype=dtype)
+
+
+class ClusterMetrics:
+    """Cluster and node metrics of one set of clusters, counted on the device (spk_cluster_metrics) and held on the
+    host: clusters() has one row per cluster, nodes() one per input record, in input order."""
+
+    def __init__(self, frame, labels, ctx, level):
+        self._frame = frame  # a ClusterFrame-shaped frame: the records' ids
+        self._labels = labels
+        n = len(labels)
+        self.n_clusters_multi, self.records_clustered, self.largest_cluster = ctx.cluster_metrics(level)
+        cols = [[], [], [], []]
+        for s in range(0, n, COPY_NODES):
+            for c, part in zip(cols, ctx.cluster_metrics_copy(s, min(COPY_NODES, n - s))):
+                c.append(part)
+        kinds = (np.uint32, np.uint32, np.uint64, np.uint32)
+        self.degree, self.size, self.degree_sum, self.max_degree = [
+            np.concatenate(c) if c else np.empty(0, dtype=k) for c, k in zip(cols, kinds)]
+
+    def clusters(self, singletons=True):
+        """cluster_id, n_nodes, n_edges, density, cluster_centralisation: one row per cluster, by cluster_id."""
+        roots = np.flatnonzero(self._labels == np.arange(len(self._labels), dtype=np.int64))
+        if not singletons:
+            roots = roots[self.size[roots] > 1]
+        n = self.size[roots].astype(np.int64)
+        edges, density, central = cluster_metric_columns(n, self.degree_sum[roots], self.max_degree[roots])
+        return pd.DataFrame(OrderedDict([("cluster_id", roots.astype(np.int64)), ("n_nodes", n), ("n_edges", edges),
+                                         ("density", density), ("cluster_centralisation", central)]))
+
+    def nodes(self):
+        """The cluster frame's columns, then node_degree and node_centrality = degree / (nodes of its cluster - 1),
+        NaN for a record that is a cluster of its own."""
+        out = ClusterFrame.toPandas(self._frame)
+        n = self.size[self._labels].astype(np.float64)
+        out["node_degree"] = self.degree.astype(np.int64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["node_centrality"] = np.where(n > 1, self.degree / (n - 1), np.nan)
+        return out
+
+
+class _SweepLevelFrame(ClusterFrame):
+    """ClusterSweepFrame.at(t): its `filtered` is the sweep's wide frame, so the metrics are the sweep's at t."""
+
+    def metrics(self):
+        sweep, t = self._of
+        return sweep.metrics(t)
+
+
+class ClusterSweepFrame(SplinkDataFrame):
+    """`filtered.clusters_at_thresholds(thresholds)`: the clusters of the frame's pairs with score > t, for every t, from
+    one selection and one nested sweep on the device (spk_components_sweep).  One row per input record, in input
+    order, and one column cluster_id_{t!r} per threshold, each equal to clusters(t)'s cluster_id."""
+
+    def __init__(self, filtered: FilteredFrame, thresholds, by=None):
+        from .select import BEST_BY
+        self.thresholds, self._desc, self._level = sweep_thresholds(thresholds)
+        scores = getattr(filtered, "inner", filtered)._best_by  # a best-match frame carries its inner frame's scores
+        by = scores[0] if by is None else by
+        if not isinstance(by, str) or by not in scores:
+            raise ValueError(f"clusters_at_thresholds: by={by!r}; legal values: " + ", ".join(repr(b) for b in scores))
+        if filtered._scored_parent() is None:
+            raise ValueError("clusters_at_thresholds: this frame has no score to put thresholds on (it was filtered "
+                             "from an unscored frame): filter the frame run_expectation_step returns")
+        job = filtered.job
+        if getattr(job, "passthrough", None) is not None:
+            raise ValueError("clusters_at_thresholds() needs the records: a job made from a gamma table has pairs "
+                             "without rows")
+        if job.n_shards > 1:
+            raise ValueError("clusters_at_thresholds() on a sharded job: a record's cluster spans the shards' pairs")
+        self.filtered = filtered
+        self.job = job
+        self.settings = filtered.settings
+        self.by = by
+        self._field = BEST_BY[by]
+        self._labels = None  # [level][node]
+        self._info = None    # (n_nodes, n_edges [L], n_clusters [L], rounds [L]), levels in descending threshold
+
+    def _sweep(self):
+        """Make the context's sweep this frame's (the frame's re-select rules, then the sweep)."""
+        job = self.job
+        job.sweep_owner = None
+        self.filtered._select()
+        info = job.ctx.components_sweep(self._field, self._desc)
+        job.sweep_owner = self
+        return info
+
+    def _run(self):
+        """Select, sweep and copy every level's labels at once, in ranges: a later selection, components or sweep call
+        of the job does not reach them."""
+        if self._labels is None:
+            ctx = self.job.ctx
+            info = self._sweep()
+            n_nodes = int(info[0])
+            self._labels = [_copy_in_ranges(lambda s, c, k=k: ctx.components_sweep_copy(k, s, c), n_nodes, np.uint32)
+                            for k in range(len(self._desc))]
+            self._info = (n_nodes, info[1].copy(), info[2].copy(), info[3].copy())
+        return self._labels
+
+    def _held(self):
+        """The context holds this frame's sweep (metrics and summary count on the device): sweep again if not."""
+        self._run()
+        if self.job.sweep_owner is not self:
+            self._sweep()
+
+    def _level_of(self, t):
+        t = float(t)
+        if t not in self.thresholds:
+            raise ValueError(f"{t!r} is not one of this frame's thresholds: " + ", ".join(repr(x) for x in self.thresholds))
+        return self._level[self.thresholds.index(t)]
+
+    def _column_order(self):
+        cols = [self.settings["unique_id_column_name"]]
+        if self.job.link_type in ("link_only", "link_and_dedupe"):
+            cols.append("_source_table")
+        return cols + sweep_column_names(self.thresholds)
+
+    def count(self) -> int:
+        return int(sum(len(t) for t in self.job.inputs))
+
+    def at(self, t):
+        """The clusters at threshold t as a ClusterFrame: the same toPandas(singletons=...), n_clusters and rounds."""
+        k = self._level_of(t)
+        labels = self._run()[k]
+        out = _SweepLevelFrame(self.filtered)
+        out._of = (self, t)
+        out._labels = labels
+        out._info = (self._info[0], int(self._info[2][k]), int(self._info[3][k]))
+        return out
+
+    def toPandas(self):
+        labels = self._run()
+        base = ClusterFrame.toPandas(self.at(self.thresholds[0])).drop(columns="cluster_id")
+        for t, name in zip(self.thresholds, sweep_column_names(self.thresholds)):
+            base[name] = labels[self._level_of(t)].astype(np.int64)
+        return base
+
+    def metrics(self, t):
+        """Cluster and node metrics at threshold t: a `ClusterMetrics`."""
+        k = self._level_of(t)
+        self._held()
+        return ClusterMetrics(self.at(t), self._labels[k], self.job.ctx, k)
+
+    def summary(self):
+        """One row per threshold, in the order given: threshold, n_edges (pairs with score > threshold), n_clusters,
+        n_clusters_multi (clusters of two or more records), records_clustered (records in those), largest_cluster,
+        rounds."""
+        self._held()
+        rows = []
+        for t in self.thresholds:
+            k = self._level_of(t)
+            multi, nodes, largest = self.job.ctx.cluster_metrics(k)
+            rows.append((t, int(self._info[1][k]), int(self._info[2][k]), multi, nodes, largest, int(self._info[3][k])))
+        return pd.DataFrame(rows, columns=["threshold", "n_edges", "n_clusters", "n_clusters_multi",
+                                           "records_clustered", "largest_cluster", "rounds"])
+
+
 def reject_filtered(frame, what):
     """The stage functions run over every pair of a job: a filtered frame must not slip into them."""
     if isinstance(frame, BestMatchFrame):
@@ -610,6 +831,6 @@ def reject_filtered(frame, what):
     if isinstance(frame, FilteredFrame):
         raise ValueError(f"{what} does not take a filtered frame (it would run over all of the job's pairs, not the "
                          "survivors): pass the frame filter() was called on")
-    if isinstance(frame, ClusterFrame):
+    if isinstance(frame, (ClusterFrame, ClusterSweepFrame, ClusterMetrics)):
         raise ValueError(f"{what} does not take a cluster frame (it holds records, not pairs): pass the frame "
                          "filter() was called on")

@@ -104,6 +104,12 @@ class TermFrequencyFrame(SplinkDataFrame):
         """Shorthand for filter(f"tf_adjusted_match_prob > {threshold!r}").clusters()."""
         return self.filter(f"tf_adjusted_match_prob > {threshold!r}").clusters()
 
+    def clusters_at_thresholds(self, thresholds):
+        """Shorthand for filter(f"tf_adjusted_match_prob > {min(thresholds)!r}").clusters_at_thresholds(thresholds)."""
+        from .frames import sweep_thresholds
+        given, _, _ = sweep_thresholds(thresholds)
+        return self.filter(f"tf_adjusted_match_prob > {min(given)!r}").clusters_at_thresholds(given)
+
     def best_matches(self, threshold=None, per="l", ties="first"):
         """Shorthand for filter(f"tf_adjusted_match_prob > {threshold!r}").best_matches(per, ties); threshold=None:
         the best match among every pair."""

@@ -69,6 +69,72 @@ def components(n_nodes, u, v, climb=CLIMB, round_cap=ROUND_CAP):
     raise RuntimeError("no fixed point within %d rounds" % round_cap)
 
 
+def components_sweep(n_nodes, u, v, level, n_levels, climb=CLIMB, round_cap=ROUND_CAP, prefix=False):
+    """spk_components_sweep's levels under the same model: edge i is new at level[i] (>= n_levels: in no level) and
+    belongs to every later level.  Level k starts from level k - 1's final labels (level 0: label[v] = v) and runs
+    rounds whose hook launch takes the level's new edges and whose jump launch also hooks, for every node v, the star
+    edge (v, label_{k-1}[v]) -- against the jump launch's own snapshot, landing at its end.  prefix=True is the other
+    variant: the hook takes every edge up to the level and the jump is the plain one.  A level without new edges runs
+    no round.  Returns (labels uint32 [n_levels, n_nodes], rounds per level)."""
+    u = np.asarray(u, dtype=np.int64)
+    v = np.asarray(v, dtype=np.int64)
+    level = np.asarray(level, dtype=np.int64)
+    nodes = np.arange(n_nodes, dtype=np.int64)
+    label = nodes.copy()
+    out, rounds_per_level = [], []
+    for k in range(n_levels):
+        prev = label.copy()
+        mine = level <= k if prefix else level == k
+        hu, hv = u[mine], v[mine]
+        rounds = 0
+        quiet = not (level == k).any()
+        while not quiet:
+            if rounds == round_cap:
+                raise RuntimeError("level %d: no fixed point within %d rounds" % (k, round_cap))
+            before = label.copy()
+            a, b = _climb(label, hu, climb), _climb(label, hv, climb)
+            ne = a != b
+            if ne.any():
+                nxt = label.copy()
+                np.minimum.at(nxt, np.maximum(a[ne], b[ne]), np.minimum(a[ne], b[ne]))
+                label = nxt
+            up = _climb(label, nodes, climb)
+            nxt = np.minimum(label, up)
+            if k > 0 and not prefix:
+                b = _climb(label, prev, climb)
+                ne = up != b
+                if ne.any():
+                    np.minimum.at(nxt, np.maximum(up[ne], b[ne]), np.minimum(up[ne], b[ne]))
+            label = nxt
+            rounds += 1
+            quiet = np.array_equal(label, before)
+        out.append(label.astype(np.uint32))
+        rounds_per_level.append(rounds)
+    return np.stack(out) if out else np.empty((0, n_nodes), dtype=np.uint32), rounds_per_level
+
+
+def alternating_path(n=65536):
+    """The path 0 - 1 - ... - n-1 in two levels: the odd edges (2i+1, 2i+2) are level 0, the even ones (2i, 2i+1)
+    level 1, so level 1 joins n / 2 pairs into one path."""
+    a = np.arange(n - 1, dtype=np.uint32)
+    return n, a, a + 1, ((a + 1) % 2).astype(np.int64)
+
+
+def random_levels(n_edges, n_levels, seed, none=0.1):
+    """A seeded level per edge in [0, n_levels), about a tenth of the edges in no level (n_levels)."""
+    rng = np.random.default_rng(seed)
+    level = rng.integers(0, n_levels, n_edges)
+    level[rng.random(n_edges) < none] = n_levels
+    return level
+
+
+def union_find_levels(n_nodes, u, v, level, n_levels):
+    """union_find of the edges with level <= k, for every k: uint32 [n_levels, n_nodes]."""
+    level = np.asarray(level)
+    u, v = np.asarray(u), np.asarray(v)
+    return np.stack([union_find(n_nodes, u[level <= k], v[level <= k]) for k in range(n_levels)])
+
+
 # ---- the graphs of tests/test_gpu_components.py (cases 3 to 5) ---------------------------------------------------
 def path_graph(n=65536, seed=3):
     """One path through a seeded random permutation of the ids, edges shuffled, orientations mixed."""
@@ -119,6 +185,14 @@ def main():
             got, rounds = components(n, u, v, climb=climb, round_cap=ROUND_CAP)
             print("%-7s nodes %7d edges %7d climb %d: rounds %4d  labels %s" % (
                 name, n, len(u), climb, rounds, "equal" if np.array_equal(got, want) else "DIFFER"))
+        n_levels = 4 if name == "hub" else 8
+        level = random_levels(len(u), n_levels, seed=n_levels)
+        want = union_find_levels(n, u, v, level, n_levels)
+        for prefix in (False, True):
+            got, rounds = components_sweep(n, u, v, level, n_levels, prefix=prefix)
+            print("%-7s sweep of %d levels, %s: rounds %s  labels %s" % (
+                name, n_levels, "every edge up to the level" if prefix else "new edges and star edges", rounds,
+                "equal" if np.array_equal(got, want) else "DIFFER"))
 
 
 if __name__ == "__main__":
