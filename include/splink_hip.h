@@ -351,7 +351,8 @@ int spk_block_profile_info(spk_ctx *ctx, double *out_key_ms, double *out_enum_ms
 int spk_block_profile_set_cut(spk_ctx *ctx, int on);
 /* Decode codes to int8 gamma columns, [count x K] row-major. */
 int spk_gammas_copy(spk_ctx *ctx, int64_t start, int64_t count, int8_t *out);
-/* Use a caller-provided gamma matrix (int8 [n x K], values -1..L_k-1). */
+/* Use a caller-provided gamma matrix (int8 [n x K], values -1..L_k-1).  The pattern space Π (L_k + 1) must be
+ * below 2^31 (SPK_E_LIMIT otherwise, as for spk_gammas). */
 int spk_gammas_load(spk_ctx *ctx, int n_cols, const int32_t *n_levels, int64_t n, const int8_t *gammas);
 int spk_n_patterns(spk_ctx *ctx, int64_t *out);
 /* Pairs the last spk_gammas evaluated in the global-memory pass (strings beyond LDS staging). */
@@ -460,6 +461,9 @@ int spk_em_histogram(spk_ctx *ctx, uint64_t *d_hist);
  * into one LDS histogram, 2 = as 1 without the fence (relies on gfx950 draining the row atomics before the
  * ticket).  For testing and measurement. */
 int spk_em_set_lane_histogram(spk_ctx *ctx, int on);
+/* The lane-private copies per pattern (64, 32, 16, 8 or 4) the E+M launch takes for the current pairs, pattern
+ * space and histogram mode; 0 = the wave-ballot histogram + finalize launches.  For testing. */
+int spk_em_lane_copies(spk_ctx *ctx, int *out);
 /* E-step per pattern with the reference's literal arithmetic, then the M-step sums:
  * out_stats (host) = [Σmp, rows, non-null rows, Σ ln(λΠm + (1-λ)Πu), non-null ln rows] + per column k,
  * per level v in -1..L_k-1:

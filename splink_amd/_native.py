@@ -84,6 +84,7 @@ EXPORTS = [
     "spk_label_histogram", "spk_label_info",
     "spk_pairs_sample", "spk_pairs_sample_info",
     "spk_block_profile", "spk_block_profile_info", "spk_block_profile_set_cut",
+    "spk_em_lane_copies",
 ]
 # spk_rule_profile / spk_block_entry: the per-rule figures and one of a rule's largest blocks (spk_block_profile)
 RULE_PROFILE_DTYPE = np.dtype([("rows_l", "<i8"), ("rows_r", "<i8"), ("blocks", "<i8"), ("candidates", "<i8"),
@@ -568,6 +569,13 @@ class Context:
         """True / 1: lane-private counters, release fence before each last-arriver ticket (default); False / 0:
         wave-ballot histogram; 2: lane counters without the fence (A/B)."""
         check(self._lib.spk_em_set_lane_histogram(self._h, ctypes.c_int(int(on))), "spk_em_set_lane_histogram")
+
+    def em_lane_copies(self) -> int:
+        """Lane-private copies per pattern of the E+M launch for the current pairs and pattern space (64 .. 4);
+        0: the wave-ballot histogram + finalize launches."""
+        n = ctypes.c_int(0)
+        check(self._lib.spk_em_lane_copies(self._h, ctypes.byref(n)), "spk_em_lane_copies")
+        return n.value
 
     def em_histogram(self, d_hist_ptr: int = 0):
         check(self._lib.spk_em_histogram(self._h, ctypes.c_void_p(d_hist_ptr)), "spk_em_histogram")

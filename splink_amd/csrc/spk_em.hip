@@ -101,6 +101,10 @@ __global__ __launch_bounds__(H_THREADS) void k_hist(const CodeT *__restrict__ co
 // against 0.142; the real 100M-record share: 0.768 against 0.598 ms per iteration; profiles/r5_ab_em_tiers.log).
 constexpr int HL_THREADS = 1024;
 constexpr int HL_LDS_BYTES = 160 * 1024;  // one workgroup per CU, all of its LDS (gfx950), capped by the device attribute
+// Reserved for k_em_iter's static LDS (s_last, s_rest, s_best and em_finalize_block's s_rr, s_tot: about 1.5 KiB),
+// which shares the workgroup's allocation with the counters: sized to the whole budget, a 640-pattern space at
+// R = 64 asked for 163 840 + 4 bytes and the launch was refused (tests/test_gpu_em_variants.py, R64_640).
+constexpr int HL_STATIC_BYTES = 2048;
 constexpr int HL_UNROLL = 4;
 constexpr int EM_AROWS = 4;               // the one-level reduction's rows (workgroup mod EM_AROWS)
 
@@ -114,7 +118,7 @@ constexpr int PA_INLINE_MU = 96;
 
 struct PatArgs {
     int K;
-    int n_pat;  // <= 2^31 (set_pattern_space)
+    int n_pat;  // < 2^31 (set_pattern_space)
     int n_slots;
     int tot;    // Σ L_k
     double lambda, one_minus;
@@ -824,7 +828,8 @@ struct LanePlan {
 static LanePlan lane_plan(spk_ctx *ctx) {
     LanePlan L;
     const int64_t n_pat = ctx->n_patterns;
-    const int64_t budget = std::min<int64_t>(HL_LDS_BYTES, ctx->lds_per_block);
+    // the counters are the launch's dynamic LDS; k_em_iter's static LDS comes on top of it in the same allocation
+    const int64_t budget = std::min<int64_t>(HL_LDS_BYTES, ctx->lds_per_block) - HL_STATIC_BYTES;
     int R = 64;
     while (R >= 4 && n_pat * R * 4 > budget) R >>= 1;
     if (R < 4 || !ctx->hist_lanes || ctx->n_pairs >= (int64_t)UINT32_MAX) return L;
@@ -968,10 +973,8 @@ static int enqueue_histogram(spk_ctx *ctx, uint64_t *d_hist) {
                 reinterpret_cast<const uint16_t *>(ctx->codes.p), P, (int)n_pat, h);
             else k_hist<uint16_t, false><<<(unsigned)blocks, H_THREADS, 0, ctx->stream>>>(
                 reinterpret_cast<const uint16_t *>(ctx->codes.p), P, (int)n_pat, h);
-        } else {
-            if (lds) k_hist<uint32_t, true><<<(unsigned)blocks, H_THREADS, shm, ctx->stream>>>(
-                reinterpret_cast<const uint32_t *>(ctx->codes.p), P, (int)n_pat, h);
-            else k_hist<uint32_t, false><<<(unsigned)blocks, H_THREADS, 0, ctx->stream>>>(
+        } else {  // uint32 codes: more than 65 536 patterns, always past H_LDS_BINS
+            k_hist<uint32_t, false><<<(unsigned)blocks, H_THREADS, 0, ctx->stream>>>(
                 reinterpret_cast<const uint32_t *>(ctx->codes.p), P, (int)n_pat, h);
         }
     }
@@ -1007,6 +1010,13 @@ extern "C" int spk_em_set_lane_histogram(spk_ctx *ctx, int on) {
     SPK_REQUIRE(ctx && on >= 0 && on <= 2, SPK_E_INVALID, "spk_em_set_lane_histogram: mode 0, 1 or 2");
     ctx->hist_lanes = on != 0;
     ctx->em_fence = on != 2;
+    return SPK_OK;
+}
+
+extern "C" int spk_em_lane_copies(spk_ctx *ctx, int *out) {
+    SPK_REQUIRE(ctx && out, SPK_E_INVALID, "spk_em_lane_copies: null arg");
+    SPK_REQUIRE(ctx->codes_valid, SPK_E_STATE, "spk_em_lane_copies: no gammas");
+    *out = lane_plan(ctx).R;
     return SPK_OK;
 }
 

@@ -1901,8 +1901,9 @@ static int set_pattern_space(spk_ctx *ctx, int K, const int32_t *nlev) {
         SPK_REQUIRE(nlev[k] >= 1 && nlev[k] <= 126, SPK_E_INVALID, "num_levels out of range");
         ctx->stride[k] = s;
         s *= (int64_t)(nlev[k] + 1);
-        SPK_REQUIRE(s <= (int64_t)1 << 31, SPK_E_LIMIT,
-                    "comparison-vector pattern space exceeds 2^31 (too many columns x levels)");
+        // pattern indices and their count are int on the device (PatArgs::n_pat): 2^31 itself does not fit
+        SPK_REQUIRE(s < (int64_t)1 << 31, SPK_E_LIMIT,
+                    "comparison-vector pattern space reaches 2^31 (too many columns x levels)");
     }
     ctx->n_patterns = s;
     ctx->code_bytes = s <= 65536 ? 2 : 4;
