@@ -251,8 +251,9 @@ static unsigned best_grid(const spk_ctx *ctx, int64_t n_chunks) {
 }
 
 // The narrowing of S (the context's former selection, now a local of spk_select_best) into T.
-static int narrow_selection(spk_ctx *ctx, Selection &S, int field, int mode, int keep_ties, int64_t n_groups,
-                            int64_t n0, int64_t n1, int64_t r_base, Selection &T, double &ms_out) {
+static int narrow_selection(spk_ctx *ctx, Selection &S, int field, int mode, int keep_ties, const NodeSpace &N,
+                            Selection &T, double &ms_out) {
+    const int64_t n_groups = N.n_nodes;
     hipStream_t st = ctx->stream;
     const int64_t n = S.n;
     T.K = S.K;
@@ -266,18 +267,7 @@ static int narrow_selection(spk_ctx *ctx, Selection &S, int field, int mode, int
     T.gamma_seq = S.gamma_seq;
     T.fix_seq = S.fix_seq;
     T.ms = S.ms;  // spk_select_info keeps its meaning: the time of the selection's own kernels
-    if (ctx->timing) {
-        if (!ctx->sel_ev0) SPK_HIP(hipEventCreate(&ctx->sel_ev0));
-        if (!ctx->sel_ev1) SPK_HIP(hipEventCreate(&ctx->sel_ev1));
-    }
-    double ms = 0.0;
-    auto lap = [&]() -> int {  // after a synchronisation: add the last event pair
-        if (!ctx->timing) return SPK_OK;
-        float t = 0.f;
-        SPK_HIP(hipEventElapsedTime(&t, ctx->sel_ev0, ctx->sel_ev1));
-        ms += (double)t;
-        return SPK_OK;
-    };
+    StageTimer watch{ctx};
     int64_t kept = 0;
     const int64_t n_chunks = (n + BEST_CHUNK - 1) / BEST_CHUNK;
     BestArgs A{};
@@ -301,9 +291,9 @@ static int narrow_selection(spk_ctx *ctx, Selection &S, int field, int mode, int
         A.n_pat = field == SPK_SEL_MP ? (int64_t)S.mpat.n - 1 : 0;  // build_selection allocates n_patterns + 1
         A.tf_mp = field == SPK_SEL_TF_MP ? S.tf_mp.p : nullptr;
         A.n_tf = S.n_tf;
-        A.n0 = n0;
-        A.n1 = n1;
-        A.r_base = r_base;
+        A.n0 = N.n0;
+        A.n1 = N.n1;
+        A.r_base = N.r_base;
         A.mode = mode;
         A.keep_ties = keep_ties;
         A.gmax = gmax.p;
@@ -312,7 +302,7 @@ static int narrow_selection(spk_ctx *ctx, Selection &S, int field, int mode, int
         A.bitmap = bitmap.p;
         A.chunk_count = chunks.count.p;
         const unsigned g = best_grid(ctx, n_chunks);
-        if (ctx->timing) SPK_HIP(hipEventRecord(ctx->sel_ev0, st));
+        SPK_TRY(watch.open());
         SPK_HIP(hipMemsetAsync(gmax.p, 0, ((size_t)n_groups + 1) * 8, st));
         if (!keep_ties) SPK_HIP(hipMemsetAsync(gwin.p, 0xFF, ((size_t)n_groups + 1) * 8, st));  // no winner yet
         SPK_HIP(hipMemsetAsync(bad.p, 0, sizeof(unsigned int), st));
@@ -329,8 +319,7 @@ static int narrow_selection(spk_ctx *ctx, Selection &S, int field, int mode, int
         SPK_HIP(hipGetLastError());
         unsigned int h_bad = 0u;
         SPK_HIP(hipMemcpyAsync(&h_bad, bad.p, sizeof(h_bad), hipMemcpyDeviceToHost, st));
-        SPK_TRY(scan_total(ctx, chunks, tmp, ctx->timing ? ctx->sel_ev1 : nullptr));  // synchronises
-        SPK_TRY(lap());
+        SPK_TRY(scan_total(ctx, chunks, tmp, &watch));  // synchronises
         SPK_REQUIRE(h_bad == 0u, SPK_E_STATE, "spk_select_best: a selected pair names a row outside its table");
         kept = chunks.total;
         SPK_REQUIRE(kept >= 0 && kept <= n, SPK_E_STATE, "spk_select_best: kept count");
@@ -356,17 +345,15 @@ static int narrow_selection(spk_ctx *ctx, Selection &S, int field, int mode, int
             A.out_tf = T.tf_mp.p;
             A.out_adj = S.n_tf > 0 ? T.adj.p : nullptr;
         }
-        if (ctx->timing) SPK_HIP(hipEventRecord(ctx->sel_ev0, st));
+        SPK_TRY(watch.open());
         k_best_emit<<<best_grid(ctx, n_chunks), BEST_THREADS, 0, st>>>(A);
         SPK_HIP(hipGetLastError());
-        if (ctx->timing) SPK_HIP(hipEventRecord(ctx->sel_ev1, st));
-        SPK_HIP(hipStreamSynchronize(st));
-        SPK_TRY(lap());
+        SPK_TRY(watch.close());
     }
     T.mpat = std::move(S.mpat);
     T.n = kept;
     T.valid = true;
-    ms_out = ctx->timing ? ms : -1.0;
+    ms_out = watch.result();
     return SPK_OK;
 }
 
@@ -387,21 +374,17 @@ extern "C" int spk_select_best(spk_ctx *ctx, int field, int mode, int keep_ties,
                 "spk_select_best: unknown mode (SPK_BEST_L, _R, _EITHER or _MUTUAL)");
     SPK_REQUIRE(keep_ties == 0 || keep_ties == 1, SPK_E_INVALID, "spk_select_best: keep_ties is 0 or 1");
     SPK_REQUIRE(S.valid, SPK_E_STATE, "spk_select_best: no selection (run spk_select)");
-    SPK_REQUIRE(ctx->codes_valid && S.pairs_epoch == ctx->pairs_epoch && S.gamma_seq == ctx->gamma_seq &&
-                    S.fix_seq == ctx->codes_fix_seq,
-                SPK_E_STATE, "spk_select_best: the pairs or codes changed since spk_select");
+    SPK_REQUIRE(S.current(ctx), SPK_E_STATE, "spk_select_best: the pairs or codes changed since spk_select");
     SPK_REQUIRE(S.has_rows, SPK_E_STATE, "spk_select_best: no pair rows (a loaded gamma table)");
     SPK_REQUIRE(field != SPK_SEL_MP || S.has_mp, SPK_E_STATE,
                 "spk_select_best: no match_probability (spk_select got no m / u)");
     SPK_REQUIRE(field != SPK_SEL_TF_MP || S.has_tf, SPK_E_STATE,
                 "spk_select_best: no tf_adjusted_match_prob (the selection was made without tf tables, spk_select)");
-    const bool two = ctx->link_type == SPK_LINK_ONLY;
-    const Table &t0 = ctx->table[0], &t1 = ctx->table[two ? 1 : 0];
-    SPK_REQUIRE(t0.n >= 0 && t1.n >= 0, SPK_E_STATE, "spk_select_best: no tables");
-    const int64_t n_groups = t0.n + (two ? t1.n : 0);
+    const NodeSpace N = node_space(ctx);
+    SPK_REQUIRE(N.n0 >= 0 && N.n1 >= 0, SPK_E_STATE, "spk_select_best: no tables");
     Selection T;
     double ms = -1.0;
-    SPK_TRY(narrow_selection(ctx, S, field, mode, keep_ties, n_groups, t0.n, t1.n, two ? t0.n : 0, T, ms));
+    SPK_TRY(narrow_selection(ctx, S, field, mode, keep_ties, N, T, ms));
     ctx->best_before = S.n;
     ctx->best_kept = T.n;
     ctx->best_ms = ms;

@@ -755,20 +755,9 @@ extern "C" int spk_block_residual(spk_ctx *ctx, int link_type, int n_rules, cons
     DevBuf<uint8_t> d_keep, tmp;
     SPK_TRY(d_keep.alloc(keep.size()));
     SPK_HIP(hipMemcpyAsync(d_keep.p, keep.data(), keep.size(), hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->timing) {
-        if (!ctx->res_ev0) SPK_HIP(hipEventCreate(&ctx->res_ev0));
-        if (!ctx->res_ev1) SPK_HIP(hipEventCreate(&ctx->res_ev1));
-    }
     // device time of the compaction alone: each rule's count kernel and scan, then the emit kernels; the host
-    // round trips between them (the survivor counts, the allocations) lie outside the event pairs
-    double filter_ms = 0.0;
-    auto lap = [&]() -> int {  // after a synchronisation: add the last event pair
-        if (!ctx->timing) return SPK_OK;
-        float ms = 0.f;
-        SPK_HIP(hipEventElapsedTime(&ms, ctx->res_ev0, ctx->res_ev1));
-        filter_ms += (double)ms;
-        return SPK_OK;
-    };
+    // round trips between them (the survivor counts, the allocations) lie outside the intervals
+    StageTimer T{ctx};
     const int64_t old_pv_base = ctx->pv_base;
     const int n_views = ctx->n_views;
     // k_residual_filter's arguments for rule r's enumerated range: what both passes must agree on.  The count pass
@@ -794,11 +783,10 @@ extern "C" int spk_block_residual(spk_ctx *ctx, int link_type, int n_rules, cons
         SPK_TRY(chunks[r].alloc(ctx, (hi - lo + RF_CHUNK - 1) / RF_CHUNK));
         ResidualFilterArgs A = filter_args(r);
         A.chunk_count = chunks[r].count.p;
-        if (ctx->timing) SPK_HIP(hipEventRecord(ctx->res_ev0, ctx->stream));
+        SPK_TRY(T.open());
         k_residual_filter<false><<<(unsigned)chunks[r].n, RF_THREADS, 0, ctx->stream>>>(A);
         SPK_HIP(hipGetLastError());
-        SPK_TRY(scan_total(ctx, chunks[r], tmp, ctx->timing ? ctx->res_ev1 : nullptr));
-        SPK_TRY(lap());
+        SPK_TRY(scan_total(ctx, chunks[r], tmp, &T));
         n_out += chunks[r].total;
     }
     SPK_REQUIRE(n_out <= n_enum, SPK_E_STATE, "spk_block_residual: survivor count");
@@ -811,7 +799,7 @@ extern "C" int spk_block_residual(spk_ctx *ctx, int link_type, int n_rules, cons
         SPK_TRY(npvl.alloc((size_t)(n_out - pv_base) + 1));
         SPK_TRY(npvr.alloc((size_t)(n_out - pv_base) + 1));
     }
-    if (ctx->timing) SPK_HIP(hipEventRecord(ctx->res_ev0, ctx->stream));
+    SPK_TRY(T.open());
     for (int r = 0; r < n_rules; ++r) {
         if (!chunks[r].n) continue;
         ResidualFilterArgs A = filter_args(r);
@@ -829,10 +817,8 @@ extern "C" int spk_block_residual(spk_ctx *ctx, int link_type, int n_rules, cons
         k_residual_filter<true><<<(unsigned)chunks[r].n, RF_THREADS, 0, ctx->stream>>>(A);
         SPK_HIP(hipGetLastError());
     }
-    if (ctx->timing) SPK_HIP(hipEventRecord(ctx->res_ev1, ctx->stream));
-    SPK_HIP(hipStreamSynchronize(ctx->stream));
-    SPK_TRY(lap());
-    if (ctx->timing) ctx->res_filter_ms = filter_ms;
+    SPK_TRY(T.close());
+    ctx->res_filter_ms = T.result();
     ctx->pl = std::move(npl);
     ctx->pr = std::move(npr);
     ctx->pvl = std::move(npvl);
@@ -854,15 +840,6 @@ struct LinkTypeLease {
     int saved;
     LinkTypeLease(spk_ctx *c, int link_type) : ctx(c), saved(c->link_type) { c->link_type = link_type; }
     ~LinkTypeLease() { ctx->link_type = saved; }
-};
-
-// The call's two HIP events (timing on), destroyed when it returns.
-struct EventPair {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~EventPair() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
 };
 
 // The first min(limit, B) blocks of a planned rule by descending metric into out[0 .. *n_out).  `bins`: blocks per
@@ -968,27 +945,15 @@ extern "C" int spk_block_profile(spk_ctx *ctx, int link_type, int n_rules, const
         SPK_REQUIRE((int)tl.key[0].size() > r && tl.key[0][r]->p && (int)tr.key[1].size() > r && tr.key[1][r]->p,
                     SPK_E_STATE, "spk_block_profile: keys not set for every rule");
     }
-    EventPair ev;
-    if (ctx->timing) {
-        SPK_HIP(hipEventCreate(&ev.e0));
-        SPK_HIP(hipEventCreate(&ev.e1));
-    }
-    auto elapsed = [&](double *ms) -> int {  // the stream is synchronised
-        if (!ctx->timing) return SPK_OK;
-        float f = 0.f;
-        SPK_HIP(hipEventElapsedTime(&f, ev.e0, ev.e1));
-        *ms = (double)f;
-        return SPK_OK;
-    };
     // ---- key level: per rule the plan (sorted views, blocks, candidates per block and their scan), the block
     // statistics and the largest blocks.  A plan is kept only while its rule may still be enumerated.
-    double key_ms = -1.0, enum_ms = -1.0;
+    StageTimer key_t{ctx}, enum_t{ctx};  // two readings, one after the other
     DevBuf<uint8_t> tmp;
     DevBuf<ProfileStats> d_stats;
     SPK_TRY(d_stats.alloc(1));
     std::vector<RulePlan> plans(n_rules);
     int64_t total = 0;
-    if (ctx->timing) SPK_HIP(hipEventRecord(ev.e0, ctx->stream));
+    SPK_TRY(key_t.open());
     for (int r = 0; r < n_rules; ++r) {
         RulePlan &P = plans[r];
         SPK_TRY(plan_rule(ctx, r, rule_symmetric[r] != 0, P, tmp));
@@ -1024,17 +989,13 @@ extern "C" int spk_block_profile(spk_ctx *ctx, int link_type, int n_rules, const
         }
         if (max_enumerate == 0) P = RulePlan();
     }
-    if (ctx->timing) {
-        SPK_HIP(hipEventRecord(ev.e1, ctx->stream));
-        SPK_HIP(hipStreamSynchronize(ctx->stream));
-        SPK_TRY(elapsed(&key_ms));
-    }
+    if (ctx->timing) SPK_TRY(key_t.close());  // timing off: nothing here waits for the stream
     // ---- enumeration: this shard's ordinals of each rule, cut as block_rules cuts them
     const int64_t g_lo = (int64_t)((__int128)total * shard / n_shards);
     const int64_t g_hi = (int64_t)((__int128)total * (shard + 1) / n_shards);
     int64_t acc = 0, ordinals = 0;
     DevBuf<int64_t> chunks;
-    if (ctx->timing) SPK_HIP(hipEventRecord(ev.e0, ctx->stream));
+    SPK_TRY(enum_t.open());
     for (int r = 0; r < n_rules && max_enumerate != 0; ++r) {
         RulePlan &P = plans[r];
         const int64_t lo = std::max<int64_t>(g_lo - acc, 0), hi = std::min<int64_t>(g_hi - acc, P.cand.total);
@@ -1056,13 +1017,9 @@ extern "C" int spk_block_profile(spk_ctx *ctx, int link_type, int n_rules, const
         }
         P = RulePlan();  // the rule's views, blocks and by-position copies
     }
-    if (ctx->timing) {
-        SPK_HIP(hipEventRecord(ev.e1, ctx->stream));
-        SPK_HIP(hipStreamSynchronize(ctx->stream));
-        SPK_TRY(elapsed(&enum_ms));
-    }
-    ctx->profile_key_ms = key_ms;
-    ctx->profile_enum_ms = enum_ms;
+    if (ctx->timing) SPK_TRY(enum_t.close());
+    ctx->profile_key_ms = key_t.result();
+    ctx->profile_enum_ms = enum_t.result();
     ctx->profile_ordinals = ordinals;
     return SPK_OK;
 }

@@ -192,76 +192,6 @@ static unsigned cc_grid(const spk_ctx *ctx, int64_t items, int64_t per_wg) {
     return (unsigned)std::max<int64_t>(std::min<int64_t>(g, CC_WG_PER_CU * (int64_t)ctx->n_cu), 1);
 }
 
-// Labels of the graph (eu, ev) [n_edges] over n_nodes nodes into C, a local of the caller.  `first` is an event pair
-// already open around the caller's own launches (the edge build), or false.
-static int build_components(spk_ctx *ctx, int64_t n_nodes, int64_t n_edges, const uint32_t *eu, const uint32_t *ev,
-                            int bad_code, const char *bad_msg, bool first, Components &C) {
-    hipStream_t st = ctx->stream;
-    double ms = 0.0;
-    auto open = [&]() -> int {
-        if (ctx->timing) SPK_HIP(hipEventRecord(ctx->cc_ev0, st));
-        return SPK_OK;
-    };
-    auto close = [&]() -> int {  // ends the open event pair, synchronises, adds it
-        if (ctx->timing) SPK_HIP(hipEventRecord(ctx->cc_ev1, st));
-        SPK_HIP(hipStreamSynchronize(st));
-        if (ctx->timing) {
-            float t = 0.f;
-            SPK_HIP(hipEventElapsedTime(&t, ctx->cc_ev0, ctx->cc_ev1));
-            ms += (double)t;
-        }
-        return SPK_OK;
-    };
-    DevBuf<unsigned int> flags;        // [changed, bad]
-    DevBuf<unsigned long long> count;
-    SPK_TRY(C.label.alloc((size_t)n_nodes + 1));
-    SPK_TRY(flags.alloc(2));
-    SPK_TRY(count.alloc(1));
-    if (!first) SPK_TRY(open());
-    k_cc_init<<<cc_grid(ctx, n_nodes, CC_THREADS), CC_THREADS, 0, st>>>(n_nodes, C.label.p);
-    SPK_HIP(hipGetLastError());
-    int rounds = 0;
-    bool quiet = n_edges == 0;
-    const unsigned hook_grid = cc_grid(ctx, n_edges, CC_CHUNK), node_grid = cc_grid(ctx, n_nodes, CC_THREADS);
-    while (!quiet) {
-        SPK_REQUIRE(rounds < CC_MAX_ROUNDS, SPK_E_LIMIT, "spk_components: no fixed point within 256 rounds");
-        if (rounds > 0) SPK_TRY(open());
-        SPK_HIP(hipMemsetAsync(flags.p, 0, 2 * sizeof(unsigned int), st));
-        if (rounds == 0) k_cc_hook<true><<<hook_grid, CC_THREADS, 0, st>>>(n_nodes, n_edges, eu, ev, C.label.p, flags.p);
-        else k_cc_hook<false><<<hook_grid, CC_THREADS, 0, st>>>(n_nodes, n_edges, eu, ev, C.label.p, flags.p);
-        SPK_HIP(hipGetLastError());
-        k_cc_jump<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, C.label.p, flags.p);
-        SPK_HIP(hipGetLastError());
-        unsigned int h[2] = {0u, 0u};
-        SPK_HIP(hipMemcpyAsync(h, flags.p, sizeof(h), hipMemcpyDeviceToHost, st));
-        SPK_TRY(close());
-        ++rounds;
-        SPK_REQUIRE(h[1] == 0u, bad_code, bad_msg);
-        quiet = h[0] == 0u;
-    }
-    if (rounds > 0) SPK_TRY(open());
-    SPK_HIP(hipMemsetAsync(count.p, 0, sizeof(unsigned long long), st));
-    k_cc_count<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, C.label.p, count.p);
-    SPK_HIP(hipGetLastError());
-    unsigned long long n_clusters = 0;
-    SPK_HIP(hipMemcpyAsync(&n_clusters, count.p, sizeof(n_clusters), hipMemcpyDeviceToHost, st));
-    SPK_TRY(close());
-    C.n_nodes = n_nodes;
-    C.n_edges = n_edges;
-    C.n_clusters = (int64_t)n_clusters;
-    C.rounds = rounds;
-    C.ms = ctx->timing ? ms : -1.0;
-    C.valid = true;
-    return SPK_OK;
-}
-
-static int cc_events(spk_ctx *ctx) {
-    if (!ctx->timing) return SPK_OK;
-    if (!ctx->cc_ev0) SPK_HIP(hipEventCreate(&ctx->cc_ev0));
-    if (!ctx->cc_ev1) SPK_HIP(hipEventCreate(&ctx->cc_ev1));
-    return SPK_OK;
-}
-
 // ---- the sweep: labels at several thresholds ------------------------------------------------------------------------
 constexpr int SW_BUCKETS = SPK_SWEEP_MAX_LEVELS + 1;  // the levels, and "in no level"
 
@@ -443,30 +373,105 @@ __global__ __launch_bounds__(CC_THREADS) void k_cm_scalars(int64_t n_nodes, cons
     }
 }
 
-// HIP-event time of the launches between open() and close(), summed; close() also synchronises the stream.
-struct CcTimer {
-    spk_ctx *ctx;
-    double ms = 0.0;
-    bool is_open = false;
-    int open() {
-        if (ctx->timing && !is_open) {
-            SPK_HIP(hipEventRecord(ctx->cc_ev0, ctx->stream));
-            is_open = true;
-        }
-        return SPK_OK;
+// ---- the round loop ---------------------------------------------------------------------------------------------------
+// Brings lab [n_nodes] to its fixed point and counts its clusters.  lab holds a start state for which invariants (1) and
+// (2) hold (k_cc_init, or a copy of the previous level's labels).  The rounds hook the edges (hu, hv) [hn] and, with
+// prev, the star edges (v, prev[v]); hn = 0 runs no round.  flags [2] and count [1] are the caller's device scratch.
+// T may be open around the caller's own launches (the edge build, the start state): they count into round 0's interval.
+static int cc_fixed_point(spk_ctx *ctx, int64_t n_nodes, const uint32_t *hu, const uint32_t *hv, int64_t hn,
+                          uint32_t *lab, const uint32_t *prev, unsigned int *flags, unsigned long long *count,
+                          int bad_code, const char *bad_msg, const char *limit_msg, StageTimer &T, int *out_rounds,
+                          int64_t *out_n_clusters) {
+    hipStream_t st = ctx->stream;
+    const unsigned hook_grid = cc_grid(ctx, hn, CC_CHUNK), node_grid = cc_grid(ctx, n_nodes, CC_THREADS);
+    int rounds = 0;
+    bool quiet = hn == 0;
+    while (!quiet) {
+        SPK_REQUIRE(rounds < CC_MAX_ROUNDS, SPK_E_LIMIT, limit_msg);
+        SPK_TRY(T.open());
+        SPK_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(unsigned int), st));
+        if (rounds == 0) k_cc_hook<true><<<hook_grid, CC_THREADS, 0, st>>>(n_nodes, hn, hu, hv, lab, flags);
+        else k_cc_hook<false><<<hook_grid, CC_THREADS, 0, st>>>(n_nodes, hn, hu, hv, lab, flags);
+        SPK_HIP(hipGetLastError());
+        if (prev) k_cc_jump_star<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab, prev, flags);
+        else k_cc_jump<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab, flags);
+        SPK_HIP(hipGetLastError());
+        unsigned int h[2] = {0u, 0u};  // [changed, bad]
+        SPK_HIP(hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, st));
+        SPK_TRY(T.close());
+        ++rounds;
+        SPK_REQUIRE(h[1] == 0u, bad_code, bad_msg);
+        quiet = h[0] == 0u;
     }
-    int close() {
-        if (is_open) SPK_HIP(hipEventRecord(ctx->cc_ev1, ctx->stream));
-        SPK_HIP(hipStreamSynchronize(ctx->stream));
-        if (is_open) {
-            float t = 0.f;
-            SPK_HIP(hipEventElapsedTime(&t, ctx->cc_ev0, ctx->cc_ev1));
-            ms += (double)t;
-            is_open = false;
-        }
-        return SPK_OK;
-    }
-};
+    SPK_TRY(T.open());
+    SPK_HIP(hipMemsetAsync(count, 0, sizeof(unsigned long long), st));
+    k_cc_count<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab, count);
+    SPK_HIP(hipGetLastError());
+    unsigned long long n_clusters = 0;
+    SPK_HIP(hipMemcpyAsync(&n_clusters, count, sizeof(n_clusters), hipMemcpyDeviceToHost, st));
+    SPK_TRY(T.close());
+    *out_rounds = rounds;
+    *out_n_clusters = (int64_t)n_clusters;
+    return SPK_OK;
+}
+
+// Labels of the graph (eu, ev) [n_edges] over n_nodes nodes into C, a local of the caller.  T: possibly open around
+// the caller's edge build.
+static int build_components(spk_ctx *ctx, int64_t n_nodes, int64_t n_edges, const uint32_t *eu, const uint32_t *ev,
+                            int bad_code, const char *bad_msg, StageTimer &T, Components &C) {
+    DevBuf<unsigned int> flags;
+    DevBuf<unsigned long long> count;
+    SPK_TRY(C.label.alloc((size_t)n_nodes + 1));
+    SPK_TRY(flags.alloc(2));
+    SPK_TRY(count.alloc(1));
+    SPK_TRY(T.open());
+    k_cc_init<<<cc_grid(ctx, n_nodes, CC_THREADS), CC_THREADS, 0, ctx->stream>>>(n_nodes, C.label.p);
+    SPK_HIP(hipGetLastError());
+    SPK_TRY(cc_fixed_point(ctx, n_nodes, eu, ev, n_edges, C.label.p, nullptr, flags.p, count.p, bad_code, bad_msg,
+                           "spk_components: no fixed point within 256 rounds", T, &C.rounds, &C.n_clusters));
+    C.n_nodes = n_nodes;
+    C.n_edges = n_edges;
+    C.ms = T.result();
+    C.valid = true;
+    return SPK_OK;
+}
+
+// The current selection's pairs as edges (eu, ev) [ctx->sel.n] over *n_nodes node ids, for spk_components and
+// spk_components_sweep (`who`): the state checks, then k_cc_edges inside an interval of T that it leaves open.
+// field: the score the caller goes on to read, SPK_SEL_ALL for none.
+static int selection_edges(spk_ctx *ctx, const char *who, int field, StageTimer &T, DevBuf<uint32_t> &eu,
+                           DevBuf<uint32_t> &ev, int64_t *n_nodes) {
+    const std::string w(who);
+    const Selection &S = ctx->sel;
+    SPK_REQUIRE(S.valid, SPK_E_STATE, w + ": no selection (run spk_select)");
+    SPK_REQUIRE(S.current(ctx), SPK_E_STATE, w + ": the pairs or codes changed since spk_select");
+    SPK_REQUIRE(S.has_rows, SPK_E_STATE, w + ": no pair rows (a loaded gamma table)");
+    SPK_REQUIRE(field != SPK_SEL_MP || S.has_mp, SPK_E_STATE, w + ": spk_select got no m / u");
+    SPK_REQUIRE(field != SPK_SEL_TF_MP || S.has_tf, SPK_E_STATE,
+                w + ": the selection was made without tf tables (spk_select)");
+    const NodeSpace N = node_space(ctx);
+    SPK_REQUIRE(N.n0 >= 0 && N.n1 >= 0, SPK_E_STATE, w + ": no tables");
+    SPK_REQUIRE(N.n_nodes <= (int64_t)UINT32_MAX, SPK_E_LIMIT, w + ": more than 2^32 - 1 nodes");
+    *n_nodes = N.n_nodes;
+    SPK_TRY(eu.alloc((size_t)S.n + 1));
+    SPK_TRY(ev.alloc((size_t)S.n + 1));
+    if (S.n == 0) return SPK_OK;
+    SPK_TRY(T.open());
+    EdgeArgs A{};
+    A.n_edges = S.n;
+    A.l = S.l.p;
+    A.r = S.r.p;
+    A.perm0 = N.t0->perm.p;
+    A.perm1 = N.t1->perm.p;
+    A.n0 = N.n0;
+    A.n1 = N.n1;
+    A.r_base = (uint32_t)N.r_base;
+    A.u = eu.p;
+    A.v = ev.p;
+    k_cc_edges<<<cc_grid(ctx, S.n, CC_THREADS), CC_THREADS, 0, ctx->stream>>>(A);
+    SPK_HIP(hipGetLastError());
+    return SPK_OK;
+}
 
 // L and the thresholds of a sweep call; `all`: the call has no scores (SPK_SEL_ALL, or host edges without thresholds)
 static int sweep_thresholds(const char *who, bool all, int n_thresholds, const double *thresholds, int *out_levels) {
@@ -488,11 +493,11 @@ static int sweep_thresholds(const char *who, bool all, int n_thresholds, const d
 }
 
 // The sweep of the graph (eu0, ev0) [n_raw] over n_nodes nodes into S, a local of the caller.  The edges' scores are
-// mpat[code[i]], score[i], or absent (L = 1; thresholds is not read then).  T: an event pair, possibly open around the
-// caller's edge build.
+// mpat[code[i]], score[i], or absent (L = 1; thresholds is not read then).  T: possibly open around the caller's edge
+// build.
 static int build_sweep(spk_ctx *ctx, int64_t n_nodes, int64_t n_raw, const uint32_t *eu0, const uint32_t *ev0,
                        const uint32_t *code, const double *mpat, const double *score, int L, const double *thresholds,
-                       int bad_code, const char *bad_msg, CcTimer &T, ComponentSweep &S) {
+                       int bad_code, const char *bad_msg, StageTimer &T, ComponentSweep &S) {
     hipStream_t st = ctx->stream;
     DevBuf<uint8_t> lev;
     DevBuf<unsigned long long> hist;  // [SW_BUCKETS] counts | [SW_BUCKETS] cursors | 1 cluster count
@@ -548,9 +553,9 @@ static int build_sweep(spk_ctx *ctx, int64_t n_nodes, int64_t n_raw, const uint3
     for (int k = 0; k < L; ++k) {
         uint32_t *lab = S.label.p + (size_t)k * (size_t)n_nodes;
         const uint32_t *prev = k ? lab - (size_t)n_nodes : nullptr;
+        // no new edge: no round, the previous level's labels are this level's
+        const int64_t hn = !S.cnt[k] ? 0 : prefix ? S.off[k] + S.cnt[k] : S.cnt[k];
         const uint32_t *hu = S.eu.p + (prefix ? 0 : S.off[k]), *hv = S.ev.p + (prefix ? 0 : S.off[k]);
-        const int64_t hn = prefix ? S.off[k] + S.cnt[k] : S.cnt[k];
-        const unsigned hook_grid = cc_grid(ctx, hn, CC_CHUNK);
         SPK_TRY(T.open());
         if (!prev) {
             k_cc_init<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab);
@@ -558,36 +563,11 @@ static int build_sweep(spk_ctx *ctx, int64_t n_nodes, int64_t n_raw, const uint3
         } else if (n_nodes > 0) {
             SPK_HIP(hipMemcpyAsync(lab, prev, (size_t)n_nodes * 4, hipMemcpyDeviceToDevice, st));
         }
-        int rounds = 0;
-        bool quiet = S.cnt[k] == 0;  // no new edge: the previous level's labels are this level's
-        while (!quiet) {
-            SPK_REQUIRE(rounds < CC_MAX_ROUNDS, SPK_E_LIMIT, "spk_components_sweep: no fixed point within 256 rounds");
-            SPK_TRY(T.open());
-            SPK_HIP(hipMemsetAsync(flags.p, 0, 2 * sizeof(unsigned int), st));
-            if (rounds == 0) k_cc_hook<true><<<hook_grid, CC_THREADS, 0, st>>>(n_nodes, hn, hu, hv, lab, flags.p);
-            else k_cc_hook<false><<<hook_grid, CC_THREADS, 0, st>>>(n_nodes, hn, hu, hv, lab, flags.p);
-            SPK_HIP(hipGetLastError());
-            if (prev && !prefix) k_cc_jump_star<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab, prev, flags.p);
-            else k_cc_jump<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab, flags.p);
-            SPK_HIP(hipGetLastError());
-            unsigned int f[2] = {0u, 0u};
-            SPK_HIP(hipMemcpyAsync(f, flags.p, sizeof(f), hipMemcpyDeviceToHost, st));
-            SPK_TRY(T.close());
-            ++rounds;
-            SPK_REQUIRE(f[1] == 0u, bad_code, bad_msg);
-            quiet = f[0] == 0u;
-        }
-        SPK_TRY(T.open());
-        SPK_HIP(hipMemsetAsync(count, 0, sizeof(unsigned long long), st));
-        k_cc_count<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab, count);
-        SPK_HIP(hipGetLastError());
-        unsigned long long n_clusters = 0;
-        SPK_HIP(hipMemcpyAsync(&n_clusters, count, sizeof(n_clusters), hipMemcpyDeviceToHost, st));
-        SPK_TRY(T.close());
-        S.n_clusters[k] = (int64_t)n_clusters;
-        S.rounds[k] = rounds;
+        SPK_TRY(cc_fixed_point(ctx, n_nodes, hu, hv, hn, lab, prefix ? nullptr : prev, flags.p, count, bad_code, bad_msg,
+                               "spk_components_sweep: no fixed point within 256 rounds", T, &S.rounds[k],
+                               &S.n_clusters[k]));
     }
-    S.ms = ctx->timing ? T.ms : -1.0;
+    S.ms = T.result();
     S.valid = true;
     return SPK_OK;
 }
@@ -608,40 +588,13 @@ extern "C" int spk_components(spk_ctx *ctx, int64_t *out_n_nodes, int64_t *out_n
     SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_components: null ctx");
     SPK_HIP(hipSetDevice(ctx->device));
     ctx->comp.clear();  // whatever happens below, the previous labels are gone
-    const Selection &S = ctx->sel;
-    SPK_REQUIRE(S.valid, SPK_E_STATE, "spk_components: no selection (run spk_select)");
-    SPK_REQUIRE(ctx->codes_valid && S.pairs_epoch == ctx->pairs_epoch && S.gamma_seq == ctx->gamma_seq &&
-                    S.fix_seq == ctx->codes_fix_seq,
-                SPK_E_STATE, "spk_components: the pairs or codes changed since spk_select");
-    SPK_REQUIRE(S.has_rows, SPK_E_STATE, "spk_components: no pair rows (a loaded gamma table)");
-    const bool two = ctx->link_type == SPK_LINK_ONLY;
-    const Table &t0 = ctx->table[0], &t1 = ctx->table[two ? 1 : 0];
-    SPK_REQUIRE(t0.n >= 0 && t1.n >= 0, SPK_E_STATE, "spk_components: no tables");
-    const int64_t n_nodes = t0.n + (two ? t1.n : 0), n_edges = S.n;
-    SPK_REQUIRE(n_nodes <= (int64_t)UINT32_MAX, SPK_E_LIMIT, "spk_components: more than 2^32 - 1 nodes");
-    SPK_TRY(cc_events(ctx));
     Components C;
+    StageTimer T{ctx};
     DevBuf<uint32_t> eu, ev;
-    SPK_TRY(eu.alloc((size_t)n_edges + 1));
-    SPK_TRY(ev.alloc((size_t)n_edges + 1));
-    if (ctx->timing) SPK_HIP(hipEventRecord(ctx->cc_ev0, ctx->stream));
-    if (n_edges > 0) {
-        EdgeArgs A{};
-        A.n_edges = n_edges;
-        A.l = S.l.p;
-        A.r = S.r.p;
-        A.perm0 = t0.perm.p;
-        A.perm1 = t1.perm.p;
-        A.n0 = t0.n;
-        A.n1 = t1.n;
-        A.r_base = two ? (uint32_t)t0.n : 0u;
-        A.u = eu.p;
-        A.v = ev.p;
-        k_cc_edges<<<cc_grid(ctx, n_edges, CC_THREADS), CC_THREADS, 0, ctx->stream>>>(A);
-        SPK_HIP(hipGetLastError());
-    }
-    SPK_TRY(build_components(ctx, n_nodes, n_edges, eu.p, ev.p, SPK_E_STATE,
-                             "spk_components: a selected pair names a row outside its table", true, C));
+    int64_t n_nodes = 0;
+    SPK_TRY(selection_edges(ctx, "spk_components", SPK_SEL_ALL, T, eu, ev, &n_nodes));
+    SPK_TRY(build_components(ctx, n_nodes, ctx->sel.n, eu.p, ev.p, SPK_E_STATE,
+                             "spk_components: a selected pair names a row outside its table", T, C));
     ctx->comp = std::move(C);
     if (out_n_nodes) *out_n_nodes = ctx->comp.n_nodes;
     if (out_n_clusters) *out_n_clusters = ctx->comp.n_clusters;
@@ -657,8 +610,8 @@ extern "C" int spk_components_edges(spk_ctx *ctx, int64_t n_nodes, int64_t n_edg
     SPK_REQUIRE(n_nodes >= 0 && n_edges >= 0, SPK_E_INVALID, "spk_components_edges: negative count");
     SPK_REQUIRE(n_edges == 0 || (u && v), SPK_E_INVALID, "spk_components_edges: null edges");
     SPK_REQUIRE(n_nodes <= (int64_t)UINT32_MAX, SPK_E_LIMIT, "spk_components_edges: more than 2^32 - 1 nodes");
-    SPK_TRY(cc_events(ctx));
     Components C;
+    StageTimer T{ctx};
     DevBuf<uint32_t> eu, ev;
     SPK_TRY(eu.alloc((size_t)n_edges + 1));
     SPK_TRY(ev.alloc((size_t)n_edges + 1));
@@ -668,7 +621,7 @@ extern "C" int spk_components_edges(spk_ctx *ctx, int64_t n_nodes, int64_t n_edg
         SPK_HIP(hipStreamSynchronize(ctx->stream));  // u / v are the caller's: done with them on every path below
     }
     SPK_TRY(build_components(ctx, n_nodes, n_edges, eu.p, ev.p, SPK_E_INVALID,
-                             "spk_components_edges: a node id is >= n_nodes", false, C));
+                             "spk_components_edges: a node id is >= n_nodes", T, C));
     ctx->comp = std::move(C);
     if (out_n_clusters) *out_n_clusters = ctx->comp.n_clusters;
     if (out_rounds) *out_rounds = ctx->comp.rounds;
@@ -718,43 +671,13 @@ extern "C" int spk_components_sweep(spk_ctx *ctx, int field, int n_thresholds, c
                 "spk_components_sweep: field is SPK_SEL_MP, SPK_SEL_TF_MP or SPK_SEL_ALL");
     int L = 0;
     SPK_TRY(sweep_thresholds("spk_components_sweep", field == SPK_SEL_ALL, n_thresholds, thresholds, &L));
-    const Selection &S = ctx->sel;
-    SPK_REQUIRE(S.valid, SPK_E_STATE, "spk_components_sweep: no selection (run spk_select)");
-    SPK_REQUIRE(ctx->codes_valid && S.pairs_epoch == ctx->pairs_epoch && S.gamma_seq == ctx->gamma_seq &&
-                    S.fix_seq == ctx->codes_fix_seq,
-                SPK_E_STATE, "spk_components_sweep: the pairs or codes changed since spk_select");
-    SPK_REQUIRE(S.has_rows, SPK_E_STATE, "spk_components_sweep: no pair rows (a loaded gamma table)");
-    SPK_REQUIRE(field != SPK_SEL_MP || S.has_mp, SPK_E_STATE, "spk_components_sweep: spk_select got no m / u");
-    SPK_REQUIRE(field != SPK_SEL_TF_MP || S.has_tf, SPK_E_STATE,
-                "spk_components_sweep: the selection was made without tf tables (spk_select)");
-    const bool two = ctx->link_type == SPK_LINK_ONLY;
-    const Table &t0 = ctx->table[0], &t1 = ctx->table[two ? 1 : 0];
-    SPK_REQUIRE(t0.n >= 0 && t1.n >= 0, SPK_E_STATE, "spk_components_sweep: no tables");
-    const int64_t n_nodes = t0.n + (two ? t1.n : 0), n_edges = S.n;
-    SPK_REQUIRE(n_nodes <= (int64_t)UINT32_MAX, SPK_E_LIMIT, "spk_components_sweep: more than 2^32 - 1 nodes");
-    SPK_TRY(cc_events(ctx));
     ComponentSweep W;
-    CcTimer T{ctx};
+    StageTimer T{ctx};
     DevBuf<uint32_t> eu, ev;
-    SPK_TRY(eu.alloc((size_t)n_edges + 1));
-    SPK_TRY(ev.alloc((size_t)n_edges + 1));
-    if (n_edges > 0) {
-        SPK_TRY(T.open());
-        EdgeArgs A{};
-        A.n_edges = n_edges;
-        A.l = S.l.p;
-        A.r = S.r.p;
-        A.perm0 = t0.perm.p;
-        A.perm1 = t1.perm.p;
-        A.n0 = t0.n;
-        A.n1 = t1.n;
-        A.r_base = two ? (uint32_t)t0.n : 0u;
-        A.u = eu.p;
-        A.v = ev.p;
-        k_cc_edges<<<cc_grid(ctx, n_edges, CC_THREADS), CC_THREADS, 0, ctx->stream>>>(A);
-        SPK_HIP(hipGetLastError());
-    }
-    SPK_TRY(build_sweep(ctx, n_nodes, n_edges, eu.p, ev.p, S.code.p, field == SPK_SEL_MP ? S.mpat.p : nullptr,
+    int64_t n_nodes = 0;
+    SPK_TRY(selection_edges(ctx, "spk_components_sweep", field, T, eu, ev, &n_nodes));
+    const Selection &S = ctx->sel;
+    SPK_TRY(build_sweep(ctx, n_nodes, S.n, eu.p, ev.p, S.code.p, field == SPK_SEL_MP ? S.mpat.p : nullptr,
                         field == SPK_SEL_TF_MP ? S.tf_mp.p : nullptr, L, thresholds, SPK_E_STATE,
                         "spk_components_sweep: a selected pair names a row outside its table", T, W));
     ctx->sweep = std::move(W);
@@ -776,9 +699,8 @@ extern "C" int spk_components_sweep_edges(spk_ctx *ctx, int64_t n_nodes, int64_t
     SPK_REQUIRE(n_nodes <= (int64_t)UINT32_MAX, SPK_E_LIMIT, "spk_components_sweep_edges: more than 2^32 - 1 nodes");
     int L = 0;
     SPK_TRY(sweep_thresholds("spk_components_sweep_edges", n_thresholds == 0, n_thresholds, thresholds, &L));
-    SPK_TRY(cc_events(ctx));
     ComponentSweep W;
-    CcTimer T{ctx};
+    StageTimer T{ctx};
     DevBuf<uint32_t> eu, ev;
     DevBuf<double> sc;
     const bool scored = n_thresholds > 0;
@@ -848,7 +770,6 @@ extern "C" int spk_cluster_metrics(spk_ctx *ctx, int level, int64_t *out3) {
     SPK_HIP(hipSetDevice(ctx->device));
     W.m_level = -1;  // whatever happens below, the previous level's metrics are gone
     W.m_ms = -1.0;
-    SPK_TRY(cc_events(ctx));
     hipStream_t st = ctx->stream;
     const int64_t n = W.n_nodes;
     DevBuf<unsigned long long> out;
@@ -857,7 +778,7 @@ extern "C" int spk_cluster_metrics(spk_ctx *ctx, int level, int64_t *out3) {
     SPK_TRY(W.size.alloc((size_t)n + 1));
     SPK_TRY(W.max_degree.alloc((size_t)n + 1));
     SPK_TRY(W.degree_sum.alloc((size_t)n + 1));
-    CcTimer T{ctx};
+    StageTimer T{ctx};
     SPK_TRY(T.open());
     SPK_HIP(hipMemsetAsync(out.p, 0, 3 * sizeof(unsigned long long), st));
     SPK_HIP(hipMemsetAsync(W.degree.p, 0, ((size_t)n + 1) * 4, st));
@@ -884,7 +805,7 @@ extern "C" int spk_cluster_metrics(spk_ctx *ctx, int level, int64_t *out3) {
     SPK_HIP(hipMemcpyAsync(h, out.p, sizeof(h), hipMemcpyDeviceToHost, st));
     SPK_TRY(T.close());
     W.m_level = level;
-    W.m_ms = ctx->timing ? T.ms : -1.0;
+    W.m_ms = T.result();
     if (out3)
         for (int i = 0; i < 3; ++i) out3[i] = (int64_t)h[i];
     return SPK_OK;

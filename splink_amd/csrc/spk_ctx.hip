@@ -512,7 +512,6 @@ void spk_ctx_destroy(spk_ctx *ctx) {
             (void)hipEventDestroy(s.xev1[k]);
         }
         if (s.ev_info) (void)hipEventDestroy(s.ev_info);
-        if (s.h_info) (void)hipHostFree(s.h_info);
     }
     if (ctx->split_ready) {
         (void)hipEventDestroy(ctx->ev_fork);
@@ -521,18 +520,9 @@ void spk_ctx_destroy(spk_ctx *ctx) {
     }
     if (ctx->gexec) (void)hipGraphExecDestroy(ctx->gexec);
     if (ctx->graph) (void)hipGraphDestroy(ctx->graph);
-    if (ctx->res_ev0) (void)hipEventDestroy(ctx->res_ev0);
-    if (ctx->res_ev1) (void)hipEventDestroy(ctx->res_ev1);
-    if (ctx->sel_ev0) (void)hipEventDestroy(ctx->sel_ev0);
-    if (ctx->sel_ev1) (void)hipEventDestroy(ctx->sel_ev1);
-    if (ctx->cc_ev0) (void)hipEventDestroy(ctx->cc_ev0);
-    if (ctx->cc_ev1) (void)hipEventDestroy(ctx->cc_ev1);
-    if (ctx->lab_ev0) (void)hipEventDestroy(ctx->lab_ev0);
-    if (ctx->lab_ev1) (void)hipEventDestroy(ctx->lab_ev1);
-    if (ctx->smp_ev0) (void)hipEventDestroy(ctx->smp_ev0);
-    if (ctx->smp_ev1) (void)hipEventDestroy(ctx->smp_ev1);
+    if (ctx->stage_ev0) (void)hipEventDestroy(ctx->stage_ev0);
+    if (ctx->stage_ev1) (void)hipEventDestroy(ctx->stage_ev1);
     if (ctx->ev_stats) (void)hipEventDestroy(ctx->ev_stats);
-    if (ctx->h_stats) (void)hipHostFree(ctx->h_stats);
     hipStream_t own = ctx->own_stream;
     delete ctx;
     if (own) (void)hipStreamDestroy(own);

@@ -985,7 +985,7 @@ static int enqueue_histogram(spk_ctx *ctx, uint64_t *d_hist) {
 
 static int em_buffers(spk_ctx *ctx, int n_stats) {
     SPK_TRY(ctx->stats.alloc((size_t)n_stats));
-    SPK_TRY(ctx->pinned_stats(n_stats));
+    SPK_TRY(ctx->h_stats.grow(n_stats));
     SPK_TRY(ctx->mpat.alloc((size_t)ctx->n_patterns));
     SPK_TRY(ctx->llpat.alloc((size_t)ctx->n_patterns));
     SPK_TRY(ctx->cpat.alloc((size_t)ctx->n_patterns));
@@ -1000,9 +1000,9 @@ static int finalize_from(spk_ctx *ctx, const unsigned long long *h, const PatArg
     k_em_finalize<<<1, EF_THREADS, 0, ctx->stream>>>(A, h, ctx->mpat.p, ctx->llpat.p, ctx->cpat.p, ctx->stats.p);
     SPK_HIP(hipGetLastError());
     SPK_TRY(ctx->end(K_EMFIN));
-    SPK_HIP(hipMemcpyAsync(ctx->h_stats, ctx->stats.p, (size_t)n_stats * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SPK_HIP(hipMemcpyAsync(ctx->h_stats.p, ctx->stats.p, (size_t)n_stats * 8, hipMemcpyDeviceToHost, ctx->stream));
     SPK_HIP(hipStreamSynchronize(ctx->stream));
-    std::memcpy(out_stats, ctx->h_stats, (size_t)n_stats * 8);
+    std::memcpy(out_stats, ctx->h_stats.p, (size_t)n_stats * 8);
     return SPK_OK;
 }
 
@@ -1084,7 +1084,7 @@ static int enqueue_em(spk_ctx *ctx) {
         SPK_TRY(ctx->end(K_EMHIST));
         ctx->ev_used[0][K_EMFIN] = ctx->ev_used[1][K_EMFIN] = false;  // one launch: the E-step is inside it
     }
-    SPK_HIP(hipMemcpyAsync(ctx->h_stats, ctx->stats.p, (size_t)n_stats * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SPK_HIP(hipMemcpyAsync(ctx->h_stats.p, ctx->stats.p, (size_t)n_stats * 8, hipMemcpyDeviceToHost, ctx->stream));
     SPK_HIP(hipEventRecord(ctx->ev_stats, ctx->stream));
     return SPK_OK;
 }
@@ -1149,7 +1149,7 @@ extern "C" int spk_em_finalize_start(spk_ctx *ctx, const uint64_t *d_hist, doubl
                                                      ctx->mpat.p, ctx->llpat.p, ctx->cpat.p, ctx->stats.p);
     SPK_HIP(hipGetLastError());
     SPK_TRY(ctx->end(K_EMFIN));
-    SPK_HIP(hipMemcpyAsync(ctx->h_stats, ctx->stats.p, (size_t)n_stats * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SPK_HIP(hipMemcpyAsync(ctx->h_stats.p, ctx->stats.p, (size_t)n_stats * 8, hipMemcpyDeviceToHost, ctx->stream));
     SPK_HIP(hipEventRecord(ctx->ev_stats, ctx->stream));
     ctx->em_n_stats = n_stats;
     ctx->em_kind = 1;
@@ -1166,7 +1166,7 @@ extern "C" int spk_em_iteration_wait(spk_ctx *ctx, double *out_stats, int n_stat
     // the codes' info block first: a correction of the codes re-enqueues this iteration (settle_gammas)
     if (ctx->em_seq == ctx->gamma_seq) SPK_TRY(settle_gammas(ctx, nullptr));
     SPK_HIP(hipEventSynchronize(ctx->ev_stats));
-    std::memcpy(out_stats, ctx->h_stats, (size_t)n_stats * 8);
+    std::memcpy(out_stats, ctx->h_stats.p, (size_t)n_stats * 8);
     ctx->em_pending = false;
     return SPK_OK;
 }

@@ -2477,7 +2477,7 @@ static int enqueue_phase(spk_ctx *ctx, Slot &S, int64_t cap, bool skip = false) 
 
 // A window's info block to the host, behind what `stream` holds so far.
 static int read_info(spk_ctx *ctx, Slot &S, hipStream_t stream) {
-    SPK_HIP(hipMemcpyAsync(S.h_info, S.xinfo.p, (size_t)ctx->gcols->n_all * 8, hipMemcpyDeviceToHost, stream));
+    SPK_HIP(hipMemcpyAsync(S.h_info.p, S.xinfo.p, (size_t)ctx->gcols->n_all * 8, hipMemcpyDeviceToHost, stream));
     SPK_HIP(hipEventRecord(S.ev_info, stream));
     return SPK_OK;
 }
@@ -2543,20 +2543,20 @@ static int settle_slot(spk_ctx *ctx, Slot &S, bool *fixed) {
     const GammaCols &C = *ctx->gcols;
     GammaPlan &G = *S.gplan;
     const int K = C.K;
-    if (S.h_info[2 * K]) {
+    if (S.h_info.p[2 * K]) {
         // the exact lists did not fit: nothing of the phase ran; grow them and run the phase again
-        const int64_t cap = S.h_info[2 * K + 1];
+        const int64_t cap = S.h_info.p[2 * K + 1];
         SPK_HIP(hipMemsetAsync(S.xinfo.p + C.n_info, 0, (size_t)(C.n_cnt + 2) * 8, S.stream));
         SPK_TRY(enqueue_phase(ctx, S, cap));
         SPK_TRY(read_info(ctx, S, S.stream));
         SPK_HIP(hipStreamSynchronize(S.stream));
         *fixed = true;
-        if (S.h_info[2 * K]) {
+        if (S.h_info.p[2 * K]) {
             ctx->codes_valid = false;
             SPK_REQUIRE(false, SPK_E_STATE, "spk_gammas: exact work list sizing failed");
         }
     }
-    const unsigned int *h_slow = reinterpret_cast<const unsigned int *>(S.h_info + C.n_info);
+    const unsigned int *h_slow = reinterpret_cast<const unsigned int *>(S.h_info.p + C.n_info);
     {  // slow-list kernels this call left out although the exact pass did list cells: run them now
         bool ran = false;
         ColSet jk{};
@@ -2577,7 +2577,7 @@ static int settle_slot(spk_ctx *ctx, Slot &S, bool *fixed) {
         G.slow_skipped.assign((size_t)K, 0);
     }
     int err = 0;
-    std::memcpy(&err, S.h_info + C.n_info + C.n_cnt, sizeof(err));
+    std::memcpy(&err, S.h_info.p + C.n_info + C.n_cnt, sizeof(err));
     if (err & 2) {
         ctx->codes_valid = false;
         SPK_REQUIRE(false, SPK_E_INVALID, "spk_gammas: unknown instruction");
@@ -2585,13 +2585,13 @@ static int settle_slot(spk_ctx *ctx, Slot &S, bool *fixed) {
     int64_t n_huge = 0, max_huge = 0;
     G.deferred = 0;
     for (int k = 0; k < K; ++k) {
-        G.exact[k] = S.h_info[K + k];
+        G.exact[k] = S.h_info.p[K + k];
         G.slow_seen[k] = h_slow[k] ? 1 : 0;
         G.deferred += h_slow[k];
         n_huge += h_slow[2 * K + k];
         max_huge = std::max<int64_t>(max_huge, h_slow[2 * K + k]);
     }
-    G.xbase.assign(S.h_info, S.h_info + K);
+    G.xbase.assign(S.h_info.p, S.h_info.p + K);
     if (n_huge) {  // cells with a string longer than SLOW_LIMIT units (none in the benchmark configs)
         Scratch Sc;
         DevBuf<uint8_t> scratch;
@@ -2599,7 +2599,7 @@ static int settle_slot(spk_ctx *ctx, Slot &S, bool *fixed) {
         for (int k = 0; k < K; ++k) {
             const int64_t nk = h_slow[2 * K + k];
             if (!nk) continue;
-            const int32_t *items = (C.huge_in_slow[k] ? G.A.slow : S.xlist.p) + S.h_info[k];  // + xinfo[k]
+            const int32_t *items = (C.huge_in_slow[k] ? G.A.slow : S.xlist.p) + S.h_info.p[k];  // + xinfo[k]
             k_gamma_huge<<<(unsigned)(Sc.n_slots / 64), 64, 0, S.stream>>>(G.A, k, items, nk, Sc);
             SPK_HIP(hipGetLastError());
         }
@@ -2929,7 +2929,7 @@ static int alloc_slots(spk_ctx *ctx, const WindowLayout &L, const GammaCols &C, 
         SPK_TRY(S.work.alloc((size_t)std::max(n_lists, 1) * (size_t)L.W + 1));
         SPK_TRY(S.region_count.alloc((size_t)C.K * L.n_regions_max));
         SPK_TRY(S.xinfo.alloc((size_t)C.n_all));
-        SPK_TRY(S.pinned_info((size_t)C.n_all));
+        SPK_TRY(S.h_info.grow((size_t)C.n_all));
         SPK_TRY(S.xpref.alloc((size_t)C.K * (L.n_regions_max + 1)));
         if (!S.gplan) S.gplan = new GammaPlan();
     }

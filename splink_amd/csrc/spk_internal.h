@@ -164,6 +164,34 @@ struct DevBuf {
     }
 };
 
+// A pinned host buffer that only grows; growing drops what it held.  Freed with its owner: a context is deleted with
+// its device set (spk_ctx_destroy).
+template <typename T>
+struct PinnedBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    int grow(size_t count) {
+        if (count <= n) return SPK_OK;
+        release();
+        if (hipHostMalloc(reinterpret_cast<void **>(&p), count * sizeof(T), hipHostMallocDefault) != hipSuccess) {
+            p = nullptr;
+            set_error("hipHostMalloc failed");
+            return SPK_E_OOM;
+        }
+        n = count;
+        return SPK_OK;
+    }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    ~PinnedBuf() { release(); }
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+};
+
 struct Column {
     ColKind kind = COL_NONE;
     DevBuf<uint16_t> units;
@@ -264,6 +292,7 @@ struct Selection {
     std::vector<int64_t> stride;
     uint64_t pairs_epoch = 0, gamma_seq = 0, fix_seq = 0;
     double ms = -1.0;        // device milliseconds of its kernels (timing on), -1 = none
+    bool current(const spk_ctx *ctx) const;  // taken from the context's present pairs and codes
     void clear() { *this = Selection(); }
 };
 
@@ -338,9 +367,8 @@ struct spk_ctx {
     void set_rule_ranges(const std::vector<int64_t> &rule_base, int64_t n_out);
     // the last spk_block_residual: key candidates it enumerated on this shard (after the link-type predicate and
     // the exclusion by earlier key-only rules), -1 = none yet; device milliseconds of its compaction (timing on:
-    // the sum over HIP event pairs around each rule's count kernel + scan and around the emit kernels), -1 = none
+    // the sum of the intervals around each rule's count kernel + scan and around the emit kernels), -1 = none
     int64_t res_enumerated = -1;
-    hipEvent_t res_ev0 = nullptr, res_ev1 = nullptr;
     double res_filter_ms = -1.0;
 
     // packed comparison-vector codes
@@ -412,21 +440,7 @@ struct spk_ctx {
         spk::DevBuf<int64_t> xinfo;       // [col_base K | col_count K | overflow | total] (k_prefix)
         spk::DevBuf<unsigned int> region_count;  // [K][regions] filter work-list lengths
         int64_t xcap = 0;
-        int64_t *h_info = nullptr;        // pinned readback of xinfo + slow counts
-        size_t h_info_n = 0;
-        int pinned_info(size_t n) {
-            if (n <= h_info_n) return SPK_OK;
-            if (h_info) (void)hipHostFree(h_info);
-            h_info = nullptr;
-            h_info_n = 0;
-            if (hipHostMalloc(reinterpret_cast<void **>(&h_info), n * 8, hipHostMallocDefault) != hipSuccess) {
-                h_info = nullptr;
-                spk::set_error("hipHostMalloc failed");
-                return SPK_E_OOM;
-            }
-            h_info_n = n;
-            return SPK_OK;
-        }
+        spk::PinnedBuf<int64_t> h_info;   // pinned readback of xinfo + slow counts
         hipEvent_t ev_info = nullptr;     // after the info-block readback
         // the window's plan (its arguments, what its settlement read), and whether its info block still has to be
         // read (settle_gammas, at the next synchronisation of a consumer)
@@ -463,23 +477,9 @@ struct spk_ctx {
     spk::DevBuf<uint32_t> em_row;         // its reduction rows (kept zero between launches)
     spk::DevBuf<int32_t> em_hot;          // the pattern it does not count with R < 64 lane copies (-1: none yet)
     std::vector<int64_t> em_hot_key;      // the pair set / pattern space it was found for
-    double *h_stats = nullptr;        // pinned host copy of the statistics vector
-    size_t h_stats_n = 0;
+    spk::PinnedBuf<double> h_stats;   // pinned host copy of the statistics vector
     int n_cu = 256;                   // compute units of the device (grid sizing)
     int lds_per_block = 64 * 1024;    // LDS a workgroup may allocate (device attribute)
-    int pinned_stats(size_t n) {
-        if (n <= h_stats_n) return SPK_OK;
-        if (h_stats) (void)hipHostFree(h_stats);
-        h_stats = nullptr;
-        h_stats_n = 0;
-        if (hipHostMalloc(reinterpret_cast<void **>(&h_stats), n * 8, hipHostMallocDefault) != hipSuccess) {
-            h_stats = nullptr;
-            spk::set_error("hipHostMalloc failed");
-            return SPK_E_OOM;
-        }
-        h_stats_n = n;
-        return SPK_OK;
-    }
     spk::DevBuf<double> mp;  // per-pair scores (final E-step)
     // tf_adjusted_match_prob kept on the device (spk_tf_apply* with out_tf_mp = NULL): pairs [tf_start, tf_start +
     // tf_count) of the pair set tf_epoch (pairs_epoch then); read back by range with spk_tf_copy
@@ -493,35 +493,31 @@ struct spk_ctx {
     ~spk_ctx();  // spk_gamma.hip, where the plans are complete types
     bool mpat_valid = false;  // mpat_score holds the mp per pattern of the current codes' last spk_score
     uint64_t score_seq = 0;   // spk_score calls so far (the tf runs depend on their mp per pattern)
-    // spk_select: the last selection's survivors, the HIP events around its kernels (created on first use with
-    // timing on), and the code corrections settle_gammas has made so far (a selection taken before one is stale)
+    // spk_select: the last selection's survivors, and the code corrections settle_gammas has made so far (a selection
+    // taken before one is stale)
     spk::Selection sel;
-    hipEvent_t sel_ev0 = nullptr, sel_ev1 = nullptr;
     uint64_t codes_fix_seq = 0;
     // the last spk_select_best (spk_best.hip): survivors before, pairs kept (-1: none, or it failed), device milliseconds
     int64_t best_before = -1, best_kept = -1;
     double best_ms = -1.0;
-    // spk_components*: the last labels and the HIP events around its launches (created on first use with timing on)
+    // spk_components*: the last labels
     spk::Components comp;
-    hipEvent_t cc_ev0 = nullptr, cc_ev1 = nullptr;
-    // spk_components_sweep*: the last sweep (it shares the components' events), and which edges a level's rounds
-    // hook: 0 the level's new edges plus a star edge per node, 1 every edge up to the level (spk_components_sweep_set_mode)
+    // spk_components_sweep*: the last sweep, and which edges a level's rounds hook: 0 the level's new edges plus a star
+    // edge per node, 1 every edge up to the level (spk_components_sweep_set_mode)
     spk::ComponentSweep sweep;
     int sweep_mode = 0;
     bool metrics_edge_agg = true;  // spk_cluster_metrics' edge pass counts inside the wave (spk_cluster_metrics_set_mode 0: off)
-    // the last spk_label_histogram (spk_labels.hip): pairs counted (-1: none, or it failed), device milliseconds, and
-    // the HIP events around its launches (created on first use with timing on); its buffers live for the call only
+    // the last spk_label_histogram (spk_labels.hip): pairs counted (-1: none, or it failed), device milliseconds of
+    // its launches; its buffers live for the call only
     int64_t label_pairs = -1;
     double label_ms = -1.0;
-    hipEvent_t lab_ev0 = nullptr, lab_ev1 = nullptr;
     // the last spk_pairs_sample (spk_sample.hip): draws generated and pairs kept (-1: none, or it failed), device
-    // milliseconds of its launches, and the HIP events around them (created on first use with timing on)
+    // milliseconds of its launches
     int64_t sample_draws = -1, sample_kept = -1;
     double sample_ms = -1.0;
-    hipEvent_t smp_ev0 = nullptr, smp_ev1 = nullptr;
     // the last spk_block_profile (spk_block.hip): ordinals its count pass enumerated (-1: none, or it failed), HIP-event
-    // milliseconds of its key-level part and of its enumeration (timing on, else -1); its buffers and events live for
-    // the call only.  profile_cut: the largest-blocks step sorts only the blocks of the top bins (0: every block)
+    // milliseconds of its key-level part and of its enumeration (timing on, else -1); its buffers live for the call
+    // only.  profile_cut: the largest-blocks step sorts only the blocks of the top bins (0: every block)
     int64_t profile_ordinals = -1;
     double profile_key_ms = -1.0, profile_enum_ms = -1.0;
     bool profile_cut = true;
@@ -556,6 +552,8 @@ struct spk_ctx {
     hipEvent_t ev0[2][spk::K_COUNT] = {}, ev1[2][spk::K_COUNT] = {};
     bool ev_used[2][spk::K_COUNT] = {};
     int ev_slot[spk::K_COUNT] = {};
+    // the one event pair of the stages that run after scoring (spk::StageTimer), created on first use with timing on
+    hipEvent_t stage_ev0 = nullptr, stage_ev1 = nullptr;
 
     // HIP events around column k's exact-pass launch in a window (timing_exact)
     int xbegin(Slot &s, int k);
@@ -567,6 +565,65 @@ struct spk_ctx {
 };
 
 namespace spk {
+inline bool Selection::current(const spk_ctx *ctx) const {
+    return ctx->codes_valid && pairs_epoch == ctx->pairs_epoch && gamma_seq == ctx->gamma_seq &&
+           fix_seq == ctx->codes_fix_seq;
+}
+
+// The node ids of the context's link type, as spk_select_best and spk_components* number them: the l side's input rows
+// are [0, n0), the r side's [r_base, r_base + n1).  Not link_only: both sides are table 0 and r_base = 0.  A table
+// that is not loaded has n = -1; the caller checks n0 and n1 under its own name before it uses the rest.
+struct NodeSpace {
+    const Table *t0, *t1;
+    int64_t n0, n1, r_base, n_nodes;
+};
+inline NodeSpace node_space(spk_ctx *ctx) {
+    const Table &t0 = ctx->table[0], &t1 = ctx->side_table(1);
+    const bool two = ctx->link_type == SPK_LINK_ONLY;
+    return NodeSpace{&t0, &t1, t0.n, t1.n, two ? t0.n : 0, t0.n + (two ? t1.n : 0)};
+}
+
+// HIP-event stopwatch of a stage that runs after scoring, over the context's one event pair: the sum of the intervals
+// between open() and close().  One pair is enough because every user is a top-level entry that has read its last
+// interval, behind a stream synchronisation, before it returns, and none calls another while an interval is open
+// (pattern_mp_table and the residual path's gamma pass time themselves with ev0 / ev1[K_*]).  With timing off
+// nothing is created or recorded.
+struct StageTimer {
+    spk_ctx *ctx;
+    double ms = 0.0;
+    enum { IDLE, OPEN, STOPPED } state = IDLE;
+    int open() {  // starts an interval unless one is open already
+        if (!ctx->timing || state != IDLE) return SPK_OK;
+        if (!ctx->stage_ev0) SPK_HIP(hipEventCreate(&ctx->stage_ev0));
+        if (!ctx->stage_ev1) SPK_HIP(hipEventCreate(&ctx->stage_ev1));
+        SPK_HIP(hipEventRecord(ctx->stage_ev0, ctx->stream));
+        state = OPEN;
+        return SPK_OK;
+    }
+    // The two halves of close(), for a caller that enqueues read-backs behind the interval's end and synchronises
+    // itself (scan_total): stop() ends the open interval, add() follows the synchronisation.
+    int stop() {
+        if (state != OPEN) return SPK_OK;
+        SPK_HIP(hipEventRecord(ctx->stage_ev1, ctx->stream));
+        state = STOPPED;
+        return SPK_OK;
+    }
+    int add() {
+        if (state != STOPPED) return SPK_OK;
+        float t = 0.f;
+        SPK_HIP(hipEventElapsedTime(&t, ctx->stage_ev0, ctx->stage_ev1));
+        ms += (double)t;
+        state = IDLE;
+        return SPK_OK;
+    }
+    int close() {  // ends the open interval, synchronises the stream (with timing off too), adds the interval
+        SPK_TRY(stop());
+        SPK_HIP(hipStreamSynchronize(ctx->stream));
+        return add();
+    }
+    double result() const { return ctx->timing ? ms : -1.0; }  // what the *_info calls report
+};
+
 int ensure_desc(spk_ctx *ctx, Table &t);
 // Finishes the last spk_gammas (work-list overflow, huge pass) once the stream is synchronised;
 // *fixed = true when codes changed after spk_gammas returned.  No-op when nothing is pending.

@@ -221,29 +221,16 @@ extern "C" int spk_label_histogram(spk_ctx *ctx, const int64_t *ids_side0, const
     SPK_TRY(hist.alloc((size_t)3 * n_pat));
     SPK_TRY(bad.alloc(1));
     if (out_pattern_mp) SPK_TRY(mpat.alloc((size_t)n_pat));
-    if (ctx->timing) {
-        if (!ctx->lab_ev0) SPK_HIP(hipEventCreate(&ctx->lab_ev0));
-        if (!ctx->lab_ev1) SPK_HIP(hipEventCreate(&ctx->lab_ev1));
-    }
     SPK_HIP(hipMemsetAsync(bad.p, 0, sizeof(unsigned int), st));
-    double ms = 0.0;
-    auto lap = [&]() -> int {  // after a synchronisation: add the last event pair
-        if (!ctx->timing) return SPK_OK;
-        float t = 0.f;
-        SPK_HIP(hipEventElapsedTime(&t, ctx->lab_ev0, ctx->lab_ev1));
-        ms += (double)t;
-        return SPK_OK;
-    };
-    // ---- the label ids, narrowed to 32 bits on the device (the upload itself is not a launch: outside the events)
+    StageTimer T{ctx};
+    // ---- the label ids, narrowed to 32 bits on the device (the upload itself is not a launch: outside the interval)
     auto narrow = [&](const int64_t *ids, int64_t n, int32_t *out) -> int {
         if (n == 0) return SPK_OK;
         SPK_HIP(hipMemcpyAsync(wide.p, ids, (size_t)n * 8, hipMemcpyHostToDevice, st));
-        if (ctx->timing) SPK_HIP(hipEventRecord(ctx->lab_ev0, st));
+        SPK_TRY(T.open());
         k_label_narrow<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, wide.p, out, bad.p);
         SPK_HIP(hipGetLastError());
-        if (ctx->timing) SPK_HIP(hipEventRecord(ctx->lab_ev1, st));
-        SPK_HIP(hipStreamSynchronize(st));  // the next upload reuses `wide`; the source is borrowed for the call
-        return lap();
+        return T.close();  // synchronises: the next upload reuses `wide`; the source is borrowed for the call
     };
     SPK_TRY(narrow(ids_side0, n0, lab0.p));
     if (second) SPK_TRY(narrow(ids_side1, n1, lab1.p));
@@ -252,7 +239,7 @@ extern "C" int spk_label_histogram(spk_ctx *ctx, const int64_t *ids_side0, const
     SPK_HIP(hipStreamSynchronize(st));
     SPK_REQUIRE(h_bad == 0u, SPK_E_INVALID, "spk_label_histogram: a label id of 2^31 or more");
     // ---- mp per pattern (spk_score's own kernel and arguments) and the counts
-    if (ctx->timing) SPK_HIP(hipEventRecord(ctx->lab_ev0, st));
+    SPK_TRY(T.open());
     if (out_pattern_mp) SPK_TRY(pattern_mp_table(ctx, lambda, one_minus, m, u, mpat.p));
     SPK_HIP(hipMemsetAsync(hist.p, 0, (size_t)3 * n_pat * 8, st));
     if (P > 0) {
@@ -271,16 +258,16 @@ extern "C" int spk_label_histogram(spk_ctx *ctx, const int64_t *ids_side0, const
         if (ctx->code_bytes == 2) SPK_TRY(launch_label_hist<uint16_t>(ctx, A, lds));
         else SPK_TRY(launch_label_hist<uint32_t>(ctx, A, lds));
     }
-    if (ctx->timing) SPK_HIP(hipEventRecord(ctx->lab_ev1, st));
+    SPK_TRY(T.stop());  // the read-backs are no launches
     SPK_HIP(hipMemcpyAsync(&h_bad, bad.p, sizeof(h_bad), hipMemcpyDeviceToHost, st));
     SPK_HIP(hipMemcpyAsync(out_counts, hist.p, (size_t)3 * n_pat * 8, hipMemcpyDeviceToHost, st));
     if (out_pattern_mp) SPK_HIP(hipMemcpyAsync(out_pattern_mp, mpat.p, (size_t)n_pat * 8, hipMemcpyDeviceToHost, st));
     SPK_HIP(hipStreamSynchronize(st));
-    SPK_TRY(lap());
+    SPK_TRY(T.add());
     SPK_REQUIRE(h_bad == 0u, SPK_E_STATE,
                 "spk_label_histogram: a pair names a row outside its table or a code outside the pattern space");
     ctx->label_pairs = P;
-    ctx->label_ms = ctx->timing ? ms : -1.0;
+    ctx->label_ms = T.result();
     return SPK_OK;
 }
 

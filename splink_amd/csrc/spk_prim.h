@@ -76,13 +76,13 @@ struct CountScan {
 };
 
 // Enqueued behind the kernel that writes S.count[0 .. n): the scan, then the read-back of the total.  Returns with
-// the stream synchronised; `scanned` (optional) is recorded between the scan and the read-back.
-inline int scan_total(spk_ctx *ctx, CountScan &S, DevBuf<uint8_t> &tmp, hipEvent_t scanned = nullptr) {
+// the stream synchronised; the open interval of `T` (optional) ends between the scan and the read-back and is added.
+inline int scan_total(spk_ctx *ctx, CountScan &S, DevBuf<uint8_t> &tmp, StageTimer *T = nullptr) {
     SPK_TRY(exclusive_scan(ctx->stream, tmp, S.count.p, S.off.p, S.n + 1));
-    if (scanned) SPK_HIP(hipEventRecord(scanned, ctx->stream));
+    if (T) SPK_TRY(T->stop());
     SPK_HIP(hipMemcpyAsync(&S.total, S.off.p + S.n, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     SPK_HIP(hipStreamSynchronize(ctx->stream));
-    return SPK_OK;
+    return T ? T->add() : SPK_OK;
 }
 
 // *out = in[0] + .. + in[n - 1], summed as Out

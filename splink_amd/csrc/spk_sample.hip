@@ -175,18 +175,7 @@ extern "C" int spk_pairs_sample(spk_ctx *ctx, int link_type, uint64_t seed, int6
     const int64_t draws = none ? 0 : n_draws;
     const int64_t chunks = (draws + SM_CHUNK - 1) / SM_CHUNK;
     hipStream_t st = ctx->stream;
-    if (ctx->timing) {
-        if (!ctx->smp_ev0) SPK_HIP(hipEventCreate(&ctx->smp_ev0));
-        if (!ctx->smp_ev1) SPK_HIP(hipEventCreate(&ctx->smp_ev1));
-    }
-    double ms = 0.0;
-    auto lap = [&]() -> int {  // after a synchronisation: add the last event pair
-        if (!ctx->timing) return SPK_OK;
-        float t = 0.f;
-        SPK_HIP(hipEventElapsedTime(&t, ctx->smp_ev0, ctx->smp_ev1));
-        ms += (double)t;
-        return SPK_OK;
-    };
+    StageTimer T{ctx};
     SampleArgs A{};
     int64_t n_out = 0;
     CountScan counts;
@@ -206,11 +195,10 @@ extern "C" int spk_pairs_sample(spk_ctx *ctx, int link_type, uint64_t seed, int6
         if (!link_only) {
             SPK_TRY(counts.alloc(ctx, chunks));
             A.chunk_count = counts.count.p;
-            if (ctx->timing) SPK_HIP(hipEventRecord(ctx->smp_ev0, st));
+            SPK_TRY(T.open());
             k_sample<false><<<(unsigned)chunks, SM_THREADS, 0, st>>>(A);
             SPK_HIP(hipGetLastError());
-            SPK_TRY(scan_total(ctx, counts, tmp, ctx->timing ? ctx->smp_ev1 : nullptr));
-            SPK_TRY(lap());
+            SPK_TRY(scan_total(ctx, counts, tmp, &T));
             n_out = counts.total;
             SPK_REQUIRE(n_out >= 0 && n_out <= draws, SPK_E_STATE, "spk_pairs_sample: survivor count");
             A.chunk_count = nullptr;
@@ -222,20 +210,18 @@ extern "C" int spk_pairs_sample(spk_ctx *ctx, int link_type, uint64_t seed, int6
     if (draws > 0) {
         A.out_l = ctx->pl.p;
         A.out_r = ctx->pr.p;
-        if (ctx->timing) SPK_HIP(hipEventRecord(ctx->smp_ev0, st));
+        SPK_TRY(T.open());
         k_sample<true><<<(unsigned)chunks, SM_THREADS, 0, st>>>(A);
         SPK_HIP(hipGetLastError());
-        if (ctx->timing) SPK_HIP(hipEventRecord(ctx->smp_ev1, st));
     }
-    SPK_HIP(hipStreamSynchronize(st));
-    if (draws > 0) SPK_TRY(lap());
+    SPK_TRY(T.close());  // synchronises, draws or none
     ctx->pairs_replaced(n_out);
     ctx->pair_terms.clear();  // as a loaded list: no rules, so no key terms, no rule ranges, no views
     ctx->set_rule_ranges({}, n_out);
     commit.done = true;
     ctx->sample_draws = n_draws;
     ctx->sample_kept = n_out;
-    ctx->sample_ms = ctx->timing ? ms : -1.0;
+    ctx->sample_ms = T.result();
     if (out_n_pairs) *out_n_pairs = n_out;
     return SPK_OK;
 }

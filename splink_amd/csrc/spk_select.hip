@@ -497,18 +497,7 @@ static int build_selection(spk_ctx *ctx, double lambda, double one_minus, const 
     S.pairs_epoch = ctx->pairs_epoch;
     S.gamma_seq = ctx->gamma_seq;
     S.fix_seq = ctx->codes_fix_seq;
-    if (ctx->timing) {
-        if (!ctx->sel_ev0) SPK_HIP(hipEventCreate(&ctx->sel_ev0));
-        if (!ctx->sel_ev1) SPK_HIP(hipEventCreate(&ctx->sel_ev1));
-    }
-    double ms = 0.0;
-    auto lap = [&]() -> int {  // after a synchronisation: add the last event pair
-        if (!ctx->timing) return SPK_OK;
-        float t = 0.f;
-        SPK_HIP(hipEventElapsedTime(&t, ctx->sel_ev0, ctx->sel_ev1));
-        ms += (double)t;
-        return SPK_OK;
-    };
+    StageTimer T{ctx};
     const int64_t words64 = (n_pat + 63) / 64;
     DevBuf<unsigned long long> keep;
     DevBuf<uint8_t> tmp;
@@ -522,7 +511,7 @@ static int build_selection(spk_ctx *ctx, double lambda, double one_minus, const 
     F.mpat = S.mpat.p;
     F.bitmap = bitmap.p;
     // ---- per pattern: mp table, keep bitset; per chunk: the kept pairs; their scan
-    if (ctx->timing) SPK_HIP(hipEventRecord(ctx->sel_ev0, ctx->stream));
+    SPK_TRY(T.open());
     if (S.has_mp) SPK_TRY(pattern_mp_table(ctx, lambda, one_minus, m, u, S.mpat.p));
     if (n_pat > 0) {
         k_select_patterns<<<(unsigned)((n_pat + SEL_THREADS - 1) / SEL_THREADS), SEL_THREADS, 0, ctx->stream>>>(
@@ -545,8 +534,7 @@ static int build_selection(spk_ctx *ctx, double lambda, double one_minus, const 
         else if (ctx->code_bytes == 2) SPK_TRY(launch_tf_count<uint16_t>(ctx, A, F, lds));
         else SPK_TRY(launch_tf_count<uint32_t>(ctx, A, F, lds));
     }
-    SPK_TRY(scan_total(ctx, chunks, tmp, ctx->timing ? ctx->sel_ev1 : nullptr));  // synchronises
-    SPK_TRY(lap());
+    SPK_TRY(scan_total(ctx, chunks, tmp, &T));  // synchronises
     const int64_t n_sel = chunks.total;
     SPK_REQUIRE(n_sel >= 0 && n_sel <= P, SPK_E_STATE, "spk_select: survivor count");
     // ---- the survivors
@@ -569,16 +557,14 @@ static int build_selection(spk_ctx *ctx, double lambda, double one_minus, const 
         A.out_code = S.code.p;
         A.out_l = S.l.p;
         A.out_r = S.r.p;
-        if (ctx->timing) SPK_HIP(hipEventRecord(ctx->sel_ev0, ctx->stream));
+        SPK_TRY(T.open());
         if (!tf) SPK_TRY(launch_select_codes<true>(ctx, A, lds));
         else if (ctx->code_bytes == 2) SPK_TRY(launch_tf_emit<uint16_t>(ctx, A, F, lds, tf_terms));
         else SPK_TRY(launch_tf_emit<uint32_t>(ctx, A, F, lds, tf_terms));
-        if (ctx->timing) SPK_HIP(hipEventRecord(ctx->sel_ev1, ctx->stream));
-        SPK_HIP(hipStreamSynchronize(ctx->stream));
-        SPK_TRY(lap());
+        SPK_TRY(T.close());
     }
     S.n = n_sel;
-    S.ms = ctx->timing ? ms : -1.0;
+    S.ms = T.result();
     S.valid = true;
     return SPK_OK;
 }
@@ -677,9 +663,7 @@ extern "C" int spk_select_copy_tf(spk_ctx *ctx, int64_t start, int64_t count, do
     const Selection &S = ctx->sel;
     SPK_REQUIRE(S.valid, SPK_E_STATE, "spk_select_copy_tf: no selection (run spk_select_tf*)");
     SPK_REQUIRE(S.has_tf, SPK_E_STATE, "spk_select_copy_tf: the selection was made without tf tables (spk_select)");
-    SPK_REQUIRE(ctx->codes_valid && S.pairs_epoch == ctx->pairs_epoch && S.gamma_seq == ctx->gamma_seq &&
-                    S.fix_seq == ctx->codes_fix_seq,
-                SPK_E_STATE, "spk_select_copy_tf: the pairs or codes changed since spk_select_tf*");
+    SPK_REQUIRE(S.current(ctx), SPK_E_STATE, "spk_select_copy_tf: the pairs or codes changed since spk_select_tf*");
     SPK_REQUIRE(start >= 0 && count >= 0 && start + count <= S.n, SPK_E_INVALID, "spk_select_copy_tf: range");
     if (!count) return SPK_OK;
     SPK_HIP(hipSetDevice(ctx->device));
@@ -696,9 +680,7 @@ extern "C" int spk_select_copy(spk_ctx *ctx, int64_t start, int64_t count, int64
     SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_select_copy: null ctx");
     const Selection &S = ctx->sel;
     SPK_REQUIRE(S.valid, SPK_E_STATE, "spk_select_copy: no selection (run spk_select)");
-    SPK_REQUIRE(ctx->codes_valid && S.pairs_epoch == ctx->pairs_epoch && S.gamma_seq == ctx->gamma_seq &&
-                    S.fix_seq == ctx->codes_fix_seq,
-                SPK_E_STATE, "spk_select_copy: the pairs or codes changed since spk_select");
+    SPK_REQUIRE(S.current(ctx), SPK_E_STATE, "spk_select_copy: the pairs or codes changed since spk_select");
     SPK_REQUIRE(start >= 0 && count >= 0 && start + count <= S.n, SPK_E_INVALID, "spk_select_copy: range");
     SPK_REQUIRE(!(out_l || out_r) || S.has_rows, SPK_E_STATE, "spk_select_copy: no pair rows (a loaded gamma table)");
     SPK_REQUIRE(!out_mp || S.has_mp, SPK_E_STATE, "spk_select_copy: spk_select got no m / u");
