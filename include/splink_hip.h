@@ -678,6 +678,35 @@ int spk_cluster_metrics_set_mode(spk_ctx *ctx, int mode);
 /* The level of the last spk_cluster_metrics (-1: none) and, with timing on, the milliseconds of its kernels. */
 int spk_cluster_metrics_info(spk_ctx *ctx, int *out_level, double *out_ms);
 
+/* ---- clusters against labels (no counterpart in the reference release) ---- */
+#define SPK_AGREE_FIELDS 10
+/* Every level of the current sweep (spk_components_sweep / _sweep_edges) against one truth id per node.
+ * ids: n_nodes values in node order, negative = NULL, an id >= 2^31 is SPK_E_INVALID (as spk_label_histogram).
+ * n_left in [0, n_nodes]; read only when cross_only != 0.  out: levels x SPK_AGREE_FIELDS, level-major.
+ * A node is labelled iff its id is >= 0; a counted pair is an unordered pair of distinct labelled nodes, under
+ * cross_only only one with a node < n_left and a node >= n_left.  Per level, with c the level's labels and g the ids:
+ *   [0] records_labelled    labelled nodes
+ *   [1] clusters_labelled   clusters holding a labelled node
+ *   [2] entities            distinct ids
+ *   [3] predicted_pairs     counted pairs with c[u] == c[v]
+ *   [4] true_pairs          counted pairs with g[u] == g[v]
+ *   [5] tp                  counted pairs with both
+ *   [6] clusters_mixed      clusters whose labelled nodes carry two or more ids
+ *   [7] entities_split      ids whose nodes lie in two or more clusters
+ *   [8] entities_recovered  ids whose nodes all lie in one cluster that holds no labelled node of another id
+ *   [9] pairs_total         all counted pairs: C(M, 2), or M_left * M_right under cross_only
+ * [0], [2], [4] and [9] do not depend on the level and are filled in every row.  Exact integers from sorted keys,
+ * independent of launch shape and of the arrival order of the atomics: two calls give the same bytes.
+ * SPK_E_STATE: no sweep.  SPK_E_INVALID: NULL ids (with n_nodes > 0), NULL out, n_left out of range under cross_only,
+ * an id >= 2^31 (found on the device before any id is used).  SPK_E_LIMIT: more than 2^31 nodes.
+ * Reads the sweep's labels and writes nothing of the context but the two numbers of spk_cluster_agreement_info (a
+ * failing call leaves those as they were): the sweep, its metrics, the labels of spk_components, the selection, scores,
+ * tf and EM state are untouched, and every device buffer of the call is freed before it returns. */
+int spk_cluster_agreement(spk_ctx *ctx, const int64_t *ids, int64_t n_left, int cross_only, int64_t *out);
+/* The last successful spk_cluster_agreement: its levels (-1: none yet) and, with timing on, the device milliseconds
+ * of all its launches (the upload and the read-backs are not in it), -1.0 otherwise. */
+int spk_cluster_agreement_info(spk_ctx *ctx, int *out_levels, double *out_ms);   /* -1 / -1.0: none yet / timing off */
+
 /* ---- pairs against labels (no counterpart in the reference release; later releases:
  *      truth_space_table_from_labels_column, estimate_m_from_label_column) ---- */
 #define SPK_LABEL_NON_MATCH 0   /* both labels non-NULL and different */

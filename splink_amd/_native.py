@@ -82,6 +82,7 @@ EXPORTS = [
     "spk_cluster_metrics", "spk_cluster_metrics_copy", "spk_cluster_metrics_info",
     "spk_cluster_metrics_set_mode",
     "spk_label_histogram", "spk_label_info",
+    "spk_cluster_agreement", "spk_cluster_agreement_info",
     "spk_pairs_sample", "spk_pairs_sample_info",
     "spk_block_profile", "spk_block_profile_info", "spk_block_profile_set_cut",
     "spk_em_lane_copies",
@@ -102,6 +103,7 @@ LABEL_NON_MATCH, LABEL_MATCH, LABEL_UNKNOWN, LABEL_STATES = 0, 1, 2, 3  # SPK_LA
 # lds_per_block()); past it the counts go to global memory.  Mirrored from LH_LDS_BYTES in csrc/spk_labels.hip;
 # only the tests' choice of pattern spaces depends on it.
 LABEL_LDS_BYTES = 64 * 1024
+AGREE_FIELDS = 10  # SPK_AGREE_FIELDS: the columns of cluster_agreement, in labels.AGREEMENT_FIELDS' order
 TF_LIMBS = 14  # SPK_TF_LIMBS
 
 
@@ -916,6 +918,29 @@ class Context:
         ms = ctypes.c_double(-1.0)
         check(self._lib.spk_label_info(self._h, ctypes.byref(n), ctypes.byref(ms)), "spk_label_info")
         return n.value, ms.value
+
+    # ---- clusters against labels --------------------------------------------------------------
+    def cluster_agreement(self, ids, n_left: int = 0, cross_only: bool = False) -> np.ndarray:
+        """spk_cluster_agreement: int64 [levels, AGREE_FIELDS], every level of the current sweep against one truth id
+        per node (node order, negative = NULL); cross_only counts only pairs with one node below n_left."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        levels, n_nodes, _, _ = self.components_sweep_info()
+        if levels >= 0 and len(ids) != n_nodes:
+            raise ValueError(f"cluster_agreement: {len(ids)} ids for the sweep's {n_nodes} nodes")
+        out = np.zeros((max(levels, 1), AGREE_FIELDS), dtype=np.int64)
+        if ids.size == 0:  # no nodes: a non-NULL pointer the library never reads
+            ids = np.zeros(1, np.int64)
+        check(self._lib.spk_cluster_agreement(self._h, _ptr(ids), ctypes.c_int64(int(n_left)),
+                                              ctypes.c_int(1 if cross_only else 0), _ptr(out)), "spk_cluster_agreement")
+        return out
+
+    def cluster_agreement_info(self):
+        """(levels of the last cluster_agreement or -1, ms of its launches with timing on or -1)."""
+        lv = ctypes.c_int(-1)
+        ms = ctypes.c_double(-1.0)
+        check(self._lib.spk_cluster_agreement_info(self._h, ctypes.byref(lv), ctypes.byref(ms)),
+              "spk_cluster_agreement_info")
+        return lv.value, ms.value
 
     def _udf(self, fn, left, right):
         from .table import encode_utf8

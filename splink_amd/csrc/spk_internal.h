@@ -511,6 +511,10 @@ struct spk_ctx {
     // its launches; its buffers live for the call only
     int64_t label_pairs = -1;
     double label_ms = -1.0;
+    // the last spk_cluster_agreement (spk_agreement.hip): levels it scored (-1: none yet), device milliseconds of its
+    // launches; a failing call leaves both as they were, and its buffers live for the call only
+    int agree_levels = -1;
+    double agree_ms = -1.0;
     // the last spk_pairs_sample (spk_sample.hip): draws generated and pairs kept (-1: none, or it failed), device
     // milliseconds of its launches
     int64_t sample_draws = -1, sample_kept = -1;

@@ -31,13 +31,23 @@ inline int prim_two_calls(const char *what, DevBuf<uint8_t> &tmp, Call call) {
     return SPK_OK;
 }
 
-// Stable sort of (key, value) pairs by all 64 bits of the key.
+// Stable sort of (key, value) pairs by the low `bits` bits of the key (the higher ones are not compared).
 template <typename V>
 inline int sort_pairs_u64(hipStream_t stream, DevBuf<uint8_t> &tmp, uint64_t *keys_in, uint64_t *keys_out, V *vals_in,
-                          V *vals_out, int64_t n) {
+                          V *vals_out, int64_t n, int bits = 64) {
     if (n <= 0) return SPK_OK;
     return prim_two_calls("rocprim::radix_sort_pairs", tmp, [&](void *scratch, size_t &bytes) {
-        return rocprim::radix_sort_pairs(scratch, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, 64, stream);
+        return rocprim::radix_sort_pairs(scratch, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0,
+                                         (unsigned int)bits, stream);
+    });
+}
+
+// Sort of keys by their low `bits` bits.
+inline int sort_keys_u64(hipStream_t stream, DevBuf<uint8_t> &tmp, uint64_t *keys_in, uint64_t *keys_out, int64_t n,
+                         int bits = 64) {
+    if (n <= 0) return SPK_OK;
+    return prim_two_calls("rocprim::radix_sort_keys", tmp, [&](void *scratch, size_t &bytes) {
+        return rocprim::radix_sort_keys(scratch, bytes, keys_in, keys_out, (size_t)n, 0, (unsigned int)bits, stream);
     });
 }
 
@@ -56,6 +66,15 @@ inline int inclusive_scan(hipStream_t stream, DevBuf<uint8_t> &tmp, T *in, T *ou
     if (n <= 0) return SPK_OK;
     return prim_two_calls("rocprim::inclusive_scan", tmp, [&](void *scratch, size_t &bytes) {
         return rocprim::inclusive_scan(scratch, bytes, in, out, (size_t)n, rocprim::plus<T>(), stream);
+    });
+}
+
+// out[i] = in[0] op .. op in[i] for an associative op over a value type of the caller's
+template <typename T, typename Op>
+inline int inclusive_scan_op(hipStream_t stream, DevBuf<uint8_t> &tmp, T *in, T *out, int64_t n, Op op) {
+    if (n <= 0) return SPK_OK;
+    return prim_two_calls("rocprim::inclusive_scan", tmp, [&](void *scratch, size_t &bytes) {
+        return rocprim::inclusive_scan(scratch, bytes, in, out, (size_t)n, op, stream);
     });
 }
 

@@ -166,6 +166,37 @@ def _label_ids(job, label_column):
     return job._host_cols[key]
 
 
+def _node_label_ids(job, label_column):
+    """One dense label id per record in node order -- the input tables' own row order, left rows then right, as the
+    cluster frames number their records -- with _label_ids' NULL rules (-1 = NULL, one id space).  Not
+    job.host_values: that is in device row order."""
+    from . import table as T
+    for s, t in enumerate(job.inputs):
+        if label_column not in t.columns:
+            raise ValueError(f"label column {label_column!r} is missing from input table {s}")
+    key = ("node_label_ids", label_column)
+    if key not in job._host_cols:
+        vals = []
+        for t in job.inputs:
+            col = t[label_column]
+            if isinstance(col.dtype, pd.api.extensions.ExtensionDtype):  # Arrow / nullable: NULL as None
+                v = col.to_numpy(dtype=object, na_value=None)
+            else:
+                v = col.to_numpy()
+            if v.dtype == object:
+                v = pd.Series([None if T.is_null_scalar(x) else x for x in v.tolist()], dtype=object)
+            vals.append(pd.Series(v))
+        codes, _ = T.factorize_joint(vals)
+        job._host_cols[key] = np.concatenate([np.asarray(c, dtype=np.int64) for c in codes])
+    return job._host_cols[key]
+
+
+def _cluster_agreement(job, label_column):
+    """int64 [levels, 10]: every level of the sweep the context holds against `label_column` (spk_cluster_agreement)."""
+    ids = _node_label_ids(job, label_column)
+    return job.ctx.cluster_agreement(ids, len(job.inputs[0]), job.link_type == "link_only")
+
+
 def _label_counts(gamma_frame, label_column, lam=None, level_probs=None):
     """LabelCounts of a frame's pairs against `label_column` of the input tables (spk_label_histogram); with lam /
     level_probs also the match_probability of every pattern under them."""
@@ -601,6 +632,11 @@ class ClusterFrame(SplinkDataFrame):
         frame's own selection, whatever its score, so clusters of pairs with NULL scores are covered too.  The sweep's
         labels are this frame's (the same definition over the same pairs): a frame that has none yet takes them, and
         one that has them does not copy them again."""
+        self._sweep_all()
+        return ClusterMetrics(self, self._labels, self.job.ctx, 0)
+
+    def _sweep_all(self):
+        """Make the context's sweep the one level of every pair of this frame's selection."""
         from ._native import SEL_ALL
         job = self.job
         job.sweep_owner = None
@@ -609,7 +645,15 @@ class ClusterFrame(SplinkDataFrame):
         if self._labels is None:
             self._labels = _copy_in_ranges(lambda s, c: job.ctx.components_sweep_copy(0, s, c), int(n_nodes), np.uint32)
             self._info = (int(n_nodes), int(n_clusters[0]), int(rounds[0]))
-        return ClusterMetrics(self, self._labels, job.ctx, 0)
+
+    def truth_table(self, label_column):
+        """These clusters against `label_column` of the input tables, one row (labels.cluster_truth_rows) with
+        threshold NaN: a pair of labelled records is predicted iff both lie in one cluster, so the closure's merges
+        count in full (spk_cluster_agreement over the one-level sweep that metrics() takes)."""
+        from .labels import cluster_truth_rows
+        _node_label_ids(self.job, label_column)  # a missing column fails before the device is touched
+        self._sweep_all()
+        return cluster_truth_rows(_cluster_agreement(self.job, label_column), [np.nan])
 
     def toPandas(self, singletons=True):
         job = self.job
@@ -714,6 +758,12 @@ class _SweepLevelFrame(ClusterFrame):
         sweep, t = self._of
         return sweep.metrics(t)
 
+    def truth_table(self, label_column):
+        """The sweep's truth-table row at this frame's threshold."""
+        sweep, t = self._of
+        table = sweep.truth_table(label_column)
+        return table.iloc[[sweep.thresholds.index(float(t))]].reset_index(drop=True)
+
 
 class ClusterSweepFrame(SplinkDataFrame):
     """`filtered.clusters_at_thresholds(thresholds)`: the clusters of the frame's pairs with score > t, for every t, from
@@ -808,6 +858,17 @@ class ClusterSweepFrame(SplinkDataFrame):
         k = self._level_of(t)
         self._held()
         return ClusterMetrics(self.at(t), self._labels[k], self.job.ctx, k)
+
+    def truth_table(self, label_column):
+        """The clusters at every threshold against `label_column` of the input tables, one row per threshold in the
+        order given (labels.cluster_truth_rows): a pair of labelled records is predicted at t iff both lie in one
+        cluster at t.  One spk_cluster_agreement call over all levels of this frame's sweep; about ten integers per
+        threshold leave the device."""
+        from .labels import cluster_truth_rows
+        _node_label_ids(self.job, label_column)  # a missing column fails before the device is touched
+        self._held()
+        counts = _cluster_agreement(self.job, label_column)
+        return cluster_truth_rows(counts[[self._level_of(t) for t in self.thresholds]], self.thresholds)
 
     def summary(self):
         """One row per threshold, in the order given: threshold, n_edges (pairs with score > threshold), n_clusters,

@@ -46,6 +46,34 @@ def _ratio(num, den):
     return out
 
 
+# The columns of spk_cluster_agreement's rows (SPK_AGREE_FIELDS), in its order.
+AGREEMENT_FIELDS = ("records_labelled", "clusters_labelled", "entities", "predicted_pairs", "true_pairs", "tp",
+                    "clusters_mixed", "entities_split", "entities_recovered", "pairs_total")
+CLUSTER_TRUTH_COLUMNS = ("threshold", "tp", "fp", "fn", "tn", "precision", "recall", "f1", "predicted_pairs",
+                         "true_pairs", "records_labelled", "clusters_labelled", "clusters_mixed", "entities",
+                         "entities_split", "entities_recovered")
+
+
+def cluster_truth_rows(counts, thresholds) -> pd.DataFrame:
+    """The truth table of clusters: one row per row of `counts` (int64 [n, len(AGREEMENT_FIELDS)], what
+    spk_cluster_agreement counts at one level each) and threshold, in the order given.  A pair is predicted iff its
+    two records share a cluster, so with P predicted, T true and tp both: fp = P - tp, fn = T - tp, tn = pairs_total -
+    P - T + tp, over the pairs of labelled records that the link type compares, whether or not blocking produced them.
+    precision, recall and f1 are NaN for 0 / 0."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1, len(AGREEMENT_FIELDS))
+    t = np.asarray(list(thresholds), dtype=np.float64)
+    if len(t) != len(counts):
+        raise ValueError(f"cluster_truth_rows: {len(t)} thresholds for {len(counts)} rows of counts")
+    f = {name: counts[:, i] for i, name in enumerate(AGREEMENT_FIELDS)}
+    tp, P, T = f["tp"], f["predicted_pairs"], f["true_pairs"]
+    fp, fn = P - tp, T - tp
+    data = {"threshold": t, "tp": tp, "fp": fp, "fn": fn, "tn": f["pairs_total"] - P - T + tp,
+            "precision": _ratio(tp, P), "recall": _ratio(tp, T), "f1": _ratio(2 * tp, 2 * tp + fp + fn)}
+    for name in CLUSTER_TRUTH_COLUMNS[8:]:
+        data[name] = f[name]
+    return pd.DataFrame(data, columns=list(CLUSTER_TRUTH_COLUMNS))
+
+
 class LabelCounts:
     """Pairs per (truth state, comparison pattern) of one pair set, and what follows from them.
 
