@@ -614,6 +614,28 @@ int spk_components_copy(spk_ctx *ctx, int64_t start, int64_t count, uint32_t *ou
  * launches, the cluster count; the host round trip after each round is not in it), -1 otherwise. */
 int spk_components_info(spk_ctx *ctx, int64_t *out_n_nodes, int64_t *out_n_edges, int *out_rounds, double *out_ms);
 int spk_components_release(spk_ctx *ctx);
+/* The same labels into device memory (the source of an all-gather over the ranks): a device-to-device copy on the
+ * context's stream, complete when the call returns. */
+int spk_components_copy_device(spk_ctx *ctx, int64_t start, int64_t count, uint32_t *d_out_label);
+
+/* ---- the clusters of a multi-GPU job: the ranks' components merged on the device ---- */
+#define SPK_COMPONENTS_MAX_PEERS 64 /* label arrays per merge call; call again for more */
+/* Brings the labels of the last spk_components*, in place, to the smallest-id labels of the union of their graph with
+ * n_peers other graphs over the same node ids.  Graph p is named by row p of peer_labels (n_peers rows of `stride`
+ * uint32 each, stride >= n_nodes, entries past n_nodes never read): any array with peer[v] <= v whose edges
+ * (v, peer[v]) span that graph's components, such as another rank's final labels.  on_device = 0: a host pointer,
+ * uploaded for the call (n_peers * stride * 4 bytes, freed before it returns); otherwise a device pointer on the
+ * context's device, read in place, whose writes must have completed.  No edge list is built: the rounds of
+ * spk_components run with a node launch that also hooks, per node v and peer p, (v, peer_p[v]).  The first round checks
+ * every peer entry before it indexes anything with it: an entry > its own index (hence any entry >= n_nodes) is
+ * SPK_E_INVALID, and like every failure past the argument checks it leaves no components.  out_n_clusters is the
+ * merged count, out_rounds the rounds of this call (the quiet one included, >= 1); spk_components_info then reports
+ * the sum of the rounds (and milliseconds) so far and, unchanged, the nodes and this graph's own edges.  May be called
+ * repeatedly, each call merging more graphs in (a ring, or a gather in groups, bounds the memory of one call).
+ * SPK_E_INVALID: n_peers outside 1..SPK_COMPONENTS_MAX_PEERS, NULL peer_labels, stride < n_nodes.  SPK_E_STATE: no
+ * components.  SPK_E_LIMIT: the round cap.  The selection, scores, tf and EM state and the sweep are not touched. */
+int spk_components_merge(spk_ctx *ctx, int n_peers, const uint32_t *peer_labels, int64_t stride, int on_device,
+                         int64_t *out_n_clusters, int *out_rounds);
 
 /* ---- clusters at several thresholds in one pass, and their metrics (no counterpart in the reference release, whose
  *      users loop connectedComponents over df_e.filter(...) and groupBy the result; later releases:
@@ -656,6 +678,17 @@ int spk_components_sweep_copy(spk_ctx *ctx, int level, int64_t start, int64_t co
  * host round trip after each round is not in it), -1 otherwise. */
 int spk_components_sweep_info(spk_ctx *ctx, int *out_levels, int64_t *out_n_nodes, int64_t *out_n_edges, double *out_ms);
 int spk_components_sweep_release(spk_ctx *ctx);
+/* The labels of one level into device memory, as spk_components_copy_device. */
+int spk_components_sweep_copy_device(spk_ctx *ctx, int level, int64_t start, int64_t count, uint32_t *d_out_label);
+/* spk_components_merge on level `level` of the current sweep, with its arguments, checks and failure rule (a failure
+ * past the argument checks leaves no sweep).  Level k of every rank merged gives level k of the whole pair set, and
+ * unions of nested sets are nested, so the levels are merged one at a time and independently: n_peers * stride labels
+ * are held per call, not L times that.  out_n_clusters replaces the level's count, out_rounds (this call's) is added
+ * to the level's rounds.  A sweep with a merged level is marked: its edges are one shard's, so spk_cluster_metrics on
+ * it is SPK_E_STATE (and the last metrics are dropped); spk_cluster_agreement, which reads labels only, keeps working.
+ * SPK_E_INVALID also for a level outside the sweep; SPK_E_STATE: no sweep. */
+int spk_components_sweep_merge(spk_ctx *ctx, int level, int n_peers, const uint32_t *peer_labels, int64_t stride,
+                               int on_device, int64_t *out_n_clusters, int *out_rounds);
 /* Which edges a level's rounds hook (both give the same labels; for A/B runs): 0 (default) the edges that are new at
  * the level, plus for every node the edge to its label at the previous level; 1 every edge of the level. */
 int spk_components_sweep_set_mode(spk_ctx *ctx, int mode);
@@ -666,8 +699,8 @@ int spk_components_sweep_set_mode(spk_ctx *ctx, int mode);
  * (label[v] == v) and 0 elsewhere: size = nodes of the cluster, degree_sum = the sum of its degrees (twice its
  * edges), max_degree = its largest degree.  out3 = clusters of >= 2 nodes, nodes in them, the largest cluster's
  * nodes (0 without nodes).  The arrays (20 bytes per node, under [6] of spk_ctx_memory) describe one level at a time:
- * they are recomputed by every call and freed with the sweep.  SPK_E_STATE without a sweep, SPK_E_INVALID for a
- * level outside it. */
+ * they are recomputed by every call and freed with the sweep.  SPK_E_STATE without a sweep or on one with a merged
+ * level (spk_components_sweep_merge), SPK_E_INVALID for a level outside it. */
 int spk_cluster_metrics(spk_ctx *ctx, int level, int64_t *out3);
 /* Nodes [start, start + count) of the last spk_cluster_metrics; any out may be NULL. */
 int spk_cluster_metrics_copy(spk_ctx *ctx, int64_t start, int64_t count, uint32_t *out_degree, uint32_t *out_size,

@@ -50,6 +50,7 @@ SELECT_CHUNK = 2048
 # Edges per workgroup step of the components' hooking kernel.  Mirrored from CC_CHUNK in csrc/spk_components.hip
 # (256 threads x one 16-byte vector of ids each); only the tests' edge sizes depend on it.
 COMPONENTS_CHUNK = 1024
+COMPONENTS_MAX_PEERS = 64  # SPK_COMPONENTS_MAX_PEERS: label arrays per components_merge call
 assert OPERAND_DTYPE.itemsize == 40 and INSTR_DTYPE.itemsize == 32 and PROGRAM_DTYPE.itemsize == 16
 
 OP = {"ISNULL": 1, "NOTNULL": 2, "STR_CMP": 3, "NUM_CMP": 4, "JW": 5, "LEV": 6, "LEVRATIO": 7, "ABSDIFF": 8,
@@ -79,6 +80,8 @@ EXPORTS = [
     "spk_components", "spk_components_edges", "spk_components_copy", "spk_components_info", "spk_components_release",
     "spk_components_sweep", "spk_components_sweep_edges", "spk_components_sweep_copy", "spk_components_sweep_info",
     "spk_components_sweep_release", "spk_components_sweep_set_mode",
+    "spk_components_merge", "spk_components_sweep_merge", "spk_components_copy_device",
+    "spk_components_sweep_copy_device",
     "spk_cluster_metrics", "spk_cluster_metrics_copy", "spk_cluster_metrics_info",
     "spk_cluster_metrics_set_mode",
     "spk_label_histogram", "spk_label_info",
@@ -792,6 +795,81 @@ class Context:
     def components_release(self):
         check(self._lib.spk_components_release(self._h), "spk_components_release")
 
+    # ---- the clusters of a multi-GPU job: other ranks' labels merged in -----------------------
+    @staticmethod
+    def _peer_labels(peers, what="components_merge"):
+        """The peers argument of components_merge / components_sweep_merge as (n_peers, address, stride, on_device,
+        the object that keeps the memory alive).  peers: [n_peers, stride] (or [stride]: one peer) of uint32 / int32, a
+        numpy array (or anything numpy converts) on the host, or a contiguous torch tensor on the context's device,
+        which is read in place.  Needs no device: the shape, dtype and peer-count checks raise ValueError here."""
+        if hasattr(peers, "is_cuda") and hasattr(peers, "data_ptr"):  # a torch tensor
+            import torch
+            kinds = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+            if peers.dtype not in kinds:
+                raise ValueError(f"{what}: peer labels are uint32 or int32, not {peers.dtype}")
+            if peers.dim() == 1:
+                peers = peers.unsqueeze(0)
+            if peers.dim() != 2:
+                raise ValueError(f"{what}: peer labels are [n_peers, stride]")
+            if not 1 <= peers.shape[0] <= COMPONENTS_MAX_PEERS:
+                raise ValueError(f"{what}: 1 to {COMPONENTS_MAX_PEERS} peers per call, not {peers.shape[0]}")
+            if not peers.is_contiguous():
+                raise ValueError(f"{what}: the peer labels must be contiguous")
+            if peers.is_cuda and peers.shape[1] > 0:
+                return int(peers.shape[0]), int(peers.data_ptr()), int(peers.shape[1]), True, peers
+            peers = peers.cpu().numpy()  # a host tensor, or rows without nodes (no address to hand over)
+        a = np.asarray(peers)
+        if a.dtype not in (np.dtype(np.uint32), np.dtype(np.int32)):
+            raise ValueError(f"{what}: peer labels are uint32 or int32, not {a.dtype}")
+        if a.ndim == 1:
+            a = a.reshape(1, -1)
+        if a.ndim != 2:
+            raise ValueError(f"{what}: peer labels are [n_peers, stride]")
+        if not 1 <= a.shape[0] <= COMPONENTS_MAX_PEERS:
+            raise ValueError(f"{what}: 1 to {COMPONENTS_MAX_PEERS} peers per call, not {a.shape[0]}")
+        a = np.ascontiguousarray(a).view(np.uint32)
+        if a.shape[1] == 0:  # no nodes: a non-NULL pointer the library never reads
+            return int(a.shape[0]), np.zeros(1, np.uint32).ctypes.data, 0, False, a
+        return int(a.shape[0]), a.ctypes.data, int(a.shape[1]), False, a
+
+    def _settle_peers(self, on_device, keep):
+        if on_device:  # written on one of torch's streams, read on the context's
+            import torch
+            if keep.device.index != self.device:
+                raise ValueError(f"the peer labels are on {keep.device}, the context on device {self.device}")
+            torch.cuda.current_stream(keep.device).synchronize()
+
+    def components_merge(self, peers):
+        """spk_components_merge: bring the labels of the last components* to those of the union of their graph with
+        the graphs named by the peers' label arrays (peers[p][v] <= v: e.g. other ranks' final labels over the same
+        records; `_peer_labels` for the forms).  Returns (n_clusters of the union, rounds of this call); an entry
+        greater than its index raises ValueError and leaves no components.  May be called repeatedly."""
+        n_peers, addr, stride, on_device, keep = self._peer_labels(peers)
+        self._settle_peers(on_device, keep)
+        c = ctypes.c_int64(0)
+        r = ctypes.c_int(0)
+        check(self._lib.spk_components_merge(self._h, ctypes.c_int(n_peers), ctypes.c_void_p(addr), ctypes.c_int64(stride),
+                                             ctypes.c_int(1 if on_device else 0), ctypes.byref(c), ctypes.byref(r)),
+              "spk_components_merge")
+        del keep
+        return c.value, r.value
+
+    def components_copy_device(self, out, start: int = 0):
+        """Labels of nodes [start, start + len(out)) of the last components* into `out`, a contiguous one-dimensional
+        uint32 / int32 torch tensor on the context's device (complete on return)."""
+        self._device_out(out, "components_copy_device")
+        check(self._lib.spk_components_copy_device(self._h, ctypes.c_int64(start), ctypes.c_int64(out.numel()),
+                                                   ctypes.c_void_p(out.data_ptr() if out.numel() else 0)),
+              "spk_components_copy_device")
+        return out
+
+    def _device_out(self, out, what):
+        import torch
+        kinds = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+        if not (out.is_cuda and out.device.index == self.device and out.dim() == 1 and out.is_contiguous()
+                and out.dtype in kinds):
+            raise ValueError(f"{what}: out is a contiguous one-dimensional uint32 / int32 tensor on the context's device")
+
     # ---- clusters at several thresholds, and their metrics ------------------------------------
     @staticmethod
     def _sweep_thresholds(thresholds):
@@ -853,6 +931,29 @@ class Context:
 
     def components_sweep_release(self):
         check(self._lib.spk_components_sweep_release(self._h), "spk_components_sweep_release")
+
+    def components_sweep_merge(self, level: int, peers):
+        """spk_components_sweep_merge: components_merge on one level of the current sweep; returns (n_clusters of the
+        union at that level, rounds of this call).  Marks the sweep as merged: cluster_metrics on it raises."""
+        n_peers, addr, stride, on_device, keep = self._peer_labels(peers, "components_sweep_merge")
+        self._settle_peers(on_device, keep)
+        c = ctypes.c_int64(0)
+        r = ctypes.c_int(0)
+        check(self._lib.spk_components_sweep_merge(self._h, ctypes.c_int(int(level)), ctypes.c_int(n_peers),
+                                                   ctypes.c_void_p(addr), ctypes.c_int64(stride),
+                                                   ctypes.c_int(1 if on_device else 0), ctypes.byref(c), ctypes.byref(r)),
+              "spk_components_sweep_merge")
+        del keep
+        return c.value, r.value
+
+    def components_sweep_copy_device(self, level: int, out, start: int = 0):
+        """components_copy_device for one level of the last sweep."""
+        self._device_out(out, "components_sweep_copy_device")
+        check(self._lib.spk_components_sweep_copy_device(self._h, ctypes.c_int(int(level)), ctypes.c_int64(start),
+                                                         ctypes.c_int64(out.numel()),
+                                                         ctypes.c_void_p(out.data_ptr() if out.numel() else 0)),
+              "spk_components_sweep_copy_device")
+        return out
 
     def components_sweep_set_mode(self, mode: int):
         """0 (default): a level hooks its new edges and a star edge per node; 1: every edge up to the level (A/B)."""

@@ -52,6 +52,35 @@
 // correct by the same argument with E_k = all edges of level k.  Measured against each other: DESIGN.md.
 // A level without new edges runs no round.  The order of the edges inside a level's range depends on the arrival
 // order of k_sw_scatter's atomics and varies from run to run; nothing observable depends on it.
+//
+// The clusters of a multi-GPU job (spk_components_merge, spk_components_sweep_merge).  Every rank labels the graph of
+// its shard of the kept pairs, and all ranks number the records the same way, so a rank's final labels are a star
+// forest over the common node ids: the edges (v, peer[v]) connect every component of that rank's graph.  The
+// components of the union of the shards' pairs are therefore the fixed point of one rank's labels hooked with the
+// star edges of every other rank's label array.  It is the round loop above with no hook launch (there is no edge
+// list) and the node launch k_cc_jump_stars, which does k_cc_jump's jump and then, for each peer p, hooks
+// (v, peer_p[v]).  The argument carries over:
+//   start state: the rank's own final labels were written by launches that have completed: invariants (1) and (2)
+//                hold (for the union's components, which contain the rank's own), and label[v] <= v;
+//   spanning:    the forest in `label` spans the rank's own components when the merge starts, and here nothing else
+//                does -- the rank's edge list is gone, where the rounds above hook every edge again and so repair a
+//                link that a hook of a non-root (a climb cut short, a stale load) has cut.  So the merge's hook
+//                (cc_hook_root) re-parents the larger end only by a compare-and-swap against its own id: only a root
+//                gains a parent, the jump moves a node to a former ancestor, trees only ever merge, and the forest
+//                keeps spanning the rank's components; the star arrays span every peer's components; together they
+//                span every component of the union.  (Lowering a non-root here lost about one merge in 2,000 on the
+//                65,536-node path: the rank's own forest came out split.)
+//   quiet round: it wrote nothing, so every load saw the final array: every star edge of every peer joins nodes
+//                with one common label, hence (with the forest) all nodes of a component of the union carry one
+//                label; every label is a root, a root is <= every node that carries it and is a member, so it is the
+//                component's smallest id;
+//   progress:    no workgroup waits for another, every loop in the kernel is bounded (CC_PEER_BATCH, n_peers, CC_CLIMB)
+//                and CC_MAX_ROUNDS caps the host loop.
+// A peer array comes from outside (another process, the host): the first round validates every entry before anything
+// is indexed with it -- q <= v, and so q < n_nodes -- and reports through flags[1], as the first hook launch does for
+// an edge list.  (2) needs nothing more of a peer array than that: any array with peer[v] <= v names some graph, and
+// the result is the components of the union with that graph.  The peer rows are read once per round and streamed past
+// the caches (non-temporal loads), so the labels, which every climb reads, keep them.
 #include <algorithm>
 
 #include "spk_internal.h"
@@ -64,6 +93,8 @@ constexpr int64_t CC_CHUNK = (int64_t)CC_THREADS * CC_VEC;  // edges per workgro
 constexpr int CC_WG_PER_CU = 8;                           // capped grid, the workgroups stride over the chunks (as k_select)
 constexpr int CC_CLIMB = 8;                               // loads of one climb; tools/emulate_components.py mirrors it
 constexpr int CC_MAX_ROUNDS = 256;                        // the loop's hard cap (SPK_E_LIMIT beyond it)
+constexpr int CC_MAX_PEERS = SPK_COMPONENTS_MAX_PEERS;    // label arrays of one merge; _native.COMPONENTS_MAX_PEERS mirrors it
+constexpr int CC_PEER_BATCH = 4;                          // peer entries a lane loads before it hooks them
 
 typedef uint32_t cc_u32x4 __attribute__((ext_vector_type(4)));
 
@@ -277,6 +308,75 @@ __global__ __launch_bounds__(CC_THREADS) void k_cc_jump_star(int64_t n_nodes, ui
     cc_raise(flags, changed, false);
 }
 
+// Star arrays hooked by the node launch: row p is rows + p * stride, [n_nodes] entries read.  `foreign`: the rows come
+// from outside this library's own launches (a merge's peers) and the first round validates them; otherwise one row, the
+// previous level's labels of a sweep.
+struct Stars {
+    const uint32_t *rows = nullptr;
+    int n = 0;
+    int64_t stride = 0;
+    bool foreign = false;
+};
+
+// cc_hook_edge of a merge.  There the rank's own components live in `label` alone (its edge list is gone), so a hook
+// must never cut a node off its parent: the larger end is re-parented only while it is a root, by a compare-and-swap
+// against its own id, which acts on the word itself and not on a possibly stale load.  A climb that stopped short of
+// the root (CC_CLIMB loads) or over stale labels then fails its swap, reports the round as not quiet and is taken up
+// again in the next one, after the jumps have shortened the chains.  With that, parents change only by a root gaining
+// one (two trees merge) and by a jump to a former ancestor (which is still in the node's tree): trees never split.
+__device__ inline void cc_hook_root(uint32_t *label, uint32_t u, uint32_t v, bool &changed) {
+    if (u == v) return;
+    uint32_t a = cc_load(label, u), b = cc_load(label, v);
+    if (a == b) return;
+    a = cc_climb(label, a);
+    b = cc_climb(label, b);
+    if (a == b) return;  // one tree, not flat yet: the jump lowers a label in it and reports that
+    changed = true;
+    uint32_t hi = a > b ? a : b;
+    const uint32_t lo = a > b ? b : a;
+    (void)__hip_atomic_compare_exchange_strong(label + (size_t)hi, &hi, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// k_cc_jump of a merge, which also hooks, for every node v and every peer p, the star edge (v, peer_p[v]).  An entry
+// equal to v (a record that is a cluster of its own on that rank: most are) costs its own load and nothing else.  A
+// lane's CC_PEER_BATCH loads are issued together; a row starts at any 4-byte alignment (stride is the caller's), so the
+// loads are scalar, coalesced over the wave's consecutive v.  CHECK: the first round, which validates every entry
+// before it indexes the labels with it: q <= v, and so q < n_nodes.
+template <bool CHECK>
+__global__ __launch_bounds__(CC_THREADS) void k_cc_jump_stars(int64_t n_nodes, uint32_t *label,
+                                                              const uint32_t *__restrict__ peer, int n_peers,
+                                                              int64_t stride, unsigned int *flags) {
+    bool changed = false, bad = false;
+    const int64_t step = (int64_t)gridDim.x * CC_THREADS;
+    for (int64_t v = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x; v < n_nodes; v += step) {
+        const uint32_t p = label[v];
+        if ((int64_t)p != v) {
+            const uint32_t r = cc_climb(label, p);
+            if (r < p) {
+                changed = true;
+                (void)__hip_atomic_fetch_min(label + v, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        for (int p0 = 0; p0 < n_peers; p0 += CC_PEER_BATCH) {
+            uint32_t q[CC_PEER_BATCH];
+#pragma unroll
+            for (int j = 0; j < CC_PEER_BATCH; ++j)  // past the last peer: v itself, which is skipped
+                q[j] = p0 + j < n_peers ? __builtin_nontemporal_load(peer + ((int64_t)(p0 + j) * stride + v)) : (uint32_t)v;
+#pragma unroll
+            for (int j = 0; j < CC_PEER_BATCH; ++j) {
+                if ((int64_t)q[j] == v) continue;
+                if (CHECK && ((int64_t)q[j] > v || (int64_t)q[j] >= n_nodes)) {
+                    bad = true;
+                    continue;
+                }
+                cc_hook_root(label, (uint32_t)v, q[j], changed);
+            }
+        }
+    }
+    cc_raise(flags, changed, bad);
+}
+
 // ---- metrics of one level ------------------------------------------------------------------------------------------
 // degree[x] += 1 for one end x per active lane.  AGG: the lanes whose end equals that of the wave's first active lane
 // issue one add of their count (the lowest of them does); the others add on their own.
@@ -375,25 +475,32 @@ __global__ __launch_bounds__(CC_THREADS) void k_cm_scalars(int64_t n_nodes, cons
 
 // ---- the round loop ---------------------------------------------------------------------------------------------------
 // Brings lab [n_nodes] to its fixed point and counts its clusters.  lab holds a start state for which invariants (1) and
-// (2) hold (k_cc_init, or a copy of the previous level's labels).  The rounds hook the edges (hu, hv) [hn] and, with
-// prev, the star edges (v, prev[v]); hn = 0 runs no round.  flags [2] and count [1] are the caller's device scratch.
+// (2) hold (k_cc_init, a copy of the previous level's labels, or a finished result about to be merged).  The rounds
+// hook the edges (hu, hv) [hn] and the star edges of S; the hook launch is left out when hn = 0, and without edges and
+// without star arrays no round runs.  flags [2] and count [1] are the caller's device scratch.
 // T may be open around the caller's own launches (the edge build, the start state): they count into round 0's interval.
 static int cc_fixed_point(spk_ctx *ctx, int64_t n_nodes, const uint32_t *hu, const uint32_t *hv, int64_t hn,
-                          uint32_t *lab, const uint32_t *prev, unsigned int *flags, unsigned long long *count,
+                          uint32_t *lab, const Stars &S, unsigned int *flags, unsigned long long *count,
                           int bad_code, const char *bad_msg, const char *limit_msg, StageTimer &T, int *out_rounds,
                           int64_t *out_n_clusters) {
     hipStream_t st = ctx->stream;
     const unsigned hook_grid = cc_grid(ctx, hn, CC_CHUNK), node_grid = cc_grid(ctx, n_nodes, CC_THREADS);
     int rounds = 0;
-    bool quiet = hn == 0;
+    bool quiet = hn == 0 && S.n == 0;
     while (!quiet) {
         SPK_REQUIRE(rounds < CC_MAX_ROUNDS, SPK_E_LIMIT, limit_msg);
         SPK_TRY(T.open());
         SPK_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(unsigned int), st));
-        if (rounds == 0) k_cc_hook<true><<<hook_grid, CC_THREADS, 0, st>>>(n_nodes, hn, hu, hv, lab, flags);
-        else k_cc_hook<false><<<hook_grid, CC_THREADS, 0, st>>>(n_nodes, hn, hu, hv, lab, flags);
-        SPK_HIP(hipGetLastError());
-        if (prev) k_cc_jump_star<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab, prev, flags);
+        if (hn > 0) {
+            if (rounds == 0) k_cc_hook<true><<<hook_grid, CC_THREADS, 0, st>>>(n_nodes, hn, hu, hv, lab, flags);
+            else k_cc_hook<false><<<hook_grid, CC_THREADS, 0, st>>>(n_nodes, hn, hu, hv, lab, flags);
+            SPK_HIP(hipGetLastError());
+        }
+        if (S.foreign && rounds == 0)
+            k_cc_jump_stars<true><<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab, S.rows, S.n, S.stride, flags);
+        else if (S.foreign)
+            k_cc_jump_stars<false><<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab, S.rows, S.n, S.stride, flags);
+        else if (S.n) k_cc_jump_star<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab, S.rows, flags);
         else k_cc_jump<<<node_grid, CC_THREADS, 0, st>>>(n_nodes, lab, flags);
         SPK_HIP(hipGetLastError());
         unsigned int h[2] = {0u, 0u};  // [changed, bad]
@@ -427,7 +534,7 @@ static int build_components(spk_ctx *ctx, int64_t n_nodes, int64_t n_edges, cons
     SPK_TRY(T.open());
     k_cc_init<<<cc_grid(ctx, n_nodes, CC_THREADS), CC_THREADS, 0, ctx->stream>>>(n_nodes, C.label.p);
     SPK_HIP(hipGetLastError());
-    SPK_TRY(cc_fixed_point(ctx, n_nodes, eu, ev, n_edges, C.label.p, nullptr, flags.p, count.p, bad_code, bad_msg,
+    SPK_TRY(cc_fixed_point(ctx, n_nodes, eu, ev, n_edges, C.label.p, Stars{}, flags.p, count.p, bad_code, bad_msg,
                            "spk_components: no fixed point within 256 rounds", T, &C.rounds, &C.n_clusters));
     C.n_nodes = n_nodes;
     C.n_edges = n_edges;
@@ -563,7 +670,13 @@ static int build_sweep(spk_ctx *ctx, int64_t n_nodes, int64_t n_raw, const uint3
         } else if (n_nodes > 0) {
             SPK_HIP(hipMemcpyAsync(lab, prev, (size_t)n_nodes * 4, hipMemcpyDeviceToDevice, st));
         }
-        SPK_TRY(cc_fixed_point(ctx, n_nodes, hu, hv, hn, lab, prefix ? nullptr : prev, flags.p, count, bad_code, bad_msg,
+        Stars stars;  // the previous level's labels, for a level that has new edges to hook
+        if (prev && !prefix && hn > 0) {
+            stars.rows = prev;
+            stars.n = 1;
+            stars.stride = n_nodes;
+        }
+        SPK_TRY(cc_fixed_point(ctx, n_nodes, hu, hv, hn, lab, stars, flags.p, count, bad_code, bad_msg,
                                "spk_components_sweep: no fixed point within 256 rounds", T, &S.rounds[k],
                                &S.n_clusters[k]));
     }
@@ -578,6 +691,47 @@ static void sweep_outputs(const ComponentSweep &S, int64_t *out_n_edges, int64_t
         if (out_n_clusters) out_n_clusters[k] = S.n_clusters[k];
         if (out_rounds) out_rounds[k] = S.rounds[k];
     }
+}
+
+// The argument checks spk_components_merge and spk_components_sweep_merge (`who`) share; nothing is touched before them.
+static int merge_arguments(const char *who, int n_peers, const uint32_t *peer_labels, int64_t stride, int64_t n_nodes) {
+    const std::string w(who);
+    SPK_REQUIRE(n_peers >= 1 && n_peers <= CC_MAX_PEERS, SPK_E_INVALID, w + ": 1 to 64 peers");
+    SPK_REQUIRE(peer_labels, SPK_E_INVALID, w + ": null peer_labels");
+    SPK_REQUIRE(stride >= n_nodes, SPK_E_INVALID, w + ": stride < n_nodes");
+    SPK_REQUIRE(stride <= (int64_t)UINT32_MAX, SPK_E_INVALID, w + ": stride beyond 2^32 - 1");
+    return SPK_OK;
+}
+
+// lab [n_nodes], a finished result, to the fixed point of itself hooked with the peers' star edges.  A host pointer is
+// uploaded into a buffer of this call.  Whatever fails here may have lowered labels already: the caller drops the result.
+static int merge_labels(spk_ctx *ctx, const char *who, int64_t n_nodes, uint32_t *lab, int n_peers,
+                        const uint32_t *peer_labels, int64_t stride, int on_device, StageTimer &T, int *out_rounds,
+                        int64_t *out_n_clusters) {
+    const std::string w(who);
+    DevBuf<uint32_t> up;
+    DevBuf<unsigned int> flags;
+    DevBuf<unsigned long long> count;
+    SPK_TRY(flags.alloc(2));
+    SPK_TRY(count.alloc(1));
+    Stars S;
+    S.rows = peer_labels;
+    S.n = n_peers;
+    S.stride = stride;
+    S.foreign = true;
+    if (!on_device) {
+        const size_t words = (size_t)n_peers * (size_t)stride;
+        SPK_TRY(up.alloc(words + 1));
+        if (words > 0) {
+            SPK_HIP(hipMemcpyAsync(up.p, peer_labels, words * 4, hipMemcpyHostToDevice, ctx->stream));
+            SPK_HIP(hipStreamSynchronize(ctx->stream));  // peer_labels is the caller's: done with it
+        }
+        S.rows = up.p;
+    }
+    const std::string bad = w + ": a peer label is greater than its own index (or >= n_nodes)";
+    const std::string limit = w + ": no fixed point within 256 rounds";
+    return cc_fixed_point(ctx, n_nodes, nullptr, nullptr, 0, lab, S, flags.p, count.p, SPK_E_INVALID, bad.c_str(),
+                          limit.c_str(), T, out_rounds, out_n_clusters);
 }
 
 }  // namespace spk
@@ -657,6 +811,46 @@ extern "C" int spk_components_release(spk_ctx *ctx) {
     SPK_HIP(hipSetDevice(ctx->device));
     SPK_HIP(hipStreamSynchronize(ctx->stream));
     ctx->comp.clear();
+    return SPK_OK;
+}
+
+extern "C" int spk_components_copy_device(spk_ctx *ctx, int64_t start, int64_t count, uint32_t *d_out_label) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_components_copy_device: null ctx");
+    const Components &C = ctx->comp;
+    SPK_REQUIRE(C.valid, SPK_E_STATE, "spk_components_copy_device: no components (run spk_components)");
+    SPK_REQUIRE(start >= 0 && count >= 0 && start <= C.n_nodes && count <= C.n_nodes - start, SPK_E_INVALID,
+                "spk_components_copy_device: range");
+    SPK_REQUIRE(count == 0 || d_out_label, SPK_E_INVALID, "spk_components_copy_device: null out");
+    if (!count) return SPK_OK;
+    SPK_HIP(hipSetDevice(ctx->device));
+    SPK_HIP(hipMemcpyAsync(d_out_label, C.label.p + start, (size_t)count * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    SPK_HIP(hipStreamSynchronize(ctx->stream));  // a collective on another stream reads it next
+    return SPK_OK;
+}
+
+extern "C" int spk_components_merge(spk_ctx *ctx, int n_peers, const uint32_t *peer_labels, int64_t stride,
+                                    int on_device, int64_t *out_n_clusters, int *out_rounds) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_components_merge: null ctx");
+    Components &C = ctx->comp;
+    SPK_REQUIRE(C.valid, SPK_E_STATE, "spk_components_merge: no components (run spk_components)");
+    SPK_TRY(merge_arguments("spk_components_merge", n_peers, peer_labels, stride, C.n_nodes));
+    SPK_HIP(hipSetDevice(ctx->device));
+    StageTimer T{ctx};
+    int rounds = 0;
+    int64_t n_clusters = 0;
+    const int rc = merge_labels(ctx, "spk_components_merge", C.n_nodes, C.label.p, n_peers, peer_labels, stride,
+                                on_device, T, &rounds, &n_clusters);
+    if (rc != SPK_OK) {
+        C.clear();  // some labels may be the union's already, others not: no components
+        return rc;
+    }
+    C.n_clusters = n_clusters;
+    C.rounds += rounds;
+    if (C.ms >= 0.0 && T.result() >= 0.0) C.ms += T.result();
+    else C.ms = -1.0;
+    C.merged = true;
+    if (out_n_clusters) *out_n_clusters = n_clusters;
+    if (out_rounds) *out_rounds = rounds;
     return SPK_OK;
 }
 
@@ -755,6 +949,53 @@ extern "C" int spk_components_sweep_release(spk_ctx *ctx) {
     return SPK_OK;
 }
 
+extern "C" int spk_components_sweep_copy_device(spk_ctx *ctx, int level, int64_t start, int64_t count,
+                                                uint32_t *d_out_label) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_components_sweep_copy_device: null ctx");
+    const ComponentSweep &W = ctx->sweep;
+    SPK_REQUIRE(W.valid, SPK_E_STATE, "spk_components_sweep_copy_device: no sweep (run spk_components_sweep)");
+    SPK_REQUIRE(level >= 0 && level < W.levels, SPK_E_INVALID, "spk_components_sweep_copy_device: level");
+    SPK_REQUIRE(start >= 0 && count >= 0 && start <= W.n_nodes && count <= W.n_nodes - start, SPK_E_INVALID,
+                "spk_components_sweep_copy_device: range");
+    SPK_REQUIRE(count == 0 || d_out_label, SPK_E_INVALID, "spk_components_sweep_copy_device: null out");
+    if (!count) return SPK_OK;
+    SPK_HIP(hipSetDevice(ctx->device));
+    SPK_HIP(hipMemcpyAsync(d_out_label, W.label.p + (size_t)level * (size_t)W.n_nodes + (size_t)start, (size_t)count * 4,
+                           hipMemcpyDeviceToDevice, ctx->stream));
+    SPK_HIP(hipStreamSynchronize(ctx->stream));  // a collective on another stream reads it next
+    return SPK_OK;
+}
+
+extern "C" int spk_components_sweep_merge(spk_ctx *ctx, int level, int n_peers, const uint32_t *peer_labels,
+                                          int64_t stride, int on_device, int64_t *out_n_clusters, int *out_rounds) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_components_sweep_merge: null ctx");
+    ComponentSweep &W = ctx->sweep;
+    SPK_REQUIRE(W.valid, SPK_E_STATE, "spk_components_sweep_merge: no sweep (run spk_components_sweep)");
+    SPK_REQUIRE(level >= 0 && level < W.levels, SPK_E_INVALID, "spk_components_sweep_merge: level");
+    SPK_TRY(merge_arguments("spk_components_sweep_merge", n_peers, peer_labels, stride, W.n_nodes));
+    SPK_HIP(hipSetDevice(ctx->device));
+    W.merged = true;  // from here on the level's labels are no longer those of the stored edges
+    W.m_level = -1;
+    W.m_ms = -1.0;
+    StageTimer T{ctx};
+    int rounds = 0;
+    int64_t n_clusters = 0;
+    const int rc = merge_labels(ctx, "spk_components_sweep_merge", W.n_nodes,
+                                W.label.p + (size_t)level * (size_t)W.n_nodes, n_peers, peer_labels, stride, on_device,
+                                T, &rounds, &n_clusters);
+    if (rc != SPK_OK) {
+        W.clear();  // some of the level's labels may be the union's already, others not: no sweep
+        return rc;
+    }
+    W.n_clusters[level] = n_clusters;
+    W.rounds[level] += rounds;
+    if (W.ms >= 0.0 && T.result() >= 0.0) W.ms += T.result();
+    else W.ms = -1.0;
+    if (out_n_clusters) *out_n_clusters = n_clusters;
+    if (out_rounds) *out_rounds = rounds;
+    return SPK_OK;
+}
+
 extern "C" int spk_components_sweep_set_mode(spk_ctx *ctx, int mode) {
     SPK_REQUIRE(ctx && (mode == 0 || mode == 1), SPK_E_INVALID, "spk_components_sweep_set_mode: mode 0 or 1");
     ctx->sweep_mode = mode;
@@ -767,6 +1008,9 @@ extern "C" int spk_cluster_metrics(spk_ctx *ctx, int level, int64_t *out3) {
     ComponentSweep &W = ctx->sweep;
     SPK_REQUIRE(W.valid, SPK_E_STATE, "spk_cluster_metrics: no sweep (run spk_components_sweep)");
     SPK_REQUIRE(level >= 0 && level < W.levels, SPK_E_INVALID, "spk_cluster_metrics: level");
+    SPK_REQUIRE(!W.merged, SPK_E_STATE,
+                "spk_cluster_metrics: a level of this sweep was merged with other shards' labels, and its stored "
+                "edges are one shard's: the degrees would be partial");
     SPK_HIP(hipSetDevice(ctx->device));
     W.m_level = -1;  // whatever happens below, the previous level's metrics are gone
     W.m_ms = -1.0;

@@ -305,6 +305,7 @@ struct Components {
     int rounds = 0;
     DevBuf<uint32_t> label;  // [n_nodes]
     double ms = -1.0;        // device milliseconds of its kernels (timing on), -1 = none
+    bool merged = false;     // spk_components_merge hooked other graphs' labels in: n_edges is still this graph's own
     void clear() { *this = Components(); }
 };
 
@@ -325,6 +326,9 @@ struct ComponentSweep {
     DevBuf<uint32_t> label;           // [levels x n_nodes], level-major; offsets into it are size_t
     DevBuf<uint32_t> eu, ev;          // the edges, bucketed by level
     double ms = -1.0;                 // device milliseconds of its kernels (timing on), -1 = none
+    // spk_components_sweep_merge ran on a level: its labels are the union's, eu / ev still one shard's, so the degrees
+    // would be partial and spk_cluster_metrics refuses
+    bool merged = false;
     // spk_cluster_metrics: the level they describe (-1: none), by node id
     int m_level = -1;
     double m_ms = -1.0;

@@ -92,6 +92,36 @@ def sum_over_ranks(n: int) -> int:
     return int(_reduce_scalar(int(n), dist.ReduceOp.SUM if dist else None, torch.int64))
 
 
+def allgather_labels(t, force: bool = False):
+    """Every rank's cluster labels: t is a [n] uint32 / int32 tensor of one length on all ranks, the result [world, n]
+    of t's dtype with row g rank g's (this rank's own row included).  Under `nccl` (RCCL over xGMI) t is a device
+    tensor and so is the result; under `gloo` the gather is staged through the host, as allreduce_histogram_ does, and
+    the result is a host tensor whatever t's device.  Without a process group (or with one rank and no force) the
+    result is t as one row.  A collective: every rank calls it, in the same order among the collectives."""
+    import torch
+    if t.dim() != 1:
+        raise ValueError("allgather_labels: a one-dimensional tensor of labels")
+    kinds = (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ())
+    if t.dtype not in kinds:
+        raise ValueError(f"allgather_labels: labels are uint32 or int32, not {t.dtype}")
+    dist = _dist()
+    if dist is None or (dist.get_world_size() <= 1 and not force):
+        return t.reshape(1, -1)
+    world = dist.get_world_size()
+    wire = t.contiguous().view(torch.int32)  # the same 32 bits: the backends know int32
+    gloo = dist.get_backend() == "gloo"
+    if gloo:
+        wire = wire.cpu()
+    elif not wire.is_cuda:
+        raise ValueError("allgather_labels: the nccl backend gathers device tensors")
+    out = torch.empty((world, wire.numel()), dtype=torch.int32, device=wire.device)
+    if gloo:
+        dist.all_gather(list(out.unbind(0)), wire)  # the rows of `out` are the receive buffers
+    else:
+        dist.all_gather_into_tensor(out, wire)
+    return out.view(t.dtype)
+
+
 def barrier():
     dist = _dist()
     if dist is not None and dist.get_world_size() > 1:

@@ -576,20 +576,75 @@ class BestMatchFrame(FilteredFrame):
 COPY_NODES = 1 << 26  # labels per spk_components_copy
 
 
+def _merges_across_ranks(job):
+    """The job's pairs are one rank's shard of a pair set split over the process group (or a test forces that path at
+    one rank): its clusters are the merge of every rank's."""
+    return job.reduces_across_ranks() or job.force_reduce
+
+
+def _refuse_unreachable_shards(job, what):
+    """A job with an explicit shard and no process group over the shards cannot reach the other shards' pairs."""
+    if job.n_shards > 1 and not job.reduces_across_ranks():
+        raise ValueError(f"{what} on one of a job's shards without a process group over all of them: a record's "
+                         "cluster spans the shards' pairs, and the other shards are out of reach (run one rank per "
+                         "shard, or merge the shards' labels yourself with Context.components_merge, DESIGN.md)")
+
+
+def _merge_ranks_labels(job, n_nodes, copy_device, copy_host, merge):
+    """Gather every rank's labels of one result (a collective) and merge them into this rank's: copy_device(tensor) /
+    copy_host() read this rank's labels, merge(peers) is components_merge or one level's components_sweep_merge.
+    Under nccl the labels never leave the devices; under gloo they are staged through the host.  Returns merge's
+    (n_clusters, rounds).  Ranks are gathered COMPONENTS_MAX_PEERS at a time."""
+    import torch
+    from . import distributed as D
+    from ._native import COMPONENTS_MAX_PEERS
+    if D.stream_ordered_reduce(job.device):
+        mine = torch.empty(n_nodes, dtype=torch.int32, device=f"cuda:{job.device}")
+        copy_device(mine)
+    else:
+        mine = torch.from_numpy(copy_host().view(np.int32))
+    peers = D.allgather_labels(mine, force=job.force_reduce)
+    out = None
+    for g in range(0, peers.shape[0], COMPONENTS_MAX_PEERS):
+        part = peers[g:g + COMPONENTS_MAX_PEERS]
+        n_clusters, rounds = merge(part if part.is_cuda else part.numpy())
+        out = (n_clusters, rounds + (out[1] if out else 0))
+    return out
+
+
+def _merge_sweep_level(job, n_nodes, level):
+    """_merge_ranks_labels for one level of the sweep the context holds."""
+    ctx = job.ctx
+    return _merge_ranks_labels(
+        job, n_nodes, lambda out: ctx.components_sweep_copy_device(level, out),
+        lambda: _copy_in_ranges(lambda s, c: ctx.components_sweep_copy(level, s, c), n_nodes, np.uint32),
+        lambda peers: ctx.components_sweep_merge(level, peers))
+
+
+def _refuse_sharded_metrics(job, what):
+    if _merges_across_ranks(job):
+        raise ValueError(f"{what} on a sharded job: node degrees and cluster edge counts need every shard's pairs, and "
+                         "a rank holds the edges of its own shard only (the merged labels, n_clusters and "
+                         "truth_table() are available)")
+
+
 class ClusterFrame(SplinkDataFrame):
     """`filtered.clusters()`: one row per input record, in input order (two input tables: left rows, then right).
 
     cluster_id (int64) is the smallest input position among the records of the cluster, so
     `inputs.iloc[cluster_id]` is its representative; then the unique id, and for the two-table link types
-    _source_table ('left' / 'right').  A record no kept pair touches is a cluster of its own."""
+    _source_table ('left' / 'right').  A record no kept pair touches is a cluster of its own.
+
+    On a job sharded over a process group every rank labels its shard's pairs, the ranks all-gather their labels and
+    each merges them on its device (spk_components_merge): every rank ends with the one-GPU cluster_ids, bit for bit.
+    Materialising the frame (toPandas, n_clusters, rounds, truth_table) is then a collective: every rank makes the same
+    calls in the same order.  metrics() needs degrees over all shards' pairs and is refused there."""
 
     def __init__(self, filtered: FilteredFrame):
         job = filtered.job
         if getattr(job, "passthrough", None) is not None:
             raise ValueError("clusters() needs the records: a job made from a gamma table has pairs without rows")
-        if job.n_shards > 1:
-            raise ValueError("clusters() on a sharded job: a record's cluster spans the shards' pairs (merge the "
-                             "shards' (node, label) pairs with spk_components_edges, DESIGN.md)")
+        _refuse_unreachable_shards(job, "clusters()")
         self.filtered = filtered
         self.job = job
         self.settings = filtered.settings
@@ -606,11 +661,15 @@ class ClusterFrame(SplinkDataFrame):
         """Select (the frame's re-select rules), then label: the labels are copied at once, so a later selection or
         components call of the job does not reach this frame."""
         if self._labels is None:
-            ctx = self.job.ctx
+            job, ctx = self.job, self.job.ctx
             self.filtered._select()
             n_nodes, n_clusters, rounds = ctx.components()
-            parts = [ctx.components_copy(s, min(COPY_NODES, n_nodes - s)) for s in range(0, n_nodes, COPY_NODES)]
-            self._labels = np.concatenate(parts) if parts else np.empty(0, dtype=np.uint32)
+            if _merges_across_ranks(job):  # a collective: this rank's rounds plus the merge's
+                n_clusters, more = _merge_ranks_labels(
+                    job, n_nodes, ctx.components_copy_device,
+                    lambda: _copy_in_ranges(ctx.components_copy, n_nodes, np.uint32), ctx.components_merge)
+                rounds += more
+            self._labels = _copy_in_ranges(ctx.components_copy, n_nodes, np.uint32)
             self._info = (int(n_nodes), int(n_clusters), int(rounds))
         return self._labels
 
@@ -632,16 +691,21 @@ class ClusterFrame(SplinkDataFrame):
         frame's own selection, whatever its score, so clusters of pairs with NULL scores are covered too.  The sweep's
         labels are this frame's (the same definition over the same pairs): a frame that has none yet takes them, and
         one that has them does not copy them again."""
+        _refuse_sharded_metrics(self.job, "metrics()")
         self._sweep_all()
         return ClusterMetrics(self, self._labels, self.job.ctx, 0)
 
     def _sweep_all(self):
-        """Make the context's sweep the one level of every pair of this frame's selection."""
+        """Make the context's sweep the one level of every pair of this frame's selection (on a job sharded over the
+        process group: of every rank's, merged -- a collective)."""
         from ._native import SEL_ALL
         job = self.job
         job.sweep_owner = None
         self.filtered._select()
         n_nodes, _, n_clusters, rounds = job.ctx.components_sweep(SEL_ALL, [])
+        if _merges_across_ranks(job):
+            n_clusters[0], more = _merge_sweep_level(job, int(n_nodes), 0)
+            rounds[0] += more
         if self._labels is None:
             self._labels = _copy_in_ranges(lambda s, c: job.ctx.components_sweep_copy(0, s, c), int(n_nodes), np.uint32)
             self._info = (int(n_nodes), int(n_clusters[0]), int(rounds[0]))
@@ -768,7 +832,11 @@ class _SweepLevelFrame(ClusterFrame):
 class ClusterSweepFrame(SplinkDataFrame):
     """`filtered.clusters_at_thresholds(thresholds)`: the clusters of the frame's pairs with score > t, for every t, from
     one selection and one nested sweep on the device (spk_components_sweep).  One row per input record, in input
-    order, and one column cluster_id_{t!r} per threshold, each equal to clusters(t)'s cluster_id."""
+    order, and one column cluster_id_{t!r} per threshold, each equal to clusters(t)'s cluster_id.
+
+    On a job sharded over a process group every rank sweeps its shard's pairs and the ranks merge level by level
+    (spk_components_sweep_merge), so toPandas(), at(t) and truth_table() are collectives: every rank makes the same
+    calls in the same order and ends with the one-GPU frames.  metrics() and summary() are refused there."""
 
     def __init__(self, filtered: FilteredFrame, thresholds, by=None):
         from .select import BEST_BY
@@ -784,8 +852,7 @@ class ClusterSweepFrame(SplinkDataFrame):
         if getattr(job, "passthrough", None) is not None:
             raise ValueError("clusters_at_thresholds() needs the records: a job made from a gamma table has pairs "
                              "without rows")
-        if job.n_shards > 1:
-            raise ValueError("clusters_at_thresholds() on a sharded job: a record's cluster spans the shards' pairs")
+        _refuse_unreachable_shards(job, "clusters_at_thresholds()")
         self.filtered = filtered
         self.job = job
         self.settings = filtered.settings
@@ -795,11 +862,20 @@ class ClusterSweepFrame(SplinkDataFrame):
         self._info = None    # (n_nodes, n_edges [L], n_clusters [L], rounds [L]), levels in descending threshold
 
     def _sweep(self):
-        """Make the context's sweep this frame's (the frame's re-select rules, then the sweep)."""
+        """Make the context's sweep this frame's (the frame's re-select rules, then the sweep).  On a job sharded over
+        the process group the ranks then gather and merge level by level (a collective per level, n_nodes labels per
+        rank in flight), n_edges is summed over the ranks and n_clusters are the merged counts."""
+        from . import distributed as D
         job = self.job
         job.sweep_owner = None
         self.filtered._select()
         info = job.ctx.components_sweep(self._field, self._desc)
+        if _merges_across_ranks(job):
+            n_nodes, n_edges, n_clusters, rounds = info
+            for k in range(len(self._desc)):
+                n_clusters[k], more = _merge_sweep_level(job, int(n_nodes), k)
+                rounds[k] += more
+                n_edges[k] = D.sum_over_ranks(int(n_edges[k]))
         job.sweep_owner = self
         return info
 
@@ -856,6 +932,7 @@ class ClusterSweepFrame(SplinkDataFrame):
     def metrics(self, t):
         """Cluster and node metrics at threshold t: a `ClusterMetrics`."""
         k = self._level_of(t)
+        _refuse_sharded_metrics(self.job, "metrics()")
         self._held()
         return ClusterMetrics(self.at(t), self._labels[k], self.job.ctx, k)
 
@@ -874,6 +951,7 @@ class ClusterSweepFrame(SplinkDataFrame):
         """One row per threshold, in the order given: threshold, n_edges (pairs with score > threshold), n_clusters,
         n_clusters_multi (clusters of two or more records), records_clustered (records in those), largest_cluster,
         rounds."""
+        _refuse_sharded_metrics(self.job, "summary()")
         self._held()
         rows = []
         for t in self.thresholds:

@@ -13,6 +13,9 @@ spk_components.hip:
 and the loop ends after the first round in which no atomic lowered a word.  Labels only decrease, and only to ids
 of the same component, so at that point every label is the smallest id of its component (see the kernel file).
 
+components_sweep adds the levels of spk_components_sweep, components_merge the rounds of spk_components_merge (one
+launch per round: the jump, then per node the star edges to the other ranks' labels), under the same model.
+
     python tools/emulate_components.py            # round counts of the test graphs, against a union-find
 """
 import numpy as np
@@ -113,6 +116,50 @@ def components_sweep(n_nodes, u, v, level, n_levels, climb=CLIMB, round_cap=ROUN
     return np.stack(out) if out else np.empty((0, n_nodes), dtype=np.uint32), rounds_per_level
 
 
+def components_merge(label, peers, climb=CLIMB, round_cap=ROUND_CAP):
+    """spk_components_merge's rounds under the same model: `label` is one rank's final labels, peers [P, n] the other
+    ranks' over the same node ids.  A round is one launch (there is no edge list, so no hook launch): per node v the
+    jump, then for every peer p the star edge (v, peers[p][v]) -- an entry equal to v is skipped -- every climb against
+    the launch's own snapshot, every write landing at its end.  A hook re-parents the larger end only if it is a root
+    (the device's compare-and-swap against its own id: the rank's own components live in the labels alone, so no node
+    may be cut off its parent).  At least one round runs; the loop ends after the first one in which every star edge
+    had equal ends and no word was lowered.  Returns (labels uint32 [n], rounds)."""
+    label = np.asarray(label, dtype=np.int64).copy()
+    peers = np.asarray(peers, dtype=np.int64).reshape(-1, len(label))
+    nodes = np.arange(len(label), dtype=np.int64)
+    if ((peers > nodes) | (peers < 0)).any():
+        raise ValueError("a peer label is greater than its own index")
+    for rounds in range(1, round_cap + 1):
+        before = label
+        up = _climb(label, nodes, climb)
+        nxt = np.minimum(label, up)
+        hooked = False  # a star edge with different ends: the round is not quiet, whether or not its swap lands
+        for q in peers:
+            star = q != nodes
+            a, b = up[star], _climb(label, q[star], climb)
+            ne = a != b
+            hooked |= bool(ne.any())
+            hi, lo = np.maximum(a[ne], b[ne]), np.minimum(a[ne], b[ne])
+            root = label[hi] == hi  # the device swaps the larger end only while it is its own label
+            if root.any():
+                np.minimum.at(nxt, hi[root], lo[root])
+        label = nxt
+        if np.array_equal(label, before) and not hooked:
+            return label.astype(np.uint32), rounds
+    raise RuntimeError("merge: no fixed point within %d rounds" % round_cap)
+
+
+def deal_edges(n_edges, parts, how):
+    """The part of every edge: "round_robin" (edge i to part i % parts, so a long path forms only in the union) or
+    "blocks" (contiguous ranges of the edge list)."""
+    i = np.arange(n_edges, dtype=np.int64)
+    if how == "round_robin":
+        return i % parts
+    if how == "blocks":
+        return i * parts // max(n_edges, 1)
+    raise ValueError(how)
+
+
 def alternating_path(n=65536):
     """The path 0 - 1 - ... - n-1 in two levels: the odd edges (2i+1, 2i+2) are level 0, the even ones (2i, 2i+1)
     level 1, so level 1 joins n / 2 pairs into one path."""
@@ -193,6 +240,14 @@ def main():
             print("%-7s sweep of %d levels, %s: rounds %s  labels %s" % (
                 name, n_levels, "every edge up to the level" if prefix else "new edges and star edges", rounds,
                 "equal" if np.array_equal(got, want) else "DIFFER"))
+        want = union_find(n, u, v)
+        for parts in (2, 3, 8):
+            for how in ("round_robin", "blocks"):
+                part = deal_edges(len(u), parts, how)
+                own = [components(n, u[part == p], v[part == p]) for p in range(parts)]
+                got, rounds = components_merge(own[0][0], np.stack([lab for lab, _ in own[1:]]))
+                print("%-7s merge of %d parts dealt %-11s: own rounds %s  merge rounds %3d  labels %s" % (
+                    name, parts, how, [r for _, r in own], rounds, "equal" if np.array_equal(got, want) else "DIFFER"))
 
 
 if __name__ == "__main__":
