@@ -711,6 +711,35 @@ int spk_cluster_metrics_set_mode(spk_ctx *ctx, int mode);
 /* The level of the last spk_cluster_metrics (-1: none) and, with timing on, the milliseconds of its kernels. */
 int spk_cluster_metrics_info(spk_ctx *ctx, int *out_level, double *out_ms);
 
+/* Bridges and 2-edge-connected cores of one level of the last sweep (later releases: the edge metric is_bridge of
+ * compute_graph_metrics).  The level's graph is its cumulative edge set as stored, over n_nodes nodes.  An edge with
+ * u != v is a bridge iff deleting that one stored edge leaves u and v in different components: a self-loop never is, and
+ * an edge stored twice never is, in either orientation (host edge lists allow repeats, a selection has none).  For a
+ * bridge (u, v), side_u and side_v are the node counts of the two parts its cluster falls into without it (their sum is
+ * the cluster's size).  core[v] is the smallest node id of v's component once every bridge is cut -- its
+ * 2-edge-connected component; a node without edges keeps core[v] = v.  Bridges come in the orientation in which the edge
+ * is stored (a selection: u the left row's node, v the right's), ascending by (u, v).  Exact integers that depend on
+ * neither the spanning tree chosen nor the arrival order of the atomics: two calls give the same bytes.
+ * out4 = bridges, cores (nodes with core[v] == v), nodes of the largest core, depth of the deepest breadth-first tree
+ * (rooted at each cluster's smallest id).  The forest takes depth + 1 host-driven rounds over the level's edges (0
+ * without edges); a tree deeper than 4095 is SPK_E_LIMIT (a chain of thousands of records).  The result (16 bytes per
+ * bridge, 4 per node, under [6] of spk_ctx_memory) is a value of its own: a call that fails past its argument checks
+ * leaves none, and the sweep as it was; it is replaced by the next spk_cluster_bridges and dropped with the sweep (and
+ * by spk_components_sweep_merge); it and the arrays of spk_cluster_metrics do not disturb each other.  SPK_E_STATE without
+ * a sweep or on one with a merged level (its edges are one shard's), SPK_E_INVALID for a level outside it.  Reads the
+ * sweep only: its labels and metrics, the labels of spk_components, the selection, scores, tf and EM state are
+ * untouched. */
+int spk_cluster_bridges(spk_ctx *ctx, int level, int64_t *out4);
+/* Bridges [start, start + count) of the last spk_cluster_bridges, in (u, v) order; any out may be NULL.  SPK_E_STATE:
+ * none; SPK_E_INVALID: a range outside them. */
+int spk_cluster_bridges_copy(spk_ctx *ctx, int64_t start, int64_t count, uint32_t *out_u, uint32_t *out_v,
+                             uint32_t *out_side_u, uint32_t *out_side_v);
+/* core[v] of nodes [start, start + count) of the last spk_cluster_bridges. */
+int spk_cluster_bridges_cores_copy(spk_ctx *ctx, int64_t start, int64_t count, uint32_t *out_core);
+/* The level of the last spk_cluster_bridges (-1: none), its forest rounds, and with timing on the device milliseconds
+ * of its kernels (the host round trip after each round is not in it), -1 otherwise. */
+int spk_cluster_bridges_info(spk_ctx *ctx, int *out_level, int *out_rounds, double *out_ms);
+
 /* ---- clusters against labels (no counterpart in the reference release) ---- */
 #define SPK_AGREE_FIELDS 10
 /* Every level of the current sweep (spk_components_sweep / _sweep_edges) against one truth id per node.

@@ -19,7 +19,7 @@ from .check_types import check_types
 from .comparison_evaluation import (DEFAULT_MAX_ENUMERATE, BlockingProfile, get_largest_blocks,
                                     profile_blocking_rules)
 from .expectation_step import run_expectation_step
-from .frames import (BestMatchFrame, ClusterFrame, ClusterMetrics, ClusterSweepFrame, FilteredFrame,
+from .frames import (BestMatchFrame, ClusterBridges, ClusterFrame, ClusterMetrics, ClusterSweepFrame, FilteredFrame,
                      SplinkDataFrame)
 from .gammas import add_gammas
 from .iterate import iterate
@@ -33,7 +33,7 @@ from .validate import validate_settings
 
 __all__ = ["Splink", "load_from_json", "AmdSession", "session", "Params", "block_using_rules", "add_gammas",
            "iterate", "run_expectation_step", "make_adjustment_for_term_frequencies", "complete_settings_dict",
-           "ClusterFrame", "ClusterSweepFrame", "ClusterMetrics", "FilteredFrame", "BestMatchFrame", "LabelCounts", "estimate_from_labels",
+           "ClusterFrame", "ClusterSweepFrame", "ClusterMetrics", "ClusterBridges", "FilteredFrame", "BestMatchFrame", "LabelCounts", "estimate_from_labels",
            "estimate_u_using_random_sampling", "random_pairs", "get_largest_blocks", "profile_blocking_rules",
            "BlockingProfile"]
 

@@ -50,6 +50,9 @@ SELECT_CHUNK = 2048
 # Edges per workgroup step of the components' hooking kernel.  Mirrored from CC_CHUNK in csrc/spk_components.hip
 # (256 threads x one 16-byte vector of ids each); only the tests' edge sizes depend on it.
 COMPONENTS_CHUNK = 1024
+# The forest rounds spk_cluster_bridges runs at most (a spanning tree of depth BRIDGES_MAX_ROUNDS - 1).  Mirrored from
+# BR_MAX_ROUNDS in csrc/spk_bridges.hip; only the tests' limit case depends on it.
+BRIDGES_MAX_ROUNDS = 4096
 COMPONENTS_MAX_PEERS = 64  # SPK_COMPONENTS_MAX_PEERS: label arrays per components_merge call
 assert OPERAND_DTYPE.itemsize == 40 and INSTR_DTYPE.itemsize == 32 and PROGRAM_DTYPE.itemsize == 16
 
@@ -84,6 +87,7 @@ EXPORTS = [
     "spk_components_sweep_copy_device",
     "spk_cluster_metrics", "spk_cluster_metrics_copy", "spk_cluster_metrics_info",
     "spk_cluster_metrics_set_mode",
+    "spk_cluster_bridges", "spk_cluster_bridges_copy", "spk_cluster_bridges_cores_copy", "spk_cluster_bridges_info",
     "spk_label_histogram", "spk_label_info",
     "spk_cluster_agreement", "spk_cluster_agreement_info",
     "spk_pairs_sample", "spk_pairs_sample_info",
@@ -985,6 +989,37 @@ class Context:
         ms = ctypes.c_double(-1.0)
         check(self._lib.spk_cluster_metrics_info(self._h, ctypes.byref(lv), ctypes.byref(ms)), "spk_cluster_metrics_info")
         return lv.value, ms.value
+
+    def cluster_bridges(self, level: int):
+        """spk_cluster_bridges of one level of the last sweep: (bridges, cores, nodes of the largest core, depth of the
+        deepest breadth-first tree)."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self._lib.spk_cluster_bridges(self._h, ctypes.c_int(int(level)), _ptr(out)), "spk_cluster_bridges")
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+    def cluster_bridges_copy(self, start: int, count: int):
+        """Bridges [start, start + count) of the last cluster_bridges, ascending by (u, v): (u, v, side_u, side_v), uint32
+        each; u -- v in the stored orientation, side_* the nodes on that end's side once the bridge is cut."""
+        k = max(count, 0)
+        u, v, su, sv = (np.empty(k, dtype=np.uint32) for _ in range(4))
+        check(self._lib.spk_cluster_bridges_copy(self._h, ctypes.c_int64(start), ctypes.c_int64(count), _ptr(u), _ptr(v),
+                                                 _ptr(su), _ptr(sv)), "spk_cluster_bridges_copy")
+        return u, v, su, sv
+
+    def cluster_bridges_cores_copy(self, start: int, count: int) -> np.ndarray:
+        """core[v] (uint32) of nodes [start, start + count) of the last cluster_bridges."""
+        out = np.empty(max(count, 0), dtype=np.uint32)
+        check(self._lib.spk_cluster_bridges_cores_copy(self._h, ctypes.c_int64(start), ctypes.c_int64(count), _ptr(out)),
+              "spk_cluster_bridges_cores_copy")
+        return out
+
+    def cluster_bridges_info(self):
+        """(level of the last cluster_bridges or -1, its forest rounds or -1, ms of its kernels with timing on or -1)."""
+        lv, r = ctypes.c_int(-1), ctypes.c_int(-1)
+        ms = ctypes.c_double(-1.0)
+        check(self._lib.spk_cluster_bridges_info(self._h, ctypes.byref(lv), ctypes.byref(r), ctypes.byref(ms)),
+              "spk_cluster_bridges_info")
+        return lv.value, r.value, ms.value
 
     # ---- pairs against labels -----------------------------------------------------------------
     def label_histogram(self, ids0, ids1=None, lam=None, one_minus=None, m=None, u=None):

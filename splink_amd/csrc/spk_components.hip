@@ -522,20 +522,28 @@ static int cc_fixed_point(spk_ctx *ctx, int64_t n_nodes, const uint32_t *hu, con
     return SPK_OK;
 }
 
+// k_cc_init and the round loop over one edge list (spk_internal.h): spk_components*, and the cores of spk_bridges.hip.
+int components_of_edges(spk_ctx *ctx, int64_t n_nodes, int64_t n_edges, const uint32_t *eu, const uint32_t *ev,
+                        uint32_t *label, int bad_code, const char *bad_msg, const char *limit_msg, StageTimer &T,
+                        int *out_rounds, int64_t *out_n_clusters) {
+    DevBuf<unsigned int> flags;
+    DevBuf<unsigned long long> count;
+    SPK_TRY(flags.alloc(2));
+    SPK_TRY(count.alloc(1));
+    SPK_TRY(T.open());
+    k_cc_init<<<cc_grid(ctx, n_nodes, CC_THREADS), CC_THREADS, 0, ctx->stream>>>(n_nodes, label);
+    SPK_HIP(hipGetLastError());
+    return cc_fixed_point(ctx, n_nodes, eu, ev, n_edges, label, Stars{}, flags.p, count.p, bad_code, bad_msg, limit_msg,
+                          T, out_rounds, out_n_clusters);
+}
+
 // Labels of the graph (eu, ev) [n_edges] over n_nodes nodes into C, a local of the caller.  T: possibly open around
 // the caller's edge build.
 static int build_components(spk_ctx *ctx, int64_t n_nodes, int64_t n_edges, const uint32_t *eu, const uint32_t *ev,
                             int bad_code, const char *bad_msg, StageTimer &T, Components &C) {
-    DevBuf<unsigned int> flags;
-    DevBuf<unsigned long long> count;
     SPK_TRY(C.label.alloc((size_t)n_nodes + 1));
-    SPK_TRY(flags.alloc(2));
-    SPK_TRY(count.alloc(1));
-    SPK_TRY(T.open());
-    k_cc_init<<<cc_grid(ctx, n_nodes, CC_THREADS), CC_THREADS, 0, ctx->stream>>>(n_nodes, C.label.p);
-    SPK_HIP(hipGetLastError());
-    SPK_TRY(cc_fixed_point(ctx, n_nodes, eu, ev, n_edges, C.label.p, Stars{}, flags.p, count.p, bad_code, bad_msg,
-                           "spk_components: no fixed point within 256 rounds", T, &C.rounds, &C.n_clusters));
+    SPK_TRY(components_of_edges(ctx, n_nodes, n_edges, eu, ev, C.label.p, bad_code, bad_msg,
+                                "spk_components: no fixed point within 256 rounds", T, &C.rounds, &C.n_clusters));
     C.n_nodes = n_nodes;
     C.n_edges = n_edges;
     C.ms = T.result();
@@ -977,6 +985,7 @@ extern "C" int spk_components_sweep_merge(spk_ctx *ctx, int level, int n_peers, 
     W.merged = true;  // from here on the level's labels are no longer those of the stored edges
     W.m_level = -1;
     W.m_ms = -1.0;
+    W.bridges.clear();  // they described the stored edges' own components
     StageTimer T{ctx};
     int rounds = 0;
     int64_t n_clusters = 0;

@@ -3595,7 +3595,9 @@ extern "C" int spk_ctx_memory(spk_ctx *ctx, int64_t *out8) {
            b(ctx->sel.tf_mp) + b(ctx->sel.adj) +
            b(ctx->comp.label) +
            b(ctx->sweep.label) + b(ctx->sweep.eu) + b(ctx->sweep.ev) + b(ctx->sweep.degree) + b(ctx->sweep.size) +
-           b(ctx->sweep.max_degree) + b(ctx->sweep.degree_sum);
+           b(ctx->sweep.max_degree) + b(ctx->sweep.degree_sum) +
+           b(ctx->sweep.bridges.u) + b(ctx->sweep.bridges.v) + b(ctx->sweep.bridges.side_u) +
+           b(ctx->sweep.bridges.side_v) + b(ctx->sweep.bridges.core);
     for (int i = 0; i < 7; ++i) m[7] += m[i];
     for (int i = 0; i < 8; ++i) out8[i] = m[i];
     return SPK_OK;

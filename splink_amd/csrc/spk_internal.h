@@ -314,6 +314,19 @@ struct Components {
 // `Components`: built in a local and moved into the context, so a failing call leaves none.  It keeps the edges
 // bucketed by level (8 bytes per edge), so spk_cluster_metrics can run later without the selection; the metrics of
 // one level at a time live in it too (recomputed per call, freed with it).
+// The bridges and cores of one level of the sweep (spk_bridges.hip), by node id.  A value of its own inside the sweep
+// it describes: built in a local and moved in at the end of spk_cluster_bridges, so a failing call leaves none; gone
+// with the sweep.  Nothing in it is read or written by the metrics, and it reads none of theirs.
+struct ClusterBridges {
+    int level = -1;  // -1: none
+    int64_t n_nodes = 0, n_bridges = 0, n_cores = 0, largest_core = 0, depth = 0;
+    int rounds = 0;            // forest rounds, the last quiet one included
+    DevBuf<uint32_t> u, v, side_u, side_v;  // [n_bridges], ascending by (u, v)
+    DevBuf<uint32_t> core;     // [n_nodes]
+    double ms = -1.0;          // device milliseconds of its kernels (timing on), -1 = none
+    void clear() { *this = ClusterBridges(); }
+};
+
 struct ComponentSweep {
     bool valid = false;
     int levels = 0;
@@ -334,6 +347,7 @@ struct ComponentSweep {
     double m_ms = -1.0;
     DevBuf<uint32_t> degree, size, max_degree;
     DevBuf<unsigned long long> degree_sum;
+    ClusterBridges bridges;  // spk_cluster_bridges: the level they describe is bridges.level
     void clear() { *this = ComponentSweep(); }
 };
 
@@ -631,6 +645,13 @@ struct StageTimer {
     }
     double result() const { return ctx->timing ? ms : -1.0; }  // what the *_info calls report
 };
+
+// spk_components.hip, also for spk_bridges.hip: label [n_nodes] (the caller's device words) = the smallest node id of
+// each node's component in the graph (eu, ev) [n_edges], by k_cc_init and the components' round loop.  eu and ev start
+// 16-byte aligned (k_cc_hook's loads).  bad_code / bad_msg: an id >= n_nodes; limit_msg: the round cap.  T may be open.
+int components_of_edges(spk_ctx *ctx, int64_t n_nodes, int64_t n_edges, const uint32_t *eu, const uint32_t *ev,
+                        uint32_t *label, int bad_code, const char *bad_msg, const char *limit_msg, StageTimer &T,
+                        int *out_rounds, int64_t *out_n_clusters);
 
 int ensure_desc(spk_ctx *ctx, Table &t);
 // Finishes the last spk_gammas (work-list overflow, huge pass) once the stream is synchronised;

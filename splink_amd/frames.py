@@ -638,7 +638,7 @@ class ClusterFrame(SplinkDataFrame):
     On a job sharded over a process group every rank labels its shard's pairs, the ranks all-gather their labels and
     each merges them on its device (spk_components_merge): every rank ends with the one-GPU cluster_ids, bit for bit.
     Materialising the frame (toPandas, n_clusters, rounds, truth_table) is then a collective: every rank makes the same
-    calls in the same order.  metrics() needs degrees over all shards' pairs and is refused there."""
+    calls in the same order.  metrics() needs degrees over all shards' pairs and is refused there, and so is bridges()."""
 
     def __init__(self, filtered: FilteredFrame):
         job = filtered.job
@@ -694,6 +694,13 @@ class ClusterFrame(SplinkDataFrame):
         _refuse_sharded_metrics(self.job, "metrics()")
         self._sweep_all()
         return ClusterMetrics(self, self._labels, self.job.ctx, 0)
+
+    def bridges(self):
+        """The bridges and 2-edge-connected cores of these clusters (a `ClusterBridges`): which link joined them?  Over
+        the same one-level sweep of every pair of the frame's selection that metrics() takes."""
+        _refuse_sharded_metrics(self.job, "bridges()")
+        self._sweep_all()
+        return ClusterBridges(self, self._labels, self.job.ctx, 0)
 
     def _sweep_all(self):
         """Make the context's sweep the one level of every pair of this frame's selection (on a job sharded over the
@@ -815,12 +822,87 @@ class ClusterMetrics:
         return out
 
 
+def bridge_edge_columns(settings, link_type):
+    """The columns of ClusterBridges.edges(): cluster_id, the pair's unique ids as df_e names them, _source_table_l / _r
+    where df_e has them (link_and_dedupe), the records on each side of the bridge, and the cluster's size."""
+    uid = settings["unique_id_column_name"]
+    cols = ["cluster_id", uid + "_l", uid + "_r"]
+    if link_type == "link_and_dedupe":
+        cols += ["_source_table_l", "_source_table_r"]
+    return cols + ["nodes_l", "nodes_r", "n_nodes"]
+
+
+def bridge_rows(side_u, side_v, min_side=1):
+    """The positions of the bridges with min(nodes_l, nodes_r) >= min_side, in device order: min_side=2 drops the
+    bridges by which a single record hangs."""
+    try:
+        ok = int(min_side) == min_side and min_side >= 1
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"edges: min_side is a whole number >= 1, not {min_side!r}")
+    return np.flatnonzero(np.minimum(side_u, side_v) >= int(min_side))
+
+
+class ClusterBridges:
+    """The bridges and cores of one set of clusters, found on the device (spk_cluster_bridges) and held on the host.  A
+    bridge is a kept pair whose removal splits its cluster; a core is what stays connected when every bridge is cut.
+    n_bridges, n_cores, largest_core (its records) and depth (of the deepest breadth-first tree, from each cluster's
+    first record) are the call's scalars."""
+
+    def __init__(self, frame, labels, ctx, level):
+        self._frame = frame  # a ClusterFrame-shaped frame: the records' ids
+        self._labels = labels
+        n = len(labels)
+        self.n_bridges, self.n_cores, self.largest_core, self.depth = ctx.cluster_bridges(level)
+        self.rounds = ctx.cluster_bridges_info()[1]
+        cols = [[], [], [], []]
+        for s in range(0, self.n_bridges, COPY_NODES):
+            for c, part in zip(cols, ctx.cluster_bridges_copy(s, min(COPY_NODES, self.n_bridges - s))):
+                c.append(part)
+        self.u, self.v, self.side_u, self.side_v = [
+            np.concatenate(c) if c else np.empty(0, dtype=np.uint32) for c in cols]
+        self.core = _copy_in_ranges(ctx.cluster_bridges_cores_copy, n, np.uint32)
+
+    def edges(self, min_side=1):
+        """One row per bridge, ascending by the pair's input positions (bridge_edge_columns): nodes_l / nodes_r are the
+        records left on the left / right record's side when the pair is cut, n_nodes their sum, the cluster's size.
+        Every record that hangs by one pair gives a (1, n - 1) row; min_side=2 keeps the bridges between groups."""
+        job, frame = self._frame.job, self._frame
+        keep = bridge_rows(self.side_u, self.side_v, min_side)
+        u, v = self.u[keep].astype(np.int64), self.v[keep].astype(np.int64)
+        records = ClusterFrame.toPandas(frame)
+        uid = frame.settings["unique_id_column_name"]
+        data = OrderedDict()
+        data["cluster_id"] = self._labels[u].astype(np.int64)
+        data[uid + "_l"] = records[uid].to_numpy()[u]
+        data[uid + "_r"] = records[uid].to_numpy()[v]
+        if job.link_type == "link_and_dedupe":
+            data["_source_table_l"] = records["_source_table"].to_numpy()[u]
+            data["_source_table_r"] = records["_source_table"].to_numpy()[v]
+        data["nodes_l"] = self.side_u[keep].astype(np.int64)
+        data["nodes_r"] = self.side_v[keep].astype(np.int64)
+        data["n_nodes"] = data["nodes_l"] + data["nodes_r"]
+        return pd.DataFrame(data, columns=bridge_edge_columns(frame.settings, job.link_type))
+
+    def cores(self):
+        """The cluster frame's columns plus core_id: the smallest input position among the records that stay connected
+        to this one when every bridge is cut ("the clusters if every bridge were cut")."""
+        out = ClusterFrame.toPandas(self._frame)
+        out["core_id"] = self.core.astype(np.int64)
+        return out
+
+
 class _SweepLevelFrame(ClusterFrame):
     """ClusterSweepFrame.at(t): its `filtered` is the sweep's wide frame, so the metrics are the sweep's at t."""
 
     def metrics(self):
         sweep, t = self._of
         return sweep.metrics(t)
+
+    def bridges(self):
+        sweep, t = self._of
+        return sweep.bridges(t)
 
     def truth_table(self, label_column):
         """The sweep's truth-table row at this frame's threshold."""
@@ -836,7 +918,7 @@ class ClusterSweepFrame(SplinkDataFrame):
 
     On a job sharded over a process group every rank sweeps its shard's pairs and the ranks merge level by level
     (spk_components_sweep_merge), so toPandas(), at(t) and truth_table() are collectives: every rank makes the same
-    calls in the same order and ends with the one-GPU frames.  metrics() and summary() are refused there."""
+    calls in the same order and ends with the one-GPU frames.  metrics(), summary() and bridges() are refused there."""
 
     def __init__(self, filtered: FilteredFrame, thresholds, by=None):
         from .select import BEST_BY
@@ -936,6 +1018,13 @@ class ClusterSweepFrame(SplinkDataFrame):
         self._held()
         return ClusterMetrics(self.at(t), self._labels[k], self.job.ctx, k)
 
+    def bridges(self, t):
+        """The bridges and cores of the clusters at threshold t: a `ClusterBridges`."""
+        k = self._level_of(t)
+        _refuse_sharded_metrics(self.job, "bridges()")
+        self._held()
+        return ClusterBridges(self.at(t), self._labels[k], self.job.ctx, k)
+
     def truth_table(self, label_column):
         """The clusters at every threshold against `label_column` of the input tables, one row per threshold in the
         order given (labels.cluster_truth_rows): a pair of labelled records is predicted at t iff both lie in one
@@ -970,6 +1059,6 @@ def reject_filtered(frame, what):
     if isinstance(frame, FilteredFrame):
         raise ValueError(f"{what} does not take a filtered frame (it would run over all of the job's pairs, not the "
                          "survivors): pass the frame filter() was called on")
-    if isinstance(frame, (ClusterFrame, ClusterSweepFrame, ClusterMetrics)):
+    if isinstance(frame, (ClusterFrame, ClusterSweepFrame, ClusterMetrics, ClusterBridges)):
         raise ValueError(f"{what} does not take a cluster frame (it holds records, not pairs): pass the frame "
                          "filter() was called on")
