@@ -798,6 +798,55 @@ int spk_label_histogram(spk_ctx *ctx, const int64_t *ids_side0, const int64_t *i
  * the histogram; the uploads and read-backs are not in it), -1 otherwise. */
 int spk_label_info(spk_ctx *ctx, int64_t *out_pairs, double *out_ms);
 
+/* ---- scores against labels, per pair (replaces taking the frame make_adjustment_for_term_frequencies returns, or a
+ *      filtered frame, to the host with the label column retained and counting the confusion matrix there) ---- */
+#define SPK_LABEL_SCORE_MAX_THRESHOLDS 1024
+/* Pairs per (truth state, score bin) where the score is decided per pair.  thresholds[0 .. n_thresholds) are ascending
+ * doubles (duplicates and +-inf allowed, n_thresholds 0..SPK_LABEL_SCORE_MAX_THRESHOLDS); bin(s) = the number of k with
+ * s > thresholds[k], the strict test of SPK_SEL_GT on the same doubles, so it lies in 0..n_thresholds; a NaN (NULL)
+ * score falls in bin n_thresholds + 1.  out_counts[s * (n_thresholds + 2) + bin], state-major, states and label ids
+ * as for spk_label_histogram (one id per record in device row order, negative = NULL, narrowed to 32 bits on the
+ * device: an id >= 2^31 is SPK_E_INVALID; label_ids1 may be NULL unless the job is link_only).  The counts are exact
+ * integers that do not depend on launch shape or on the arrival order of the atomics: ranks holding shards sum them.
+ *
+ * spk_label_scores_tf* (replaces spk_tf_apply* over every pair followed by a host group-by with the labels): every
+ * pair of the context, scored by tf_adjusted_match_prob under lambda / one_minus / m / u and the given value ids and
+ * tables -- host value ids as for spk_tf_apply, device dictionary ids of the columns `cols` as for
+ * spk_tf_apply_columns.  The value is the one spk_tf_apply* gives for the pair, bit for bit (one shared device
+ * function); mp comes from a pattern table built for the call, never from spk_score's scores.  m and u are required,
+ * n_tf_cols is 1..8, and the context needs codes and a pair set with rows (SPK_E_STATE for a loaded gamma table).
+ * Nothing of P elements is stored.
+ * SPK_E_INVALID: NULL label_ids0; NULL label_ids1 under link_only; NULL out_counts; more than
+ * SPK_LABEL_SCORE_MAX_THRESHOLDS thresholds, a NaN threshold or a descending pair of them; an id >= 2^31.
+ * SPK_E_STATE also when a pair names a row outside its table or a code outside the pattern space (it is not counted).
+ * The calls read the pairs, codes and tables (spk_label_scores_selection: the selection) and write nothing of the
+ * context but the numbers of spk_label_scores_info: the selection, the scores of spk_score, the device-resident tf
+ * results, the tf sums, EM and component state are untouched, and every device buffer of a call is freed before it
+ * returns. */
+int spk_label_scores_tf(spk_ctx *ctx, const int64_t *label_ids0, const int64_t *label_ids1, double lambda,
+                        double one_minus, const double *m, const double *u, int n_tf_cols,
+                        const int64_t *const *ids_side0, const int64_t *const *ids_side1,
+                        const double *const *adj_tables, const int64_t *table_sizes, int n_thresholds,
+                        const double *thresholds,
+                        uint64_t *out_counts /* host [SPK_LABEL_STATES x (n_thresholds + 2)], state-major */);
+int spk_label_scores_tf_columns(spk_ctx *ctx, const int64_t *label_ids0, const int64_t *label_ids1, double lambda,
+                                double one_minus, const double *m, const double *u, int n_tf_cols, const int32_t *cols,
+                                const double *const *adj_tables, const int64_t *table_sizes, int n_thresholds,
+                                const double *thresholds, uint64_t *out_counts);
+/* The same over the survivors of the context's selection, one narrowed by spk_select_best included (replaces
+ * spk_select_copy* of every survivor followed by the host group-by).  field SPK_SEL_MP: the score is the selection's
+ * own match_probability of the survivor's pattern; SPK_SEL_TF_MP: its tf_adjusted_match_prob.  An empty selection is
+ * legal and counts nothing.  SPK_E_INVALID: unknown field, and the argument errors above.  SPK_E_STATE: no selection;
+ * a stale one; one without pair rows (a loaded gamma table); SPK_SEL_MP on a selection made without m / u;
+ * SPK_SEL_TF_MP on one not made by spk_select_tf*. */
+int spk_label_scores_selection(spk_ctx *ctx, const int64_t *label_ids0, const int64_t *label_ids1,
+                               int field /* SPK_SEL_MP | SPK_SEL_TF_MP */, int n_thresholds, const double *thresholds,
+                               uint64_t *out_counts);
+/* The last spk_label_scores_*: pairs counted (-1: none yet, or the last call failed), and with timing on
+ * (spk_ctx_enable_timing) the device milliseconds of its launches (id narrowing, pattern table, counter clear and
+ * the counting kernel; the uploads, the value-id staging and the read-backs are not in it), -1 otherwise. */
+int spk_label_scores_info(spk_ctx *ctx, int64_t *out_pairs, double *out_ms);
+
 /* ---- term-frequency adjustment (term_frequencies.py:122-168) ------------------- */
 /* For value ids of one column (per row, -1 NULL; both sides in one id space) accumulate, over
  * pairs with equal non-null values, Σ mp and count(mp) per value id (n_values slots), after spk_score.

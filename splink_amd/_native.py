@@ -89,6 +89,7 @@ EXPORTS = [
     "spk_cluster_metrics_set_mode",
     "spk_cluster_bridges", "spk_cluster_bridges_copy", "spk_cluster_bridges_cores_copy", "spk_cluster_bridges_info",
     "spk_label_histogram", "spk_label_info",
+    "spk_label_scores_tf", "spk_label_scores_tf_columns", "spk_label_scores_selection", "spk_label_scores_info",
     "spk_cluster_agreement", "spk_cluster_agreement_info",
     "spk_pairs_sample", "spk_pairs_sample_info",
     "spk_block_profile", "spk_block_profile_info", "spk_block_profile_set_cut",
@@ -110,6 +111,12 @@ LABEL_NON_MATCH, LABEL_MATCH, LABEL_UNKNOWN, LABEL_STATES = 0, 1, 2, 3  # SPK_LA
 # lds_per_block()); past it the counts go to global memory.  Mirrored from LH_LDS_BYTES in csrc/spk_labels.hip;
 # only the tests' choice of pattern spaces depends on it.
 LABEL_LDS_BYTES = 64 * 1024
+LABEL_SCORE_MAX_THRESHOLDS = 1024  # SPK_LABEL_SCORE_MAX_THRESHOLDS
+# Pairs one workgroup of spk_label_scores_tf*'s kernel takes per step (256 threads x 8 pairs) and the workgroups per
+# compute unit its grid is capped at.  Mirrored from LS_THREADS, LS_PAIRS and LS_WG_PER_CU in csrc/spk_labels.hip; only
+# the tests' edge sizes depend on them.
+LABEL_SCORE_STEP = 256 * 8
+LABEL_SCORE_WG_PER_CU = 3
 AGREE_FIELDS = 10  # SPK_AGREE_FIELDS: the columns of cluster_agreement, in labels.AGREEMENT_FIELDS' order
 TF_LIMBS = 14  # SPK_TF_LIMBS
 
@@ -1053,6 +1060,83 @@ class Context:
         n = ctypes.c_int64(-1)
         ms = ctypes.c_double(-1.0)
         check(self._lib.spk_label_info(self._h, ctypes.byref(n), ctypes.byref(ms)), "spk_label_info")
+        return n.value, ms.value
+
+    # ---- scores against labels, per pair ------------------------------------------------------
+    @staticmethod
+    def _score_args(label_ids0, label_ids1, thresholds):
+        """(ids0, ids1 or None, thresholds float64, zeroed counts uint64 [3, T + 2]) as the spk_label_scores_* calls
+        take them; an empty id array becomes one the library never reads."""
+        ids0 = np.ascontiguousarray(label_ids0, dtype=np.int64)
+        ids1 = None if label_ids1 is None else np.ascontiguousarray(label_ids1, dtype=np.int64)
+        if ids0.size == 0:
+            ids0 = np.zeros(1, np.int64)
+        if ids1 is not None and ids1.size == 0:
+            ids1 = np.zeros(1, np.int64)
+        t = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        return ids0, ids1, t, np.zeros((LABEL_STATES, len(t) + 2), dtype=np.uint64)
+
+    def label_scores_tf(self, label_ids0, label_ids1, lam, one_minus, m, u, ids0_list, ids1_list, tables,
+                        thresholds) -> np.ndarray:
+        """spk_label_scores_tf: int64 [3, T + 2], every pair per (LABEL_* state, bin of tf_adjusted_match_prob): bin b
+        in 0..T = b of the ascending `thresholds` lie below the score, bin T + 1 = a NULL score.  Label ids as for
+        label_histogram, parameters, host value ids and tables as for select_tf."""
+        n = len(tables)
+        if len(ids0_list) != n or len(ids1_list) != n:
+            raise ValueError("label_scores_tf: one id array per side and table")
+        keep = [np.ascontiguousarray(a, dtype=np.int64) for a in ids0_list] + \
+               [np.ascontiguousarray(a, dtype=np.int64) for a in ids1_list] + \
+               [np.ascontiguousarray(t, dtype=np.float64) if len(t) else np.zeros(1) for t in tables]
+        P = ctypes.c_void_p * max(n, 1)
+        ids0 = P(*[a.ctypes.data for a in keep[:n]])
+        ids1 = P(*[a.ctypes.data for a in keep[n:2 * n]])
+        tabs = P(*[a.ctypes.data for a in keep[2 * n:]])
+        sizes = np.array([len(t) for t in tables] + [0], dtype=np.int64)
+        lab0, lab1, t, counts = self._score_args(label_ids0, label_ids1, thresholds)
+        m = np.ascontiguousarray(m, dtype=np.float64)
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        check(self._lib.spk_label_scores_tf(self._h, _ptr(lab0), _ptr(lab1), ctypes.c_double(lam),
+                                            ctypes.c_double(one_minus), _ptr(m), _ptr(u), ctypes.c_int(n), ids0, ids1,
+                                            tabs, _ptr(sizes), ctypes.c_int(len(t)),
+                                            _ptr(t) if len(t) else ctypes.c_void_p(0), _ptr(counts)),
+              "spk_label_scores_tf")
+        return counts.astype(np.int64)
+
+    def label_scores_tf_columns(self, label_ids0, label_ids1, lam, one_minus, m, u, cols, tables,
+                                thresholds) -> np.ndarray:
+        """spk_label_scores_tf_columns: the same with the value ids taken from the device dictionary ids of the string
+        columns `cols` (as select_tf_columns)."""
+        n = len(tables)
+        if len(cols) != n:
+            raise ValueError("label_scores_tf_columns: one column per table")
+        keep = [np.ascontiguousarray(t, dtype=np.float64) if len(t) else np.zeros(1) for t in tables]
+        tabs = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in keep])
+        sizes = np.array([len(t) for t in tables] + [0], dtype=np.int64)
+        cols = np.ascontiguousarray(list(cols) + [0], dtype=np.int32)
+        lab0, lab1, t, counts = self._score_args(label_ids0, label_ids1, thresholds)
+        m = np.ascontiguousarray(m, dtype=np.float64)
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        check(self._lib.spk_label_scores_tf_columns(self._h, _ptr(lab0), _ptr(lab1), ctypes.c_double(lam),
+                                                    ctypes.c_double(one_minus), _ptr(m), _ptr(u), ctypes.c_int(n),
+                                                    _ptr(cols), tabs, _ptr(sizes), ctypes.c_int(len(t)),
+                                                    _ptr(t) if len(t) else ctypes.c_void_p(0), _ptr(counts)),
+              "spk_label_scores_tf_columns")
+        return counts.astype(np.int64)
+
+    def label_scores_selection(self, label_ids0, label_ids1, field: int, thresholds) -> np.ndarray:
+        """spk_label_scores_selection: int64 [3, T + 2] over the survivors of the last select* (or select_best), by
+        `field` (SEL_MP or SEL_TF_MP); bins as for label_scores_tf."""
+        lab0, lab1, t, counts = self._score_args(label_ids0, label_ids1, thresholds)
+        check(self._lib.spk_label_scores_selection(self._h, _ptr(lab0), _ptr(lab1), ctypes.c_int(int(field)),
+                                                   ctypes.c_int(len(t)), _ptr(t) if len(t) else ctypes.c_void_p(0),
+                                                   _ptr(counts)), "spk_label_scores_selection")
+        return counts.astype(np.int64)
+
+    def label_scores_info(self):
+        """(pairs the last label_scores_* counted or -1, ms of its launches with timing on or -1)."""
+        n = ctypes.c_int64(-1)
+        ms = ctypes.c_double(-1.0)
+        check(self._lib.spk_label_scores_info(self._h, ctypes.byref(n), ctypes.byref(ms)), "spk_label_scores_info")
         return n.value, ms.value
 
     # ---- clusters against labels --------------------------------------------------------------

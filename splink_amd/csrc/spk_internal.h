@@ -529,6 +529,9 @@ struct spk_ctx {
     // its launches; its buffers live for the call only
     int64_t label_pairs = -1;
     double label_ms = -1.0;
+    // the last spk_label_scores_* (spk_labels.hip): the same two numbers; its buffers live for the call only
+    int64_t score_pairs = -1;
+    double score_ms = -1.0;
     // the last spk_cluster_agreement (spk_agreement.hip): levels it scored (-1: none yet), device milliseconds of its
     // launches; a failing call leaves both as they were, and its buffers live for the call only
     int agree_levels = -1;

@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "spk_internal.h"
+#include "spk_tf_pair.h"
 
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "spk_labels.hip targets gfx950 (MI355X) only"
@@ -179,6 +180,357 @@ static int launch_label_hist(spk_ctx *ctx, const LabelArgs &A, bool lds) {
     return SPK_OK;
 }
 
+// The label ids of one call on the device, 32 bits per record in device row order: locals of the entry points.
+struct LabelIds {
+    DevBuf<int64_t> wide;
+    DevBuf<int32_t> lab0, lab1;
+    DevBuf<unsigned int> bad;  // [1]: 1 = an id of 2^31 or more (read here), 2 = set by the counting kernels
+    bool second = false;       // the right rows have an id array of their own
+    const int32_t *side0() const { return lab0.p; }
+    const int32_t *side1() const { return second ? lab1.p : lab0.p; }
+};
+
+// Uploads and narrows the ids of n0 / n1 records (k_label_narrow, inside T's intervals; the upload itself is not a
+// launch: outside them).  An id of 2^31 or more is SPK_E_INVALID.  Leaves *L.bad = 0 and the stream synchronised.
+static int stage_label_ids(spk_ctx *ctx, const char *what, const int64_t *ids_side0, const int64_t *ids_side1,
+                           int64_t n0, int64_t n1, StageTimer &T, LabelIds &L) {
+    hipStream_t st = ctx->stream;
+    L.second = ids_side1 && (ctx->link_type == SPK_LINK_ONLY || ids_side1 != ids_side0);
+    SPK_TRY(L.wide.alloc((size_t)std::max(n0, L.second ? n1 : 0) + 1));
+    SPK_TRY(L.lab0.alloc((size_t)n0 + 1));
+    if (L.second) SPK_TRY(L.lab1.alloc((size_t)n1 + 1));
+    SPK_TRY(L.bad.alloc(1));
+    SPK_HIP(hipMemsetAsync(L.bad.p, 0, sizeof(unsigned int), st));
+    auto narrow = [&](const int64_t *ids, int64_t n, int32_t *out) -> int {
+        if (n == 0) return SPK_OK;
+        SPK_HIP(hipMemcpyAsync(L.wide.p, ids, (size_t)n * 8, hipMemcpyHostToDevice, st));
+        SPK_TRY(T.open());
+        k_label_narrow<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, L.wide.p, out, L.bad.p);
+        SPK_HIP(hipGetLastError());
+        return T.close();  // synchronises: the next upload reuses `wide`; the source is borrowed for the call
+    };
+    SPK_TRY(narrow(ids_side0, n0, L.lab0.p));
+    if (L.second) SPK_TRY(narrow(ids_side1, n1, L.lab1.p));
+    unsigned int h_bad = 0u;
+    SPK_HIP(hipMemcpyAsync(&h_bad, L.bad.p, sizeof(h_bad), hipMemcpyDeviceToHost, st));
+    SPK_HIP(hipStreamSynchronize(st));
+    SPK_REQUIRE(h_bad == 0u, SPK_E_INVALID, std::string(what) + ": a label id of 2^31 or more");
+    return SPK_OK;
+}
+
+// ---- pairs per (truth state, score bin), the score decided per pair -------------------------------------------
+// spk_label_scores_*: the counting that k_label_hist does per pattern, for scores that are not a function of the
+// pattern alone (tf_adjusted_match_prob) or for pair sets that are not the context's (a selection's survivors).
+// Thresholds t[0..T) ascending; bin(s) = #{k : s > t[k]} in 0..T (filter's `>`), a NaN score in bin T + 1; counters
+// [3 x (T + 2)], state-major.  Both kernels keep the thresholds (8 T bytes) and 32-bit counters (12 (T + 2) bytes) in
+// LDS -- 20.3 KB at T = 1024, so several workgroups stay resident per CU -- add with one LDS atomic per pair (no ballot
+// aggregation: profiles/ab_labels_agg.log) and flush the non-empty counters with 64-bit global atomics.
+constexpr int LS_THREADS = 256;
+constexpr int LS_PAIRS = 8;       // all-pairs kernel: pairs per lane and step, as k_select_tf_count's slab (no scratch)
+// Workgroups per CU the grid is capped at (a compile-time switch for tools/ab_label_scores.py's A/B): 3 is what
+// k_label_scores_tf's 140 VGPRs keep resident (3 waves per SIMD, a workgroup puts one on each), so every workgroup
+// runs from the first cycle and takes an equal share of the steps.  cfg2 link job, device ms of the call at T = 72 /
+// 1024: 0.25 / 0.31 with 3, 0.32 / 0.40 with 4 (a quarter of the workgroups start when the others are done):
+// profiles/ab_label_scores.log.
+#ifndef SPK_LABEL_SCORE_WG_PER_CU
+#define SPK_LABEL_SCORE_WG_PER_CU 3
+#endif
+constexpr int LS_WG_PER_CU = SPK_LABEL_SCORE_WG_PER_CU;
+constexpr int LS_SEL_WG_PER_CU = 8;  // k_label_scores_sel (16 VGPRs): 32 waves per CU
+constexpr int64_t LS_BLOCK_PAIRS_MAX = (int64_t)1 << 31;  // pairs one workgroup may count (32-bit LDS counters)
+
+struct ScoreArgs {
+    int64_t P;                   // pairs of the context, or survivors of the selection
+    const int32_t *pl, *pr;      // their rows
+    const int32_t *lab0, *lab1;  // label id per device row of the left / right table (-1 = NULL)
+    uint32_t n0, n1;             // their row counts
+    uint32_t n_pat;
+    int T;                       // thresholds, 0..SPK_LABEL_SCORE_MAX_THRESHOLDS
+    int top;                     // the largest power of two <= T (0: T = 0): the search's first stride
+    const double *thr;           // [T] ascending, no NaN
+    const double *mpat;          // mp per pattern [n_pat] (the call's own or the selection's), or null
+    const uint32_t *code;        // selection kernel: the survivors' codes
+    const double *per_pair;      // selection kernel: the survivors' tf_adjusted_match_prob, or null = mpat[code]
+    unsigned long long *gcnt;    // [3 x (T + 2)], zeroed before the launch
+    unsigned int *bad;           // set to 2 when a pair names a row or a code out of range (it is not counted)
+};
+
+// bin(s): the thresholds below s, by strides top, top / 2, .., 1 (at most 11, the same for every lane); the index is
+// clamped so that every read lies inside th[0..T), and no step branches.
+__device__ __forceinline__ uint32_t score_bin(double s, const double *th, uint32_t T, int top) {
+    uint32_t pos = 0;
+    for (int step = top; step > 0; step >>= 1) {
+        const uint32_t k = pos + (uint32_t)step;  // >= 1
+        const double t = th[min(k, T) - 1u];
+        pos = (k <= T && s > t) ? k : pos;
+    }
+    return s != s ? T + 1u : pos;
+}
+
+__device__ __forceinline__ void score_add(uint32_t *cnt, const ScoreArgs &A, const double *th, int32_t a, int32_t b,
+                                          double s) {
+    const uint32_t state = (a < 0 || b < 0) ? (uint32_t)SPK_LABEL_UNKNOWN : (uint32_t)(a == b);
+    atomicAdd(&cnt[state * ((uint32_t)A.T + 2u) + score_bin(s, th, (uint32_t)A.T, A.top)], 1u);
+}
+
+// LDS of both kernels: the thresholds, then the counters (cleared); ends with a barrier.
+__device__ __forceinline__ uint32_t *score_lds_init(const ScoreArgs &A, double *s_th) {
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(s_th + A.T);
+    for (int i = threadIdx.x; i < A.T; i += LS_THREADS) s_th[i] = A.thr[i];
+    for (int b = threadIdx.x; b < 3 * (A.T + 2); b += LS_THREADS) cnt[b] = 0;
+    __syncthreads();
+    return cnt;
+}
+
+__device__ __forceinline__ void score_lds_flush(const ScoreArgs &A, const uint32_t *cnt) {
+    __syncthreads();
+    for (int b = threadIdx.x; b < 3 * (A.T + 2); b += LS_THREADS) {
+        const uint32_t n = cnt[b];
+        if (n) atomicAdd(&A.gcnt[b], (unsigned long long)n);
+    }
+}
+
+// Every pair of the context against the labels, by tf_adjusted_match_prob under the call's tables F and mp table.
+// k_label_hist's shape: each lane takes LS_PAIRS consecutive pairs per step, their rows as two 16-byte vectors per
+// side and their codes as one (uint16_t) or two (uint32_t), all coalesced; the loop exit is wave-uniform; the tail
+// (P mod LS_PAIRS) is workgroup 0's first wave.  The gathers are issued as k_select_tf_count issues them: the labels
+// and mp of all the lane's pairs, then column by column the value ids of every pair, the table entries, the fold
+// (tf_begin / tf_adj / tf_fold / tf_finish, spk_tf_pair.h: the bits of spk_tf_apply*).  A row or a code out of range
+// sets *bad and the pair gathers and counts nothing.  A workgroup counts at most LS_BLOCK_PAIRS_MAX + one step's
+// pairs (score_grid), so no LDS word wraps.
+template <typename CodeT>
+__global__ __launch_bounds__(LS_THREADS) void k_label_scores_tf(ScoreArgs A, TfApply F, const CodeT *__restrict__ codes) {
+    extern __shared__ __attribute__((aligned(16))) double s_th[];
+    uint32_t *cnt = score_lds_init(A, s_th);
+    constexpr int V = LS_PAIRS;
+    const int lane = threadIdx.x & 63;
+    const int64_t n_vec = A.P / V;
+    const uint4 *lv = reinterpret_cast<const uint4 *>(A.pl);
+    const uint4 *rv = reinterpret_cast<const uint4 *>(A.pr);
+    const uint4 *cv = reinterpret_cast<const uint4 *>(codes);
+    constexpr int CW = V * (int)sizeof(CodeT) / 16;  // 16-byte code vectors per step: 1 or 2
+    for (int64_t v = (int64_t)blockIdx.x * LS_THREADS + threadIdx.x;; v += (int64_t)gridDim.x * LS_THREADS) {
+        const bool in = v < n_vec;
+        if (!__any(in)) break;  // wave-uniform
+        uint32_t l[V], r[V], c[V];
+        unsigned ok = 0;  // bit j: pair j is inside P and names rows and a code in range
+#pragma unroll
+        for (int j = 0; j < V; ++j) l[j] = r[j] = c[j] = 0u;
+        if (in) {
+            const uint4 l0 = lv[2 * v], l1 = lv[2 * v + 1], r0 = rv[2 * v], r1 = rv[2 * v + 1];
+            l[0] = l0.x, l[1] = l0.y, l[2] = l0.z, l[3] = l0.w, l[4] = l1.x, l[5] = l1.y, l[6] = l1.z, l[7] = l1.w;
+            r[0] = r0.x, r[1] = r0.y, r[2] = r0.z, r[3] = r0.w, r[4] = r1.x, r[5] = r1.y, r[6] = r1.z, r[7] = r1.w;
+            uint4 w[CW];
+#pragma unroll
+            for (int j = 0; j < CW; ++j) w[j] = cv[CW * v + j];
+            const CodeT *e = reinterpret_cast<const CodeT *>(w);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                c[j] = (uint32_t)e[j];
+                ok |= (l[j] < A.n0 && r[j] < A.n1 && c[j] < A.n_pat ? 1u : 0u) << j;
+            }
+            if (ok != (1u << V) - 1u) *A.bad = 2u;
+        }
+        int32_t la[V], lb[V];
+        double m[V], a[V], b[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            la[j] = lb[j] = -1;
+            m[j] = 0.0;
+            if ((ok >> j) & 1u) {
+                la[j] = A.lab0[l[j]];
+                lb[j] = A.lab1[r[j]];
+                m[j] = A.mpat[c[j]];
+            }
+            tf_begin(m[j], a[j], b[j]);
+        }
+        for (int t = 0; t < F.n; ++t) {
+            const int64_t *__restrict__ i0 = F.ids0[t];
+            const int64_t *__restrict__ i1 = F.ids1[t];
+            const double *__restrict__ tab = F.tab[t];
+            const int64_t tab_n = F.tab_n[t];
+            int64_t ia[V], ib[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                ia[j] = ib[j] = -1;
+                if ((ok >> j) & 1u) {
+                    ia[j] = i0[l[j]];
+                    ib[j] = i1[r[j]];
+                }
+            }
+            double x[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) x[j] = tf_adj(ia[j], ib[j], tab, tab_n);  // -1: no load; an id past the table: 0.5
+#pragma unroll
+            for (int j = 0; j < V; ++j) tf_fold(a[j], b[j], x[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j)
+            if ((ok >> j) & 1u) score_add(cnt, A, s_th, la[j], lb[j], tf_finish(m[j], a[j], b[j]));
+    }
+    // tail (P not a multiple of LS_PAIRS): workgroup 0's first wave, one pair per lane
+    if (blockIdx.x == 0 && threadIdx.x < 64) {
+        const int64_t p = n_vec * V + lane;
+        if (p < A.P) {
+            const uint32_t l = (uint32_t)A.pl[p], r = (uint32_t)A.pr[p], c = (uint32_t)codes[p];
+            if (l < A.n0 && r < A.n1 && c < A.n_pat)
+                score_add(cnt, A, s_th, A.lab0[l], A.lab1[r], tf_pair(F, A.mpat[c], (int32_t)l, (int32_t)r, nullptr));
+            else
+                *A.bad = 2u;
+        }
+    }
+    score_lds_flush(A, cnt);
+}
+
+// The survivors of a selection against the labels: one survivor per lane and step, its rows and code read coalesced
+// from the selection, its score mpat[code] (SPK_SEL_MP) or per_pair[q] (SPK_SEL_TF_MP).
+__global__ __launch_bounds__(LS_THREADS) void k_label_scores_sel(ScoreArgs A) {
+    extern __shared__ __attribute__((aligned(16))) double s_th[];
+    uint32_t *cnt = score_lds_init(A, s_th);
+    for (int64_t q = (int64_t)blockIdx.x * LS_THREADS + threadIdx.x; q < A.P; q += (int64_t)gridDim.x * LS_THREADS) {
+        const uint32_t l = (uint32_t)A.pl[q], r = (uint32_t)A.pr[q], c = A.code[q];
+        if (l < A.n0 && r < A.n1 && c < A.n_pat)
+            score_add(cnt, A, s_th, A.lab0[l], A.lab1[r], A.per_pair ? A.per_pair[q] : A.mpat[c]);
+        else
+            *A.bad = 2u;
+    }
+    score_lds_flush(A, cnt);
+}
+
+// Workgroups of either launch: wg_per_cu per CU (what the kernel's registers keep resident), never more than the
+// steps there are (one at least), and never so few that one workgroup would count more than LS_BLOCK_PAIRS_MAX pairs.
+static unsigned score_grid(const spk_ctx *ctx, int64_t P, int per_lane, int wg_per_cu) {
+    const int64_t steps = (P / per_lane + LS_THREADS - 1) / LS_THREADS;
+    int64_t g = std::min<int64_t>(steps, wg_per_cu * (int64_t)ctx->n_cu);
+    g = std::max<int64_t>(g, (P + LS_BLOCK_PAIRS_MAX - 1) / LS_BLOCK_PAIRS_MAX);
+    return (unsigned)std::max<int64_t>(g, 1);
+}
+
+static size_t score_lds_bytes(int T) { return (size_t)T * 8 + (size_t)3 * (T + 2) * 4; }
+
+// What the spk_label_scores_* entry points share.  check(): the arguments (SPK_E_INVALID).  stage(): the label ids and
+// thresholds on the device and zeroed counters.  finish(): the read-back, behind the interval's end.
+struct ScoreCall {
+    spk_ctx *ctx;
+    const char *what;
+    int T = 0;
+    LabelIds L;
+    DevBuf<double> thr;
+    DevBuf<unsigned long long> cnt;
+    StageTimer timer;
+    ScoreCall(spk_ctx *c, const char *w) : ctx(c), what(w), timer{c} {}
+
+    int check(const int64_t *ids0, const int64_t *ids1, int n_thresholds, const double *thresholds,
+              const uint64_t *out_counts) {
+        const std::string w(what);
+        SPK_REQUIRE(ids0, SPK_E_INVALID, w + ": null label_ids0");
+        SPK_REQUIRE(ctx->link_type != SPK_LINK_ONLY || ids1, SPK_E_INVALID,
+                    w + ": link_only needs the right table's label_ids1");
+        SPK_REQUIRE(out_counts, SPK_E_INVALID, w + ": null out_counts");
+        SPK_REQUIRE(n_thresholds >= 0 && n_thresholds <= SPK_LABEL_SCORE_MAX_THRESHOLDS, SPK_E_INVALID,
+                    w + ": 0..SPK_LABEL_SCORE_MAX_THRESHOLDS (1024) thresholds");
+        SPK_REQUIRE(n_thresholds == 0 || thresholds, SPK_E_INVALID, w + ": null thresholds");
+        for (int k = 0; k < n_thresholds; ++k) {
+            SPK_REQUIRE(thresholds[k] == thresholds[k], SPK_E_INVALID, w + ": a threshold is NaN");
+            SPK_REQUIRE(k == 0 || thresholds[k] >= thresholds[k - 1], SPK_E_INVALID, w + ": the thresholds descend");
+        }
+        T = n_thresholds;
+        return SPK_OK;
+    }
+
+    int stage(const int64_t *ids0, const int64_t *ids1, const double *thresholds, int64_t n0, int64_t n1) {
+        SPK_REQUIRE((int64_t)score_lds_bytes(T) <= ctx->lds_per_block, SPK_E_LIMIT, std::string(what) + ": LDS");
+        SPK_TRY(thr.alloc((size_t)T + 1));
+        SPK_TRY(cnt.alloc((size_t)3 * (T + 2)));
+        SPK_TRY(stage_label_ids(ctx, what, ids0, ids1, n0, n1, timer, L));
+        if (T) SPK_HIP(hipMemcpyAsync(thr.p, thresholds, (size_t)T * 8, hipMemcpyHostToDevice, ctx->stream));
+        return SPK_OK;
+    }
+
+    void fill(ScoreArgs &A, int64_t P, const int32_t *pl, const int32_t *pr, int64_t n0, int64_t n1) {
+        A.P = P;
+        A.pl = pl;
+        A.pr = pr;
+        A.lab0 = L.side0();
+        A.lab1 = L.side1();
+        A.n0 = (uint32_t)n0;
+        A.n1 = (uint32_t)n1;
+        A.n_pat = (uint32_t)ctx->n_patterns;
+        A.T = T;
+        A.top = 0;
+        for (int s = 1; s <= T; s *= 2) A.top = s;
+        A.thr = thr.p;
+        A.gcnt = cnt.p;
+        A.bad = L.bad.p;
+    }
+
+    int finish(int64_t P, uint64_t *out_counts) {
+        hipStream_t st = ctx->stream;
+        unsigned int h_bad = 0u;
+        SPK_TRY(timer.stop());  // the read-backs are no launches
+        SPK_HIP(hipMemcpyAsync(&h_bad, L.bad.p, sizeof(h_bad), hipMemcpyDeviceToHost, st));
+        SPK_HIP(hipMemcpyAsync(out_counts, cnt.p, (size_t)3 * (T + 2) * 8, hipMemcpyDeviceToHost, st));
+        SPK_HIP(hipStreamSynchronize(st));
+        SPK_TRY(timer.add());
+        SPK_REQUIRE(h_bad == 0u, SPK_E_STATE,
+                    std::string(what) + ": a pair names a row outside its table or a code outside the pattern space");
+        ctx->score_pairs = P;
+        ctx->score_ms = timer.result();
+        return SPK_OK;
+    }
+};
+
+// spk_label_scores_tf*: the arguments and the state, before anything is staged.
+static int scores_tf_begin(ScoreCall &C, const int64_t *label_ids0, const int64_t *label_ids1, const double *m,
+                           const double *u, int n_tf_cols, bool ids_given, const double *const *adj_tables,
+                           const int64_t *table_sizes, int n_thresholds, const double *thresholds,
+                           const uint64_t *out_counts) {
+    spk_ctx *ctx = C.ctx;
+    const std::string w(C.what);
+    SPK_TRY(C.check(label_ids0, label_ids1, n_thresholds, thresholds, out_counts));
+    SPK_REQUIRE(m && u, SPK_E_INVALID, w + ": m and u are required");
+    SPK_REQUIRE(n_tf_cols >= 1 && n_tf_cols <= 8, SPK_E_INVALID, w + ": 1..8 columns");
+    SPK_REQUIRE(ids_given && adj_tables && table_sizes, SPK_E_INVALID, w + ": null arg");
+    SPK_REQUIRE(ctx->codes_valid, SPK_E_STATE, w + ": no gammas");
+    SPK_TRY(settle_gammas(ctx, nullptr));
+    SPK_REQUIRE(ctx->codes_valid, SPK_E_STATE, w + ": no gammas");
+    const int64_t P = ctx->n_pairs;
+    SPK_REQUIRE(ctx->pairs_valid && ctx->pl.p && ctx->pr.p && ctx->pl.n >= (size_t)P && ctx->pr.n >= (size_t)P,
+                SPK_E_STATE, w + ": no pair rows (a loaded gamma table)");
+    SPK_REQUIRE(ctx->n_patterns >= 1 && ctx->n_patterns <= (int64_t)UINT32_MAX, SPK_E_LIMIT, w + ": pattern space");
+    SPK_REQUIRE(ctx->table[0].n >= 0 && ctx->side_table(1).n >= 0, SPK_E_STATE, w + ": no tables");
+    return SPK_OK;
+}
+
+// The counting itself, once the value ids are staged in G.
+static int scores_tf_run(ScoreCall &C, TfStage &G, const int64_t *label_ids0, const int64_t *label_ids1, double lambda,
+                         double one_minus, const double *m, const double *u, const double *const *adj_tables,
+                         const int64_t *table_sizes, const double *thresholds, uint64_t *out_counts) {
+    spk_ctx *ctx = C.ctx;
+    const int64_t P = ctx->n_pairs, n0 = ctx->table[0].n, n1 = ctx->side_table(1).n;
+    hipStream_t st = ctx->stream;
+    SPK_TRY(tf_stage_tables(ctx, adj_tables, table_sizes, G));
+    DevBuf<double> mpat;  // mp per pattern under the call's parameters: never ctx->mp
+    SPK_TRY(mpat.alloc((size_t)ctx->n_patterns + 1));
+    SPK_TRY(C.stage(label_ids0, label_ids1, thresholds, n0, n1));
+    SPK_TRY(C.timer.open());
+    SPK_TRY(pattern_mp_table(ctx, lambda, one_minus, m, u, mpat.p));
+    SPK_HIP(hipMemsetAsync(C.cnt.p, 0, (size_t)3 * (C.T + 2) * 8, st));
+    if (P > 0) {
+        ScoreArgs A{};
+        C.fill(A, P, ctx->pl.p, ctx->pr.p, n0, n1);
+        A.mpat = mpat.p;
+        const unsigned g = score_grid(ctx, P, LS_PAIRS, LS_WG_PER_CU);
+        const size_t lds = score_lds_bytes(C.T);
+        if (ctx->code_bytes == 2)
+            k_label_scores_tf<uint16_t><<<g, LS_THREADS, lds, st>>>(A, G.T, reinterpret_cast<const uint16_t *>(ctx->codes.p));
+        else
+            k_label_scores_tf<uint32_t><<<g, LS_THREADS, lds, st>>>(A, G.T, reinterpret_cast<const uint32_t *>(ctx->codes.p));
+        SPK_HIP(hipGetLastError());
+    }
+    return C.finish(P, out_counts);
+}
+
 }  // namespace spk
 
 using namespace spk;
@@ -207,37 +559,16 @@ extern "C" int spk_label_histogram(spk_ctx *ctx, const int64_t *ids_side0, const
     Table &t0 = ctx->table[0], &t1 = ctx->side_table(1);
     SPK_REQUIRE(t0.n >= 0 && t1.n >= 0, SPK_E_STATE, "spk_label_histogram: no tables");
     const int64_t n0 = t0.n, n1 = t1.n;  // not link_only: t1 is t0, and ids_side1 (if given) describes its rows too
-    hipStream_t st = ctx->stream;
     // everything below lives for this call only
-    DevBuf<int64_t> wide;
-    DevBuf<int32_t> lab0, lab1;
+    LabelIds L;
     DevBuf<unsigned long long> hist;
     DevBuf<double> mpat;
-    DevBuf<unsigned int> bad;
-    const bool second = ids_side1 && (two || ids_side1 != ids_side0);  // the right rows have an id array of their own
-    SPK_TRY(wide.alloc((size_t)std::max(n0, second ? n1 : 0) + 1));
-    SPK_TRY(lab0.alloc((size_t)n0 + 1));
-    if (second) SPK_TRY(lab1.alloc((size_t)n1 + 1));
-    SPK_TRY(hist.alloc((size_t)3 * n_pat));
-    SPK_TRY(bad.alloc(1));
-    if (out_pattern_mp) SPK_TRY(mpat.alloc((size_t)n_pat));
-    SPK_HIP(hipMemsetAsync(bad.p, 0, sizeof(unsigned int), st));
     StageTimer T{ctx};
-    // ---- the label ids, narrowed to 32 bits on the device (the upload itself is not a launch: outside the interval)
-    auto narrow = [&](const int64_t *ids, int64_t n, int32_t *out) -> int {
-        if (n == 0) return SPK_OK;
-        SPK_HIP(hipMemcpyAsync(wide.p, ids, (size_t)n * 8, hipMemcpyHostToDevice, st));
-        SPK_TRY(T.open());
-        k_label_narrow<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, wide.p, out, bad.p);
-        SPK_HIP(hipGetLastError());
-        return T.close();  // synchronises: the next upload reuses `wide`; the source is borrowed for the call
-    };
-    SPK_TRY(narrow(ids_side0, n0, lab0.p));
-    if (second) SPK_TRY(narrow(ids_side1, n1, lab1.p));
+    SPK_TRY(hist.alloc((size_t)3 * n_pat));
+    if (out_pattern_mp) SPK_TRY(mpat.alloc((size_t)n_pat));
+    SPK_TRY(stage_label_ids(ctx, "spk_label_histogram", ids_side0, ids_side1, n0, n1, T, L));
+    hipStream_t st = ctx->stream;
     unsigned int h_bad = 0u;
-    SPK_HIP(hipMemcpyAsync(&h_bad, bad.p, sizeof(h_bad), hipMemcpyDeviceToHost, st));
-    SPK_HIP(hipStreamSynchronize(st));
-    SPK_REQUIRE(h_bad == 0u, SPK_E_INVALID, "spk_label_histogram: a label id of 2^31 or more");
     // ---- mp per pattern (spk_score's own kernel and arguments) and the counts
     SPK_TRY(T.open());
     if (out_pattern_mp) SPK_TRY(pattern_mp_table(ctx, lambda, one_minus, m, u, mpat.p));
@@ -247,19 +578,19 @@ extern "C" int spk_label_histogram(spk_ctx *ctx, const int64_t *ids_side0, const
         A.P = P;
         A.pl = ctx->pl.p;
         A.pr = ctx->pr.p;
-        A.lab0 = lab0.p;
-        A.lab1 = second ? lab1.p : lab0.p;
+        A.lab0 = L.side0();
+        A.lab1 = L.side1();
         A.n0 = (uint32_t)n0;
         A.n1 = (uint32_t)n1;
         A.n_pat = (uint32_t)n_pat;
         A.ghist = hist.p;
-        A.bad = bad.p;
+        A.bad = L.bad.p;
         const bool lds = 3 * n_pat * 4 <= std::min<int64_t>(LH_LDS_BYTES, ctx->lds_per_block);
         if (ctx->code_bytes == 2) SPK_TRY(launch_label_hist<uint16_t>(ctx, A, lds));
         else SPK_TRY(launch_label_hist<uint32_t>(ctx, A, lds));
     }
     SPK_TRY(T.stop());  // the read-backs are no launches
-    SPK_HIP(hipMemcpyAsync(&h_bad, bad.p, sizeof(h_bad), hipMemcpyDeviceToHost, st));
+    SPK_HIP(hipMemcpyAsync(&h_bad, L.bad.p, sizeof(h_bad), hipMemcpyDeviceToHost, st));
     SPK_HIP(hipMemcpyAsync(out_counts, hist.p, (size_t)3 * n_pat * 8, hipMemcpyDeviceToHost, st));
     if (out_pattern_mp) SPK_HIP(hipMemcpyAsync(out_pattern_mp, mpat.p, (size_t)n_pat * 8, hipMemcpyDeviceToHost, st));
     SPK_HIP(hipStreamSynchronize(st));
@@ -275,5 +606,86 @@ extern "C" int spk_label_info(spk_ctx *ctx, int64_t *out_pairs, double *out_ms) 
     SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_label_info: null ctx");
     if (out_pairs) *out_pairs = ctx->label_pairs;
     if (out_ms) *out_ms = ctx->label_ms;
+    return SPK_OK;
+}
+
+extern "C" int spk_label_scores_tf(spk_ctx *ctx, const int64_t *label_ids0, const int64_t *label_ids1, double lambda,
+                                   double one_minus, const double *m, const double *u, int n_tf_cols,
+                                   const int64_t *const *ids_side0, const int64_t *const *ids_side1,
+                                   const double *const *adj_tables, const int64_t *table_sizes, int n_thresholds,
+                                   const double *thresholds, uint64_t *out_counts) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_label_scores_tf: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    ctx->score_pairs = -1;
+    ctx->score_ms = -1.0;
+    ScoreCall C(ctx, "spk_label_scores_tf");
+    SPK_TRY(scores_tf_begin(C, label_ids0, label_ids1, m, u, n_tf_cols, ids_side0 && ids_side1, adj_tables, table_sizes,
+                            n_thresholds, thresholds, out_counts));
+    TfStage G;  // the id arrays and tables live until this call returns
+    SPK_TRY(tf_stage_host_ids(ctx, n_tf_cols, ids_side0, ids_side1, G));
+    return scores_tf_run(C, G, label_ids0, label_ids1, lambda, one_minus, m, u, adj_tables, table_sizes, thresholds,
+                         out_counts);
+}
+
+extern "C" int spk_label_scores_tf_columns(spk_ctx *ctx, const int64_t *label_ids0, const int64_t *label_ids1,
+                                           double lambda, double one_minus, const double *m, const double *u,
+                                           int n_tf_cols, const int32_t *cols, const double *const *adj_tables,
+                                           const int64_t *table_sizes, int n_thresholds, const double *thresholds,
+                                           uint64_t *out_counts) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_label_scores_tf_columns: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    ctx->score_pairs = -1;
+    ctx->score_ms = -1.0;
+    ScoreCall C(ctx, "spk_label_scores_tf_columns");
+    SPK_TRY(scores_tf_begin(C, label_ids0, label_ids1, m, u, n_tf_cols, cols != nullptr, adj_tables, table_sizes,
+                            n_thresholds, thresholds, out_counts));
+    TfStage G;
+    SPK_TRY(tf_stage_column_ids(ctx, n_tf_cols, cols, G));
+    return scores_tf_run(C, G, label_ids0, label_ids1, lambda, one_minus, m, u, adj_tables, table_sizes, thresholds,
+                         out_counts);
+}
+
+extern "C" int spk_label_scores_selection(spk_ctx *ctx, const int64_t *label_ids0, const int64_t *label_ids1, int field,
+                                          int n_thresholds, const double *thresholds, uint64_t *out_counts) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_label_scores_selection: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    ctx->score_pairs = -1;
+    ctx->score_ms = -1.0;
+    ScoreCall C(ctx, "spk_label_scores_selection");
+    SPK_TRY(C.check(label_ids0, label_ids1, n_thresholds, thresholds, out_counts));
+    SPK_REQUIRE(field == SPK_SEL_MP || field == SPK_SEL_TF_MP, SPK_E_INVALID,
+                "spk_label_scores_selection: unknown field");
+    const Selection &S = ctx->sel;
+    SPK_REQUIRE(S.valid, SPK_E_STATE, "spk_label_scores_selection: no selection (run spk_select*)");
+    SPK_REQUIRE(S.current(ctx), SPK_E_STATE,
+                "spk_label_scores_selection: the pairs or codes changed since spk_select*");
+    SPK_REQUIRE(S.has_rows, SPK_E_STATE, "spk_label_scores_selection: no pair rows (a loaded gamma table)");
+    SPK_REQUIRE(field != SPK_SEL_MP || S.has_mp, SPK_E_STATE, "spk_label_scores_selection: spk_select got no m / u");
+    SPK_REQUIRE(field != SPK_SEL_TF_MP || S.has_tf, SPK_E_STATE,
+                "spk_label_scores_selection: the selection was made without tf tables (spk_select)");
+    SPK_REQUIRE(ctx->n_patterns >= 1 && ctx->n_patterns <= (int64_t)UINT32_MAX, SPK_E_LIMIT,
+                "spk_label_scores_selection: pattern space");
+    const int64_t n = S.n, n0 = ctx->table[0].n, n1 = ctx->side_table(1).n;
+    SPK_REQUIRE(n0 >= 0 && n1 >= 0, SPK_E_STATE, "spk_label_scores_selection: no tables");
+    hipStream_t st = ctx->stream;
+    SPK_TRY(C.stage(label_ids0, label_ids1, thresholds, n0, n1));
+    SPK_TRY(C.timer.open());
+    SPK_HIP(hipMemsetAsync(C.cnt.p, 0, (size_t)3 * (C.T + 2) * 8, st));
+    if (n > 0) {
+        ScoreArgs A{};
+        C.fill(A, n, S.l.p, S.r.p, n0, n1);
+        A.code = S.code.p;
+        A.mpat = S.mpat.p;
+        A.per_pair = field == SPK_SEL_TF_MP ? S.tf_mp.p : nullptr;
+        k_label_scores_sel<<<score_grid(ctx, n, 1, LS_SEL_WG_PER_CU), LS_THREADS, score_lds_bytes(C.T), st>>>(A);
+        SPK_HIP(hipGetLastError());
+    }
+    return C.finish(n, out_counts);
+}
+
+extern "C" int spk_label_scores_info(spk_ctx *ctx, int64_t *out_pairs, double *out_ms) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_label_scores_info: null ctx");
+    if (out_pairs) *out_pairs = ctx->score_pairs;
+    if (out_ms) *out_ms = ctx->score_ms;
     return SPK_OK;
 }

@@ -220,6 +220,34 @@ def _label_counts(gamma_frame, label_column, lam=None, level_probs=None):
     return LabelCounts(names, levels, counts, mp, job.link_type, true_pairs_total(job.link_type, ids0, ids1))
 
 
+def _score_thresholds(thresholds, what):
+    """Thresholds as the spk_label_scores_* calls take them: float64, ascending (sorted here, as
+    LabelCounts.truth_table sorts them), no NaN, at most _native.LABEL_SCORE_MAX_THRESHOLDS."""
+    from . import _native as N
+    t = np.sort(np.asarray(list(thresholds), dtype=np.float64).reshape(-1))
+    if np.isnan(t).any():
+        raise ValueError(f"{what}: a threshold is NaN")
+    if len(t) > N.LABEL_SCORE_MAX_THRESHOLDS:
+        raise ValueError(f"{what}: {len(t)} thresholds, more than the {N.LABEL_SCORE_MAX_THRESHOLDS} one pass "
+                         "takes: pass explicit thresholds, fewer of them")
+    return t
+
+
+def _score_label_counts(job, counts, totals, t, ids0, ids1):
+    """ScoreLabelCounts of one rank's (or the one GPU's) counts [3, T + 2] and totals [3] (or None: the counts' own
+    row sums): on a sharded job both are summed over the ranks -- exact integers, so every rank ends with the one-GPU
+    table; every rank holds all the records, so the true pairs are counted locally."""
+    from . import distributed as D
+    from .labels import ScoreLabelCounts, true_pairs_total
+    if job.reduces_across_ranks() or job.force_reduce:
+        D.allreduce_host_(counts, force=job.force_reduce)
+        if totals is not None:
+            D.allreduce_host_(totals, force=job.force_reduce)
+    if totals is None:
+        totals = counts.sum(axis=1)
+    return ScoreLabelCounts(counts, t, totals, job.link_type, true_pairs_total(job.link_type, ids0, ids1))
+
+
 class ComparisonFrame(SplinkDataFrame):
     """Candidate pairs (block_using_rules)."""
 
@@ -518,6 +546,36 @@ class FilteredFrame(SplinkDataFrame):
         ties="first" keeps the pair that comes first in the frame, ties="all" every pair at the maximum."""
         return BestMatchFrame(self, per, ties, self._best_by[0] if by is None else by)
 
+    def _score_names(self):
+        """The scores this frame's pairs carry, the default first."""
+        return self._best_by
+
+    def truth_table(self, label_column, thresholds=None, by=None):
+        """This frame's pairs against the labels in the input column `label_column`, counted on the device
+        (spk_label_scores_selection), with LabelCounts.truth_table's columns.  thresholds=None: one row with
+        threshold = -inf that describes the frame as it stands -- every kept pair is a predicted match.  Given
+        thresholds: one row per threshold, ascending, the kept pairs with score > threshold predicted (a NULL score
+        never); by: the score, the frame's first by default.  fn and tn are taken against the labelled pairs among
+        all candidate pairs of the job, so what the filter or the best-match step dropped counts as missed."""
+        from . import _native as N
+        job = self.job
+        if getattr(job, "passthrough", None) is not None:
+            raise ValueError("truth_table() needs the records: a job made from a gamma table has pairs without rows")
+        names = self._score_names()
+        by = names[0] if by is None else by
+        if self._scored_parent() is None or by not in names:
+            raise ValueError(f"truth_table: this frame has no score {by!r}" +
+                             (" (it was filtered from an unscored frame)" if self._scored_parent() is None
+                              else f": by is one of {list(names)}"))
+        ids0, ids1 = _label_ids(job, label_column)  # a missing column fails before the device is touched
+        t = _score_thresholds([] if thresholds is None else thresholds, "truth_table")
+        self._select()
+        field = N.SEL_TF_MP if by == "tf_adjusted_match_prob" else N.SEL_MP
+        counts = job.ctx.label_scores_selection(ids0, ids1, field, t)
+        totals = job.ctx.label_histogram(ids0, ids1)[0].sum(axis=1)  # the parent's pairs: one pass, no scores
+        slc = _score_label_counts(job, counts, totals, t, ids0, ids1)
+        return slc.kept_row() if thresholds is None else slc.truth_table()
+
 
 class BestMatchFrame(FilteredFrame):
     """`filtered.best_matches(per, ties)`: lazily narrowed on the device.  The frame has the filtered frame's columns
@@ -549,6 +607,9 @@ class BestMatchFrame(FilteredFrame):
 
     def _extra_columns(self, n):
         return self.inner._extra_columns(n)
+
+    def _score_names(self):
+        return self.inner._score_names()
 
     def _refuse(self, *args, **kwargs):
         raise ValueError("a best-match frame takes no further filter() or best_matches(): filter first, then take the "

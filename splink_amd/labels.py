@@ -4,8 +4,10 @@ truth_space_table_from_labels_column, roc_chart_from_labels_column, estimate_m_f
 match_probability is a function of a pair's comparison pattern alone, so one device pass that counts the pairs per
 (truth state, pattern) (spk_label_histogram) leaves the host with everything it needs, over n_patterns rows only:
 the exact confusion matrix at every threshold, the true pairs blocking never produced, and the supervised estimate
-of m / u / λ -- one M-step with match_probability replaced by the label.  This module is the host side: pure
-numpy / pandas, importable without a device.
+of m / u / λ -- one M-step with match_probability replaced by the label.  Scores that are decided per pair
+(tf_adjusted_match_prob, the pairs a filter or a best-match step kept) are counted per (truth state, threshold bin)
+instead (spk_label_scores_*, ScoreLabelCounts).  This module is the host side: pure numpy / pandas, importable
+without a device.
 """
 from __future__ import annotations
 
@@ -183,6 +185,56 @@ class LabelCounts:
     def m_step(self):
         """(λ, π rows) in the shape engine.m_step_rows returns: the supervised estimate of the parameters."""
         return m_step_rows(self.m_step_stats(), self.names, self.n_levels)
+
+
+SCORE_TRUTH_COLUMNS = ("threshold", "tp", "fp", "tn", "fn", "n_unlabelled_above", "precision", "recall", "fpr", "f1",
+                       "recall_of_all_true_pairs")  # LabelCounts.truth_table's, in its order
+
+
+class ScoreLabelCounts:
+    """Pairs per (truth state, score bin) where the score is decided per pair (spk_label_scores_*): the counterpart
+    of LabelCounts for tf_adjusted_match_prob and for the pairs a filter or a best-match step kept.
+
+    thresholds: T ascending doubles; counts int64 [3, T + 2] by NON_MATCH / MATCH / UNKNOWN: bin b in 0..T holds the
+    pairs whose score is above exactly b of the thresholds (`>`), bin T + 1 the pairs with a NULL score.  totals: the
+    labelled (NON_MATCH, MATCH) pairs among all candidate pairs of the job, kept or not -- what fn and tn are taken
+    against; true_pairs_total as the function of that name gives it."""
+
+    def __init__(self, counts, thresholds, totals, link_type="dedupe_only", true_pairs_total=0):
+        self.thresholds = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        T = len(self.thresholds)
+        if np.isnan(self.thresholds).any() or (self.thresholds[1:] < self.thresholds[:-1]).any():
+            raise ValueError("ScoreLabelCounts: the thresholds must be ascending and not NaN")
+        self.counts = np.ascontiguousarray(counts, dtype=np.int64)
+        if self.counts.shape != (3, T + 2):
+            raise ValueError(f"ScoreLabelCounts: counts must be [3, {T + 2}] for {T} thresholds")
+        self.totals = (int(totals[NON_MATCH]), int(totals[MATCH]))
+        self.link_type = link_type
+        self.true_pairs_total = int(true_pairs_total)
+
+    def _rows(self, t, above) -> pd.DataFrame:
+        tp, fp, unl = above[MATCH], above[NON_MATCH], above[UNKNOWN]
+        fn = self.totals[MATCH] - tp
+        tn = self.totals[NON_MATCH] - fp
+        return pd.DataFrame({
+            "threshold": t, "tp": tp, "fp": fp, "tn": tn, "fn": fn, "n_unlabelled_above": unl,
+            "precision": _ratio(tp, tp + fp), "recall": _ratio(tp, tp + fn), "fpr": _ratio(fp, fp + tn),
+            "f1": _ratio(2 * tp, 2 * tp + fp + fn),
+            "recall_of_all_true_pairs": _ratio(tp, np.full(len(t), self.true_pairs_total, dtype=np.int64)),
+        }, columns=list(SCORE_TRUTH_COLUMNS))
+
+    def truth_table(self) -> pd.DataFrame:
+        """LabelCounts.truth_table's columns, one row per threshold: row k predicts the pairs of the bins above k
+        (score > thresholds[k]); a NULL score is never predicted a match."""
+        T = len(self.thresholds)
+        # suffix[:, k] = pairs of each state in bins k + 1 .. T
+        suffix = np.cumsum(self.counts[:, T:0:-1], axis=1)[:, ::-1] if T else np.zeros((3, 0), dtype=np.int64)
+        return self._rows(self.thresholds.copy(), suffix)
+
+    def kept_row(self) -> pd.DataFrame:
+        """One row with threshold = -inf that predicts every counted pair, NULL scores included: a filtered or
+        best-match frame as it stands."""
+        return self._rows(np.array([-np.inf]), self.counts.sum(axis=1).reshape(3, 1))
 
 
 def estimate_from_labels(df_gammas: object, params, settings: dict, spark: object, label_column: str):

@@ -37,8 +37,8 @@ def _bayes_pair(a, b):
 
 class TermFrequencyFrame(SplinkDataFrame):
     """The tf stage's frame.  The per-value adjustment tables are computed when it is made; the per-pair part
-    (spk_tf_apply*) runs on the first toPandas(), and filter() / clusters() never run it: they select on the device
-    (spk_select_tf*) and copy the survivors only."""
+    (spk_tf_apply*) runs on the first toPandas(), and filter() / clusters() / truth_table() never run it: they select
+    (spk_select_tf*) or count (spk_label_scores_tf*) on the device and copy the survivors or the counts only."""
 
     def __init__(self, df_e: ExpectationFrame, settings, tf_cols, tables, one_minus, retain_adjustment_columns,
                  dev_cols=None, host_ids=None):
@@ -117,6 +117,30 @@ class TermFrequencyFrame(SplinkDataFrame):
         f = (TfFilteredFrame(self, Predicate()) if threshold is None
              else self.filter(f"tf_adjusted_match_prob > {threshold!r}"))
         return f.best_matches(per=per, ties=ties)
+
+    def truth_table(self, label_column, thresholds=None):
+        """The confusion matrix of `tf_adjusted_match_prob > threshold` against the labels in the input column
+        `label_column`, with df_e.truth_table's columns: the score is decided per pair on the device
+        (spk_label_scores_tf*), the per-pair part of this frame never runs and no pair leaves the device.
+        thresholds=None: the thresholds of df_e.truth_table(label_column), so the two tables line up row for row."""
+        from .frames import _label_ids, _score_label_counts, _score_thresholds
+        job, df_e = self.job, self.df_e
+        if getattr(job, "passthrough", None) is not None:
+            raise ValueError("truth_table() needs the records: a job made from a gamma table has pairs without rows")
+        lab0, lab1 = _label_ids(job, label_column)  # a missing column fails before the device is touched
+        if thresholds is None:
+            thresholds = df_e.truth_table(label_column)["threshold"].to_numpy()
+        t = _score_thresholds(thresholds, "truth_table")
+        df_e.gammas.ensure_codes()
+        m, u = job.flat_tables(df_e.level_probs)
+        lam = float(df_e.lam)
+        if self.dev_cols is not None:
+            counts = job.ctx.label_scores_tf_columns(lab0, lab1, lam, float(1 - df_e.lam), m, u, self.dev_cols,
+                                                     self.tables, t)
+        else:
+            ids0, ids1 = self.host_ids
+            counts = job.ctx.label_scores_tf(lab0, lab1, lam, float(1 - df_e.lam), m, u, ids0, ids1, self.tables, t)
+        return _score_label_counts(job, counts, None, t, lab0, lab1).truth_table()
 
 
 class TfFilteredFrame(FilteredFrame):
