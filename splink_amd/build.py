@@ -10,10 +10,10 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["spk_ctx.hip", "spk_block.hip", "spk_gamma.hip", "spk_filter.hip", "spk_em.hip", "spk_tf.hip", "spk_ingest.hip",
-           "spk_select.hip", "spk_components.hip", "spk_bridges.hip", "spk_best.hip", "spk_labels.hip", "spk_sample.hip",
-           "spk_agreement.hip"]
-HEADERS = ["spk_internal.h", "spk_prim.h", "spk_strsim.h", "spk_gamma.h", "spk_tf_pair.h"]
+SOURCES = ["spk_ctx.hip", "spk_block.hip", "spk_gamma.hip", "spk_filter.hip", "spk_exact.hip", "spk_udf.hip", "spk_em.hip",
+           "spk_tf.hip", "spk_ingest.hip", "spk_select.hip", "spk_components.hip", "spk_bridges.hip", "spk_best.hip",
+           "spk_labels.hip", "spk_sample.hip", "spk_agreement.hip"]
+HEADERS = ["spk_internal.h", "spk_prim.h", "spk_strsim.h", "spk_gamma.h", "spk_interp.h", "spk_tf_pair.h"]
 OUT = os.path.join(HERE, "libsplink_hip.so")
 OBJ = os.path.join(HERE, "build")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",

@@ -1,5 +1,7 @@
-// Shared definitions of the comparison-vector passes (spk_gamma.hip: interpreter, exact / slow / huge
-// passes, host orchestration; spk_filter.hip: the template-column filter pass).
+// Shared definitions of the comparison-vector passes and the interfaces between their units: spk_gamma.hip
+// (planner, windows, settlement, the interpreter's filter kernel), spk_filter.hip (the template-column filter
+// pass), spk_exact.hip (everything that runs over the work lists: exact / slow / huge passes) and spk_interp.h
+// (the RPN interpreter's device functions).
 #pragma once
 
 #include <vector>
@@ -142,10 +144,6 @@ struct GammaArgs {
 // Codes are written in place: the filter pass sets each pair's code (a 2-byte store leaves the
 // neighbouring pair's code alone), the exact / slow passes of column k add to it (a pair occurs at
 // most once in column k's lists).
-__device__ inline void code_set(const GammaArgs &A, int64_t p, uint32_t v) {
-    if (A.code16) static_cast<uint16_t *>(A.codes)[p] = (uint16_t)v;
-    else static_cast<uint32_t *>(A.codes)[p] = v;
-}
 // The exact and slow passes add their column's digit to the code the filter set.  Launches of one
 // column run in stream order and a pair occurs once in a column's lists: a plain read-modify-write
 // (an atomic add measured 2.4x the HBM writes of the Levenshtein pass at the same kernel time,
@@ -301,31 +299,6 @@ __device__ inline double bits_to_double(uint32_t lo, uint32_t hi) {
     return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 
-// Append the lanes' wanted values of FP ballots to a list: one LDS atomic per call.  The wave must be
-// converged (lane 0 active).
-template <int FP>
-__device__ inline void wave_append_batch(int32_t *list, unsigned int *count, const bool (&want)[FP],
-                                         const int64_t (&val)[FP]) {
-    unsigned long long m[FP];
-    unsigned int total = 0;
-#pragma unroll
-    for (int u = 0; u < FP; ++u) {
-        m[u] = __ballot(want[u]);
-        total += (unsigned int)__popcll(m[u]);
-    }
-    if (!total) return;
-    const int lane = threadIdx.x & 63;
-    unsigned int base = 0;
-    if (lane == 0) base = atomicAdd(count, total);
-    base = __shfl(base, 0);
-    const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int u = 0; u < FP; ++u) {
-        if (want[u]) list[base + __popcll(m[u] & below)] = (int32_t)val[u];
-        base += (unsigned int)__popcll(m[u]);
-    }
-}
-
 // ---- template-column filter pass (spk_filter.hip) -------------------------------------------------
 // Filter regions [region_lo, region_hi) of A's pair range over the simple columns (every one of class
 // SC_EQ / SC_JW / SC_LEV / SC_NUM, laid out in A's row image), `shm` bytes of LDS for the threshold
@@ -334,5 +307,50 @@ int launch_template_filter(hipStream_t stream, const GammaArgs &A, const std::ve
                            int64_t region_lo, int64_t region_hi);
 // Columns of each class the filter kernel handles (more go to the interpreter).
 constexpr int FJ_MAX = 4, FL_MAX = 3, FE_MAX = 6, FN_MAX = 4;
+
+// ---- exact phase (spk_exact.hip) -------------------------------------------------------------------
+// Up to four columns per launch (blockIdx.y picks the column): the JW template columns' lists are
+// compacted, their slow lists evaluated, in one launch each instead of one per column.
+struct ColSet {
+    int n;
+    int k[4];
+};
+
+// What the exact / slow / huge passes of the last spk_gammas need, kept so that an overflow of the work
+// lists or cells past SLOW_LIMIT can be settled after the call returned (settle_gammas): the column decisions
+// once per call (spk_ctx::gcols), and in each window's slot its arguments and what its settlement read.
+struct GammaCols {
+    std::vector<SimpleCol> simple;
+    std::vector<int> simple_of;
+    std::vector<char> may_exact, huge_in_slow, free_text, bag;
+    int K = 0, n_info = 0, n_cnt = 0, n_all = 0;
+    int64_t max_units = 1;
+};
+struct GammaPlan {
+    GammaArgs A{};                   // the window as a pair set of its own
+    int n_regions = 0;
+    int64_t g_exact = 1;
+    int64_t first = 0;               // its first pair ordinal
+    std::vector<char> slow_skipped;  // columns whose slow-list kernels the window did not launch
+    // read by its settlement, per column: start of the exact list in xlist, exact-pass cells, slow list not empty
+    std::vector<int64_t> xbase, exact;
+    std::vector<uint8_t> slow_seen;
+    int64_t deferred = 0;            // its slow-list cells
+};
+using Slot = spk_ctx::Slot;
+// The exact and slow passes of the window in S over the lists its filter wrote, list capacity `cap`.  k_prefix
+// sizes the lists on the device; if they exceed `cap` every exact kernel is a no-op and settle_gammas runs the
+// phase again with room.  skip: leave out the slow-list kernels of columns whose slow lists were empty in the
+// last settled call (GammaPlan.slow_skipped says which).
+int enqueue_phase(spk_ctx *ctx, Slot &S, int64_t cap, bool skip = false);
+// The slow-list kernels of column k, or of the fused JW columns jk: the cells the exact pass left.
+int enqueue_slow(spk_ctx *ctx, Slot &S, int k, const ColSet *jk);
+// The huge pass of the settled window in S, n_huge[k] listed cells in column k, and a wait for it.
+int run_huge(spk_ctx *ctx, Slot &S, const unsigned int *n_huge);
+// Device scratch of a huge pass over `cells` cells whose strings have at most `units` UTF-16 units.
+int huge_scratch(int64_t units, int64_t cells, DevBuf<uint8_t> &buf, Scratch &S);
+
+// UTF-8 to UTF-16 units on the host (program literals, the bulk UDFs' strings); *ncp = code points.
+std::vector<uint16_t> utf8_to_utf16(const uint8_t *b, int64_t n, int32_t *ncp);
 
 }  // namespace spk

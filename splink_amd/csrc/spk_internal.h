@@ -351,8 +351,8 @@ struct ComponentSweep {
     void clear() { *this = ComponentSweep(); }
 };
 
-struct GammaCols;  // spk_gamma.hip: a call's column decisions
-struct GammaPlan;  // spk_gamma.hip: one window's plan
+struct GammaCols;  // spk_gamma.h: a call's column decisions
+struct GammaPlan;  // spk_gamma.h: one window's plan
 enum Kern { K_BLOCK = 0, K_GAMMA = 1, K_EMHIST = 2, K_EMFIN = 3, K_SCORE = 4, K_COUNT = 5 };
 
 }  // namespace spk

@@ -477,7 +477,7 @@ def rule_as_case(rule):
 
 
 # ---------------------------------------------------------------------------------------------------------
-# emulator of a CompiledComparisons (the semantics of spk_gamma.hip eval_pred / eval_column)
+# emulator of a CompiledComparisons (the semantics of spk_interp.h eval_pred / eval_column)
 # ---------------------------------------------------------------------------------------------------------
 OPNAME = {v: k for k, v in N.OP.items()}
 CMPNAME = {0: "=", 1: "!=", 2: "<", 3: "<=", 4: ">", 5: ">="}

@@ -1,5 +1,5 @@
 """Host restatement of the character-bag lower bound that k_bag_rows / k_compact_lev (spk_ctx.hip,
-spk_gamma.hip) use to decide free-text Levenshtein cells before the exact pass: 60 buckets ('a'-'z', 'A'-'Z',
+spk_exact.hip) use to decide free-text Levenshtein cells before the exact pass: 60 buckets ('a'-'z', 'A'-'Z',
 digits mod 8) in 4-bit saturating counts, the count of other units and the length (255: no bag), the bound
 max(la, lb) - (Σ min over buckets + min(other_a, other_b)), skipped when a bucket saturates on both sides.
 Property checked against the oracle's Levenshtein (the reference's levenshtein over code points): the bound

@@ -27,8 +27,19 @@ def _launched(*files):
     return names
 
 
+def _gamma_sources():
+    """The units of build.SOURCES that include spk_gamma.h: the comparison pass and what shares its definitions."""
+    from splink_amd import build
+    out = []
+    for f in build.SOURCES:
+        with open(os.path.join(ROOT, "splink_amd", "csrc", f)) as fh:
+            if '#include "spk_gamma.h"' in fh.read():
+                out.append(f)
+    return out
+
+
 def test_gamma_group_covers_every_gamma_launch():
-    launched = _launched("spk_gamma.hip", "spk_filter.hip")
+    launched = _launched(*_gamma_sources())
     assert "k_filter" in launched
     unknown = launched - set(traffic.GAMMA_KERNELS) - set(traffic.NOT_GAMMA_KERNELS)
     assert not unknown, f"kernels launched by the γ sources but in neither traffic.py list: {unknown}"
@@ -39,6 +50,13 @@ def test_gamma_group_covers_every_gamma_launch():
     # kernels of other entry points never count as γ traffic
     for k in ("k_em_iter<unsigned short, 64, true>", "k_score<unsigned short, true>", "k_hist_lanes", "k_enum<true>"):
         assert not traffic.GAMMA.search(f"void spk::{k}(a)"), k
+
+
+def test_build_lists_every_source_and_header():
+    from splink_amd import build
+    csrc = os.listdir(os.path.join(ROOT, "splink_amd", "csrc"))
+    assert sorted(f for f in csrc if f.endswith(".hip")) == sorted(build.SOURCES)
+    assert {f for f in csrc if f.endswith(".h")} <= set(build.HEADERS)
 
 
 def _bench_traffic_file():

@@ -1,6 +1,6 @@
 """Per-workgroup timeline of the JW exact launch (diagnostic build):
 
-    python tools/build_ab.py splink_amd/ab_xstamps.so spk_gamma.hip -DSPK_X_STAMPS
+    python tools/build_ab.py splink_amd/ab_xstamps.so spk_exact.hip -DSPK_X_STAMPS
     SPLINK_AMD_LIB=splink_amd/ab_xstamps.so python tools/ab_x_stamps.py
 
 Prints when the workgroups start (dispatch timeline), how long working and empty ones live, and the

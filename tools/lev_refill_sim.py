@@ -1,4 +1,4 @@
-"""Host simulation behind k_lev_refill (spk_gamma.hip): scan steps per Levenshtein exact-pass cell and the lane
+"""Host simulation behind k_lev_refill (spk_exact.hip): scan steps per Levenshtein exact-pass cell and the lane
 utilisation of one-cell-per-lane waves vs lane-refill waves.
 
 Cells are drawn like the exact pass's lists: pairs that share a blocking key (cfg5: surname, addresses of
