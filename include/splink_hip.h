@@ -798,6 +798,45 @@ int spk_label_histogram(spk_ctx *ctx, const int64_t *ids_side0, const int64_t *i
  * the histogram; the uploads and read-backs are not in it), -1 otherwise. */
 int spk_label_info(spk_ctx *ctx, int64_t *out_pairs, double *out_ms);
 
+/* ---- pairs against a table of labelled pairs (later releases: truth_space_table_from_labels_table,
+ *      prediction_errors_from_labels_table, estimate_m_from_pairwise_labels; replaces taking every scored pair to the
+ *      host and merging it with the labels there) ---- */
+/* spk_label_histogram's counts with the truth state of a candidate pair looked up in a set of n_labels labelled pairs,
+ * e.g. a clerical-review sample: MATCH and NON_MATCH hold the labelled candidate pairs, UNKNOWN the candidate pairs
+ * without a label, and the three rows sum to spk_em_histogram bin for bin.  rows_l / rows_r are device rows (as
+ * spk_pairs_copy gives them), is_match is 0 or 1.  n_labels = 0 is legal: every pair is UNKNOWN.
+ * The set is a hash table built on the device for the call:
+ *   - open addressing with linear probing (slot + 1, wrapping), one 64-bit word per slot, an empty slot all ones;
+ *   - capacity = the smallest power of two >= 2 * n_labels, and at least 64;
+ *   - key = lo << 31 | hi (rows are non-negative int32: 62 bits); bit 62 of the word is the label, 1 = match;
+ *   - orientation: under link_only (lo, hi) = (left-table row, right-table row) as given; otherwise both rows index
+ *     table 0 and (lo, hi) = (min, max).  The rule holds for a label and for a candidate pair alike, so the order
+ *     in which a labelled pair is given does not matter;
+ *   - home slot = fmix64(key) & (capacity - 1), fmix64 = MurmurHash3's 64-bit finaliser
+ *     (k ^= k >> 33; k *= 0xff51afd7ed558ccd; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53; k ^= k >> 33).
+ * out_label_code[i] (optional) is the packed code of the candidate pair that label i names, -1 when blocking did not
+ * produce it; if a hand-loaded pair set repeats that pair, the largest of its codes.  out_pattern_mp as for
+ * spk_label_histogram (the same device function as spk_score, bit for bit; NULL without m / u).
+ * SPK_E_INVALID: NULL rows_l / rows_r / is_match with n_labels > 0; NULL out_counts; out_pattern_mp without m / u; an
+ * is_match other than 0 / 1; a row outside its table; l == r on a one-table job; a pair given twice (in either order
+ * on a one-table job) -- the last four are found on the device before any pair is counted.  SPK_E_STATE: no
+ * comparison codes; no pair rows (a loaded gamma table); a candidate pair that names a row outside its table or a
+ * code outside the pattern space (it is not counted).  SPK_E_LIMIT: more than 2^27 labels; 3 * n_patterns > 2^30.
+ * Reads the pairs and the codes only: no selection, score, tf, EM or component state is touched, and every device
+ * buffer of the call is freed before it returns. */
+int spk_label_pairs_histogram(spk_ctx *ctx, int64_t n_labels,
+                              const int32_t *rows_l, const int32_t *rows_r /* host, device row order */,
+                              const uint8_t *is_match                      /* host, 0 / 1 */,
+                              double lambda, double one_minus, const double *m, const double *u,
+                              uint64_t *out_counts     /* host [SPK_LABEL_STATES x n_patterns], state-major */,
+                              double   *out_pattern_mp /* host [n_patterns] or NULL */,
+                              int32_t  *out_label_code /* host [n_labels] or NULL */);
+/* The last spk_label_pairs_histogram: pairs counted; with timing on the device milliseconds of its launches (table
+ * clear, build, pattern table, counter clear and the histogram; the uploads and read-backs are not in it), -1.0
+ * otherwise; the table's capacity in slots; the longest insert probe (slots an insert looked at, its home slot
+ * included; 0 without labels).  -1 / -1.0 / -1 / -1: none yet, or the last call failed. */
+int spk_label_pairs_info(spk_ctx *ctx, int64_t *out_pairs, double *out_ms, int64_t *out_capacity, int *out_max_probe);
+
 /* ---- scores against labels, per pair (replaces taking the frame make_adjustment_for_term_frequencies returns, or a
  *      filtered frame, to the host with the label column retained and counting the confusion matrix there) ---- */
 #define SPK_LABEL_SCORE_MAX_THRESHOLDS 1024

@@ -89,6 +89,7 @@ EXPORTS = [
     "spk_cluster_metrics_set_mode",
     "spk_cluster_bridges", "spk_cluster_bridges_copy", "spk_cluster_bridges_cores_copy", "spk_cluster_bridges_info",
     "spk_label_histogram", "spk_label_info",
+    "spk_label_pairs_histogram", "spk_label_pairs_info",
     "spk_label_scores_tf", "spk_label_scores_tf_columns", "spk_label_scores_selection", "spk_label_scores_info",
     "spk_cluster_agreement", "spk_cluster_agreement_info",
     "spk_pairs_sample", "spk_pairs_sample_info",
@@ -111,6 +112,7 @@ LABEL_NON_MATCH, LABEL_MATCH, LABEL_UNKNOWN, LABEL_STATES = 0, 1, 2, 3  # SPK_LA
 # lds_per_block()); past it the counts go to global memory.  Mirrored from LH_LDS_BYTES in csrc/spk_labels.hip;
 # only the tests' choice of pattern spaces depends on it.
 LABEL_LDS_BYTES = 64 * 1024
+LABEL_PAIRS_MAX = 1 << 27  # labelled pairs one spk_label_pairs_histogram takes
 LABEL_SCORE_MAX_THRESHOLDS = 1024  # SPK_LABEL_SCORE_MAX_THRESHOLDS
 # Pairs one workgroup of spk_label_scores_tf*'s kernel takes per step (256 threads x 8 pairs) and the workgroups per
 # compute unit its grid is capped at.  Mirrored from LS_THREADS, LS_PAIRS and LS_WG_PER_CU in csrc/spk_labels.hip; only
@@ -1061,6 +1063,44 @@ class Context:
         ms = ctypes.c_double(-1.0)
         check(self._lib.spk_label_info(self._h, ctypes.byref(n), ctypes.byref(ms)), "spk_label_info")
         return n.value, ms.value
+
+    # ---- pairs against a table of labelled pairs -----------------------------------------------
+    def label_pairs_histogram(self, rows_l, rows_r, is_match, lam=None, one_minus=None, m=None, u=None):
+        """spk_label_pairs_histogram: (counts int64 [3, n_patterns] by LABEL_NON_MATCH / LABEL_MATCH / LABEL_UNKNOWN,
+        match_probability per pattern or None without m / u, label_code int32 [n_labels]: the packed code of the
+        candidate pair each label names, -1 = not among them).  rows_l / rows_r: device rows of the labelled pairs
+        (in either order unless the job is link_only), is_match: 0 / 1."""
+        rows_l = np.ascontiguousarray(rows_l, dtype=np.int32).reshape(-1)
+        rows_r = np.ascontiguousarray(rows_r, dtype=np.int32).reshape(-1)
+        is_match = np.ascontiguousarray(is_match, dtype=np.uint8).reshape(-1)
+        if not len(rows_l) == len(rows_r) == len(is_match):
+            raise ValueError("label_pairs_histogram: rows_l, rows_r and is_match differ in length")
+        if (m is None) != (u is None):
+            raise ValueError("label_pairs_histogram: m and u come together")
+        scored = m is not None
+        m = np.ascontiguousarray(m, dtype=np.float64) if scored else None
+        u = np.ascontiguousarray(u, dtype=np.float64) if scored else None
+        n, n_pat = len(rows_l), self.n_patterns()
+        counts = np.zeros((LABEL_STATES, max(n_pat, 1)), dtype=np.uint64)
+        mp = np.empty(max(n_pat, 1), dtype=np.float64) if scored else None
+        code = np.full(max(n, 1), -1, dtype=np.int32)
+        check(self._lib.spk_label_pairs_histogram(self._h, ctypes.c_int64(n), _ptr(rows_l if n else None),
+                                                  _ptr(rows_r if n else None), _ptr(is_match if n else None),
+                                                  ctypes.c_double(float(lam) if scored else 0.0),
+                                                  ctypes.c_double(float(one_minus) if scored else 0.0), _ptr(m),
+                                                  _ptr(u), _ptr(counts), _ptr(mp), _ptr(code)),
+              "spk_label_pairs_histogram")
+        return counts[:, :n_pat].astype(np.int64), (mp[:n_pat] if scored else None), code[:n]
+
+    def label_pairs_info(self):
+        """(pairs the last label_pairs_histogram counted, ms of its launches with timing on, slots of its hash table,
+        its longest insert probe); (-1, -1.0, -1, -1): none yet, or the last call failed."""
+        n, cap = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        ms = ctypes.c_double(-1.0)
+        probe = ctypes.c_int(-1)
+        check(self._lib.spk_label_pairs_info(self._h, ctypes.byref(n), ctypes.byref(ms), ctypes.byref(cap),
+                                             ctypes.byref(probe)), "spk_label_pairs_info")
+        return n.value, ms.value, cap.value, probe.value
 
     # ---- scores against labels, per pair ------------------------------------------------------
     @staticmethod

@@ -532,6 +532,11 @@ struct spk_ctx {
     // the last spk_label_scores_* (spk_labels.hip): the same two numbers; its buffers live for the call only
     int64_t score_pairs = -1;
     double score_ms = -1.0;
+    // the last spk_label_pairs_histogram (spk_labels.hip): pairs counted and device milliseconds as above, the slots of
+    // its hash table and the longest insert probe (all -1: none, or it failed); its buffers live for the call only
+    int64_t lpairs_pairs = -1, lpairs_capacity = -1;
+    double lpairs_ms = -1.0;
+    int lpairs_max_probe = -1;
     // the last spk_cluster_agreement (spk_agreement.hip): levels it scored (-1: none yet), device milliseconds of its
     // launches; a failing call leaves both as they were, and its buffers live for the call only
     int agree_levels = -1;

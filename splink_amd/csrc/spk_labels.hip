@@ -163,9 +163,9 @@ __global__ __launch_bounds__(LH_THREADS) void k_label_hist(LabelArgs A, const Co
 
 // Workgroups of the launch: enough for LH_WG_PER_CU per CU, never more than the steps there are, and never so few
 // that one workgroup would count more than LH_BLOCK_PAIRS_MAX pairs (its LDS counters are 32-bit).
-static unsigned label_grid(const spk_ctx *ctx, int64_t P) {
+static unsigned label_grid(const spk_ctx *ctx, int64_t P, int wg_per_cu = LH_WG_PER_CU) {
     const int64_t steps = (P / LH_PAIRS + LH_THREADS - 1) / LH_THREADS;
-    int64_t g = std::min<int64_t>(steps, LH_WG_PER_CU * (int64_t)ctx->n_cu);
+    int64_t g = std::min<int64_t>(steps, wg_per_cu * (int64_t)ctx->n_cu);
     g = std::max<int64_t>(g, (P + LH_BLOCK_PAIRS_MAX - 1) / LH_BLOCK_PAIRS_MAX);
     return (unsigned)std::max<int64_t>(g, 1);
 }
@@ -531,6 +531,215 @@ static int scores_tf_run(ScoreCall &C, TfStage &G, const int64_t *label_ids0, co
     return C.finish(P, out_counts);
 }
 
+// ---- pairs against a table of labelled pairs -----------------------------------------------------------------
+// spk_label_pairs_histogram: k_label_hist's counting with the truth state of a pair looked up in a set of labelled
+// pairs (a clerical-review sample) instead of gathered from two per-record ids.  The set is a hash table built on the
+// device for the call -- open addressing, linear probing, one 64-bit word per slot; key layout, hash and capacity
+// rule: include/splink_hip.h -- and probed once per candidate pair.  At 8 bytes per slot and a load of at most 0.5 the
+// table of 10^5 labels is 2 MiB (L2 resident), that of 10^7 labels 256 MiB (past the Infinity Cache: every probe of
+// it is an HBM gather).  An unlabelled pair, the common case, ends at the first empty slot: 2.5 slots expected at
+// load 0.5, mostly in its home slot's 64-byte line.  cfg2 (46 M pairs, LDS variant), device ms of the call at 10^3 /
+// 10^5 / 10^7 labels: 0.62 / 0.53 / 3.27, next to 0.19 for spk_label_histogram (profiles/ab_label_pairs.log).
+constexpr unsigned long long LP_EMPTY = ~0ull;
+constexpr unsigned long long LP_MATCH_BIT = 1ull << 62;
+constexpr int LP_BUILD_THREADS = 256;
+// Workgroups per CU of the histogram's grid, and the waves per SIMD its registers are held to (80 VGPRs: the keys,
+// home slots and words of 8 pairs are live together): 3 workgroups of 8 waves are resident per CU, so every workgroup
+// runs from the first cycle and takes an equal share of the steps (LS_WG_PER_CU's reasoning).
+constexpr int LP_WG_PER_CU = 3;
+constexpr int LP_WAVES_PER_SIMD = 6;
+constexpr int64_t LP_MAX_LABELS = (int64_t)1 << 27;
+// bits of the call's `bad` word.  The build's are SPK_E_INVALID, read before any pair is counted; the histogram's are
+// SPK_E_STATE (the pair is not counted).
+constexpr unsigned LP_BAD_ROW = 1u;     // a label names a row outside its table
+constexpr unsigned LP_BAD_SELF = 2u;    // a label pairs a record with itself (one-table jobs)
+constexpr unsigned LP_BAD_TWICE = 4u;   // a labelled pair given twice
+constexpr unsigned LP_BAD_FLAG = 8u;    // is_match other than 0 / 1
+constexpr unsigned LP_BAD_FULL = 16u;   // build: no free slot (cannot happen at load <= 0.5)
+constexpr unsigned LP_BAD_PAIR = 32u;   // histogram: a pair names a row or a code out of range
+constexpr unsigned LP_BAD_TABLE = 64u;  // histogram: a walk read every slot, or a slot names no label: a damaged table
+
+struct PairTable {
+    unsigned long long *slot;  // [mask + 1]: LP_EMPTY, or key | LP_MATCH_BIT if the pair is a match
+    uint32_t *index;           // [mask + 1]: the label a full slot came from; read only on a hit
+    uint32_t mask;             // capacity - 1
+    uint32_t n_labels;
+    bool ordered;              // link_only: (left row, right row) as given; otherwise (min, max)
+};
+
+// MurmurHash3's 64-bit finaliser
+__device__ __forceinline__ uint64_t lp_fmix64(uint64_t k) {
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33;
+    k *= 0xc4ceb9fe1a85ec53ull;
+    k ^= k >> 33;
+    return k;
+}
+
+// the canonical key of a pair of rows, both below 2^31
+__device__ __forceinline__ uint64_t lp_key(const PairTable &T, uint32_t l, uint32_t r) {
+    const uint32_t lo = T.ordered ? l : min(l, r), hi = T.ordered ? r : max(l, r);
+    return (uint64_t)lo << 31 | hi;
+}
+
+// One label per thread into a table of LP_EMPTY slots.  flags[0]: the bad bits, flags[1]: the longest probe (slots an
+// insert looked at, its home slot included).
+__global__ __launch_bounds__(LP_BUILD_THREADS) void k_label_pairs_build(int64_t n, const int32_t *__restrict__ rows_l,
+                                                                        const int32_t *__restrict__ rows_r,
+                                                                        const uint8_t *__restrict__ is_match,
+                                                                        uint32_t n0, uint32_t n1, PairTable T,
+                                                                        unsigned int *__restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * LP_BUILD_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t l = (uint32_t)rows_l[i], r = (uint32_t)rows_r[i], match = is_match[i];
+    unsigned bad = 0u;
+    if (l >= n0 || r >= n1) bad |= LP_BAD_ROW;
+    else if (!T.ordered && l == r) bad |= LP_BAD_SELF;
+    if (match > 1u) bad |= LP_BAD_FLAG;
+    if (bad) {
+        atomicOr(&flags[0], bad);
+        return;
+    }
+    const uint64_t key = lp_key(T, l, r);
+    const unsigned long long word = key | (match ? LP_MATCH_BIT : 0ull);
+    uint32_t h = (uint32_t)lp_fmix64(key) & T.mask;
+    for (uint32_t probe = 1;; ++probe) {
+        const unsigned long long old = atomicCAS(&T.slot[h], LP_EMPTY, word);
+        if (old == LP_EMPTY) {
+            T.index[h] = (uint32_t)i;
+            atomicMax(&flags[1], probe);
+            return;
+        }
+        if ((old & ~LP_MATCH_BIT) == key) {
+            atomicOr(&flags[0], LP_BAD_TWICE);
+            return;
+        }
+        if (probe > T.mask) {  // every slot seen
+            atomicOr(&flags[0], LP_BAD_FULL);
+            return;
+        }
+        h = (h + 1u) & T.mask;
+    }
+}
+
+struct PairLabelArgs {
+    int64_t P;
+    const int32_t *pl, *pr;
+    PairTable T;
+    uint32_t n0, n1;            // row counts of the pairs' left / right table
+    uint32_t n_pat;
+    int32_t *label_code;        // [n_labels], -1 before the launch: the largest code of a pair that hit the label; or null
+    unsigned long long *ghist;  // [3 x n_pat], zeroed before the launch
+    unsigned int *bad;
+};
+
+// The walk of one pair from its home slot h, whose word w is loaded already: the pair's bin, or in = false when the
+// table is damaged.  At most capacity slots are read, so no wave can spin.
+__device__ __forceinline__ uint32_t lp_bin(const PairLabelArgs &A, uint64_t key, uint32_t h, unsigned long long w,
+                                           uint32_t c, bool &in) {
+    if (!in) return 0xFFFFFFFFu;
+    uint32_t state = (uint32_t)SPK_LABEL_UNKNOWN;
+    for (uint32_t left = A.T.mask; w != LP_EMPTY; --left) {  // left: slots the walk may still move on to
+        if ((w & ~LP_MATCH_BIT) == key) {
+            const uint32_t at = A.T.index[h];
+            if (at >= A.T.n_labels) break;  // a slot that names no label
+            state = (uint32_t)((w >> 62) & 1ull);
+            if (A.label_code) atomicMax(&A.label_code[at], (int32_t)c);
+            return state * A.n_pat + c;
+        }
+        if (left == 0u) break;  // every slot read
+        h = (h + 1u) & A.T.mask;
+        w = A.T.slot[h];
+    }
+    if (w == LP_EMPTY) return state * A.n_pat + c;  // no label: the loop ended, it was not left by a break
+    atomicOr(A.bad, LP_BAD_TABLE);
+    in = false;
+    return 0xFFFFFFFFu;
+}
+
+// k_label_hist with the two label gathers replaced by the probe: the same 8 pairs per lane and step, the same tail
+// wave, label_add and LDS flush.  Per step a lane first issues the home-slot loads of all its pairs, so that they are in
+// flight together as k_label_hist's gathers are, and only then walks on where a home slot held another key.
+template <typename CodeT, bool LDS>
+__global__ __launch_bounds__(LH_THREADS, LP_WAVES_PER_SIMD) void k_label_pairs_hist(PairLabelArgs A,
+                                                                                   const CodeT *__restrict__ codes) {
+    extern __shared__ uint32_t sh[];
+    const int n_bins = 3 * (int)A.n_pat;
+    if (LDS) {
+        for (int b = threadIdx.x; b < n_bins; b += LH_THREADS) sh[b] = 0;
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & 63;
+    const int64_t n_vec = A.P / LH_PAIRS;
+    const uint4 *lv = reinterpret_cast<const uint4 *>(A.pl);
+    const uint4 *rv = reinterpret_cast<const uint4 *>(A.pr);
+    const uint4 *cv = reinterpret_cast<const uint4 *>(codes);
+    constexpr int CW = LH_PAIRS * (int)sizeof(CodeT) / 16;  // 16-byte code vectors per step: 1 or 2
+    for (int64_t v = (int64_t)blockIdx.x * LH_THREADS + threadIdx.x;; v += (int64_t)gridDim.x * LH_THREADS) {
+        const bool in = v < n_vec;
+        if (!__any(in)) break;  // wave-uniform: every lane stays inside the ballots of label_add
+        uint32_t l[LH_PAIRS], r[LH_PAIRS], c[LH_PAIRS], h[LH_PAIRS], bin[LH_PAIRS];
+        uint64_t key[LH_PAIRS];
+        unsigned long long w[LH_PAIRS];
+        bool ok[LH_PAIRS];
+#pragma unroll
+        for (int j = 0; j < LH_PAIRS; ++j) l[j] = r[j] = c[j] = 0xFFFFFFFFu;
+        if (in) {
+            const uint4 l0 = lv[2 * v], l1 = lv[2 * v + 1], r0 = rv[2 * v], r1 = rv[2 * v + 1];
+            l[0] = l0.x, l[1] = l0.y, l[2] = l0.z, l[3] = l0.w, l[4] = l1.x, l[5] = l1.y, l[6] = l1.z, l[7] = l1.w;
+            r[0] = r0.x, r[1] = r0.y, r[2] = r0.z, r[3] = r0.w, r[4] = r1.x, r[5] = r1.y, r[6] = r1.z, r[7] = r1.w;
+            uint4 x[CW];
+#pragma unroll
+            for (int j = 0; j < CW; ++j) x[j] = cv[CW * v + j];
+            const CodeT *e = reinterpret_cast<const CodeT *>(x);
+#pragma unroll
+            for (int j = 0; j < LH_PAIRS; ++j) c[j] = (uint32_t)e[j];
+        }
+#pragma unroll
+        for (int j = 0; j < LH_PAIRS; ++j) {  // all the home slots first
+            ok[j] = in && l[j] < A.n0 && r[j] < A.n1 && c[j] < A.n_pat;
+            if (in && !ok[j]) atomicOr(A.bad, LP_BAD_PAIR);
+            key[j] = lp_key(A.T, l[j], r[j]);
+            h[j] = (uint32_t)lp_fmix64(key[j]) & A.T.mask;
+            w[j] = ok[j] ? A.T.slot[h[j]] : LP_EMPTY;
+        }
+#pragma unroll
+        for (int j = 0; j < LH_PAIRS; ++j) bin[j] = lp_bin(A, key[j], h[j], w[j], c[j], ok[j]);
+#pragma unroll
+        for (int j = 0; j < LH_PAIRS; ++j) label_add<LDS>(bin[j], ok[j], lane, sh, A.ghist);
+    }
+    // tail (P not a multiple of LH_PAIRS): workgroup 0's first wave, one pair per lane, every lane in the ballots
+    if (blockIdx.x == 0 && threadIdx.x < 64) {
+        const int64_t p = n_vec * LH_PAIRS + lane;
+        const bool in = p < A.P;
+        const uint32_t l = in ? (uint32_t)A.pl[p] : 0u, r = in ? (uint32_t)A.pr[p] : 0u, c = in ? (uint32_t)codes[p] : 0u;
+        bool ok = in && l < A.n0 && r < A.n1 && c < A.n_pat;
+        if (in && !ok) atomicOr(A.bad, LP_BAD_PAIR);
+        const uint64_t key = lp_key(A.T, l, r);
+        const uint32_t h = (uint32_t)lp_fmix64(key) & A.T.mask;
+        const uint32_t bin = lp_bin(A, key, h, ok ? A.T.slot[h] : LP_EMPTY, c, ok);
+        label_add<LDS>(bin, ok, lane, sh, A.ghist);
+    }
+    if (LDS) {
+        __syncthreads();
+        for (int b = threadIdx.x; b < n_bins; b += LH_THREADS) {
+            const uint32_t n = sh[b];
+            if (n) atomicAdd(&A.ghist[b], (unsigned long long)n);
+        }
+    }
+}
+
+template <typename CodeT>
+static int launch_label_pairs_hist(spk_ctx *ctx, const PairLabelArgs &A, bool lds) {
+    const unsigned g = label_grid(ctx, A.P, LP_WG_PER_CU);
+    const CodeT *codes = reinterpret_cast<const CodeT *>(ctx->codes.p);
+    if (lds) k_label_pairs_hist<CodeT, true><<<g, LH_THREADS, (size_t)3 * A.n_pat * 4, ctx->stream>>>(A, codes);
+    else k_label_pairs_hist<CodeT, false><<<g, LH_THREADS, 0, ctx->stream>>>(A, codes);
+    SPK_HIP(hipGetLastError());
+    return SPK_OK;
+}
+
 }  // namespace spk
 
 using namespace spk;
@@ -681,6 +890,129 @@ extern "C" int spk_label_scores_selection(spk_ctx *ctx, const int64_t *label_ids
         SPK_HIP(hipGetLastError());
     }
     return C.finish(n, out_counts);
+}
+
+extern "C" int spk_label_pairs_histogram(spk_ctx *ctx, int64_t n_labels, const int32_t *rows_l, const int32_t *rows_r,
+                                         const uint8_t *is_match, double lambda, double one_minus, const double *m,
+                                         const double *u, uint64_t *out_counts, double *out_pattern_mp,
+                                         int32_t *out_label_code) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_label_pairs_histogram: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    ctx->lpairs_pairs = ctx->lpairs_capacity = -1;
+    ctx->lpairs_ms = -1.0;
+    ctx->lpairs_max_probe = -1;
+    SPK_REQUIRE(n_labels >= 0, SPK_E_INVALID, "spk_label_pairs_histogram: negative n_labels");
+    SPK_REQUIRE(n_labels == 0 || (rows_l && rows_r && is_match), SPK_E_INVALID,
+                "spk_label_pairs_histogram: null rows_l, rows_r or is_match");
+    SPK_REQUIRE(out_counts, SPK_E_INVALID, "spk_label_pairs_histogram: null out_counts");
+    SPK_REQUIRE((m == nullptr) == (u == nullptr), SPK_E_INVALID, "spk_label_pairs_histogram: m and u come together");
+    SPK_REQUIRE(!out_pattern_mp || (m && u), SPK_E_INVALID, "spk_label_pairs_histogram: out_pattern_mp needs m and u");
+    SPK_REQUIRE(ctx->codes_valid, SPK_E_STATE, "spk_label_pairs_histogram: no gammas");
+    SPK_TRY(settle_gammas(ctx, nullptr));
+    SPK_REQUIRE(ctx->codes_valid, SPK_E_STATE, "spk_label_pairs_histogram: no gammas");
+    const int64_t P = ctx->n_pairs, n_pat = ctx->n_patterns;
+    SPK_REQUIRE(ctx->pairs_valid && ctx->pl.p && ctx->pr.p && ctx->pl.n >= (size_t)P && ctx->pr.n >= (size_t)P,
+                SPK_E_STATE, "spk_label_pairs_histogram: no pair rows (a loaded gamma table)");
+    SPK_REQUIRE(n_labels <= LP_MAX_LABELS, SPK_E_LIMIT, "spk_label_pairs_histogram: more than 2^27 labelled pairs");
+    SPK_REQUIRE(n_pat >= 1 && 3 * n_pat <= ((int64_t)1 << 30), SPK_E_LIMIT,
+                "spk_label_pairs_histogram: more than 2^30 (state, pattern) counters");
+    Table &t0 = ctx->table[0], &t1 = ctx->side_table(1);
+    SPK_REQUIRE(t0.n >= 0 && t1.n >= 0, SPK_E_STATE, "spk_label_pairs_histogram: no tables");
+    int64_t capacity = 64;
+    while (capacity < 2 * n_labels) capacity *= 2;
+    // everything below lives for this call only
+    DevBuf<unsigned long long> slot, hist;
+    DevBuf<uint32_t> index;
+    DevBuf<int32_t> d_l, d_r, code;
+    DevBuf<uint8_t> d_match;
+    DevBuf<unsigned int> flags;  // [0] the bad bits, [1] the longest insert probe
+    DevBuf<double> mpat;
+    StageTimer T{ctx};
+    SPK_TRY(slot.alloc((size_t)capacity));
+    SPK_TRY(index.alloc((size_t)capacity));
+    SPK_TRY(hist.alloc((size_t)3 * n_pat));
+    SPK_TRY(flags.alloc(2));
+    if (out_pattern_mp) SPK_TRY(mpat.alloc((size_t)n_pat));
+    hipStream_t st = ctx->stream;
+    PairTable tab{slot.p, index.p, (uint32_t)(capacity - 1), (uint32_t)n_labels, ctx->link_type == SPK_LINK_ONLY};
+    unsigned int h_flags[2] = {0u, 0u};
+    // ---- the table: cleared, then one insert per label; what is wrong with the labels is known before a pair is counted
+    if (n_labels > 0) {
+        SPK_TRY(d_l.alloc((size_t)n_labels));
+        SPK_TRY(d_r.alloc((size_t)n_labels));
+        SPK_TRY(d_match.alloc((size_t)n_labels));
+        if (out_label_code) SPK_TRY(code.alloc((size_t)n_labels));
+        SPK_HIP(hipMemcpyAsync(d_l.p, rows_l, (size_t)n_labels * 4, hipMemcpyHostToDevice, st));
+        SPK_HIP(hipMemcpyAsync(d_r.p, rows_r, (size_t)n_labels * 4, hipMemcpyHostToDevice, st));
+        SPK_HIP(hipMemcpyAsync(d_match.p, is_match, (size_t)n_labels, hipMemcpyHostToDevice, st));
+    }
+    SPK_TRY(T.open());
+    SPK_HIP(hipMemsetAsync(flags.p, 0, 2 * sizeof(unsigned int), st));
+    SPK_HIP(hipMemsetAsync(slot.p, 0xFF, (size_t)capacity * 8, st));
+    if (n_labels > 0) {
+        if (out_label_code) SPK_HIP(hipMemsetAsync(code.p, 0xFF, (size_t)n_labels * 4, st));  // -1
+        k_label_pairs_build<<<(unsigned)((n_labels + LP_BUILD_THREADS - 1) / LP_BUILD_THREADS), LP_BUILD_THREADS, 0,
+                              st>>>(n_labels, d_l.p, d_r.p, d_match.p, (uint32_t)t0.n, (uint32_t)t1.n, tab, flags.p);
+        SPK_HIP(hipGetLastError());
+    }
+    SPK_TRY(T.stop());
+    SPK_HIP(hipMemcpyAsync(h_flags, flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, st));
+    SPK_HIP(hipStreamSynchronize(st));
+    SPK_TRY(T.add());
+    SPK_REQUIRE(!(h_flags[0] & LP_BAD_FLAG), SPK_E_INVALID, "spk_label_pairs_histogram: an is_match other than 0 or 1");
+    SPK_REQUIRE(!(h_flags[0] & LP_BAD_ROW), SPK_E_INVALID,
+                "spk_label_pairs_histogram: a labelled pair names a row outside its table");
+    SPK_REQUIRE(!(h_flags[0] & LP_BAD_SELF), SPK_E_INVALID,
+                "spk_label_pairs_histogram: a labelled pair of a record with itself");
+    SPK_REQUIRE(!(h_flags[0] & LP_BAD_TWICE), SPK_E_INVALID, "spk_label_pairs_histogram: a labelled pair given twice");
+    SPK_REQUIRE(h_flags[0] == 0u, SPK_E_STATE, "spk_label_pairs_histogram: the pair table is full");
+    // ---- mp per pattern (spk_score's own kernel and arguments) and the counts
+    SPK_TRY(T.open());
+    if (out_pattern_mp) SPK_TRY(pattern_mp_table(ctx, lambda, one_minus, m, u, mpat.p));
+    SPK_HIP(hipMemsetAsync(hist.p, 0, (size_t)3 * n_pat * 8, st));
+    if (P > 0) {
+        PairLabelArgs A{};
+        A.P = P;
+        A.pl = ctx->pl.p;
+        A.pr = ctx->pr.p;
+        A.T = tab;
+        A.n0 = (uint32_t)t0.n;
+        A.n1 = (uint32_t)t1.n;
+        A.n_pat = (uint32_t)n_pat;
+        A.label_code = code.p;
+        A.ghist = hist.p;
+        A.bad = flags.p;
+        const bool lds = 3 * n_pat * 4 <= std::min<int64_t>(LH_LDS_BYTES, ctx->lds_per_block);
+        if (ctx->code_bytes == 2) SPK_TRY(launch_label_pairs_hist<uint16_t>(ctx, A, lds));
+        else SPK_TRY(launch_label_pairs_hist<uint32_t>(ctx, A, lds));
+    }
+    SPK_TRY(T.stop());  // the read-backs are no launches
+    unsigned int h_bad = 0u;
+    SPK_HIP(hipMemcpyAsync(&h_bad, flags.p, sizeof(h_bad), hipMemcpyDeviceToHost, st));
+    SPK_HIP(hipMemcpyAsync(out_counts, hist.p, (size_t)3 * n_pat * 8, hipMemcpyDeviceToHost, st));
+    if (out_pattern_mp) SPK_HIP(hipMemcpyAsync(out_pattern_mp, mpat.p, (size_t)n_pat * 8, hipMemcpyDeviceToHost, st));
+    if (out_label_code && n_labels > 0)
+        SPK_HIP(hipMemcpyAsync(out_label_code, code.p, (size_t)n_labels * 4, hipMemcpyDeviceToHost, st));
+    SPK_HIP(hipStreamSynchronize(st));
+    SPK_TRY(T.add());
+    SPK_REQUIRE(!(h_bad & LP_BAD_PAIR), SPK_E_STATE,
+                "spk_label_pairs_histogram: a pair names a row outside its table or a code outside the pattern space");
+    SPK_REQUIRE(h_bad == 0u, SPK_E_STATE, "spk_label_pairs_histogram: the pair table is damaged");
+    ctx->lpairs_pairs = P;
+    ctx->lpairs_ms = T.result();
+    ctx->lpairs_capacity = capacity;
+    ctx->lpairs_max_probe = (int)h_flags[1];
+    return SPK_OK;
+}
+
+extern "C" int spk_label_pairs_info(spk_ctx *ctx, int64_t *out_pairs, double *out_ms, int64_t *out_capacity,
+                                    int *out_max_probe) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_label_pairs_info: null ctx");
+    if (out_pairs) *out_pairs = ctx->lpairs_pairs;
+    if (out_ms) *out_ms = ctx->lpairs_ms;
+    if (out_capacity) *out_capacity = ctx->lpairs_capacity;
+    if (out_max_probe) *out_max_probe = ctx->lpairs_max_probe;
+    return SPK_OK;
 }
 
 extern "C" int spk_label_scores_info(spk_ctx *ctx, int64_t *out_pairs, double *out_ms) {

@@ -220,6 +220,45 @@ def _label_counts(gamma_frame, label_column, lam=None, level_probs=None):
     return LabelCounts(names, levels, counts, mp, job.link_type, true_pairs_total(job.link_type, ids0, ids1))
 
 
+def pair_label_sides(job):
+    """labels.PairLabelSides of a job: its unique ids (and, link_and_dedupe, source tables) in device row order."""
+    from .labels import PairLabelSides
+    sides = (0, 1) if job.link_type == "link_only" else (0,)
+    for s in sides:
+        if job.uid not in job.inputs[s].columns:
+            raise ValueError(f"unique_id_column_name {job.uid!r} is not a column of input table {s}")
+    source = job.host_values(0, "_source_table") if job.link_type == "link_and_dedupe" else None
+    return PairLabelSides(job.link_type, job.uid, [job.host_values(s, job.uid) for s in sides], source)
+
+
+def _pair_label_counts(gamma_frame, labels, match_threshold, lam=None, level_probs=None):
+    """PairLabelCounts of a frame's pairs against the labels table `labels` (labels.pair_label_rows' columns;
+    spk_label_pairs_histogram); with lam / level_probs also the match_probability of every pattern under them."""
+    from . import distributed as D
+    from .labels import PairLabelCounts, pair_label_rows
+    job = gamma_frame.job
+    if getattr(job, "passthrough", None) is not None:
+        raise ValueError("label_counts_from_pairs() needs the records: a job made from a gamma table has pairs "
+                         "without rows")
+    if not isinstance(labels, pd.DataFrame):
+        from .blocking import as_pandas
+        labels = as_pandas(labels)
+    rows_l, rows_r, is_match = pair_label_rows(pair_label_sides(job), labels, match_threshold)
+    gamma_frame.ensure_codes()
+    if level_probs is None:
+        counts, mp, code = job.ctx.label_pairs_histogram(rows_l, rows_r, is_match)
+    else:
+        m, u = job.flat_tables(level_probs)
+        counts, mp, code = job.ctx.label_pairs_histogram(rows_l, rows_r, is_match, float(lam), float(1 - lam), m, u)
+    if job.reduces_across_ranks() or job.force_reduce:
+        # ranks hold shards of the pairs: the counts sum exactly, and a labelled pair is a candidate of one rank only
+        # (-1 on the others), so the maximum is its code
+        D.allreduce_host_(counts, force=job.force_reduce)
+        D.allreduce_host_(code, force=job.force_reduce, op="max")
+    names, levels = gamma_frame.meta
+    return PairLabelCounts(names, levels, counts, mp, job.link_type, labels, is_match, code)
+
+
 def _score_thresholds(thresholds, what):
     """Thresholds as the spk_label_scores_* calls take them: float64, ascending (sorted here, as
     LabelCounts.truth_table sorts them), no NaN, at most _native.LABEL_SCORE_MAX_THRESHOLDS."""
@@ -334,6 +373,13 @@ class GammaFrame(SplinkDataFrame):
         scores (its patterns() and m_step() work, truth_table() needs the scored frame's)."""
         return _label_counts(self, label_column)
 
+    def label_counts_from_pairs(self, labels, match_threshold=0.5):
+        """label_counts against a table of labelled pairs instead of a column of the records (a clerical-review
+        sample: `<unique id>_l`, `<unique id>_r`, `clerical_match_score`, labels.pair_label_rows): a
+        `PairLabelCounts` without scores.  A pair is a match iff its score >= match_threshold; candidate pairs
+        without a label are unlabelled."""
+        return _pair_label_counts(self, labels, match_threshold)
+
 
 class ExpectationFrame(SplinkDataFrame):
     """E-step output (run_expectation_step): lazily scored with the parameters it was created with."""
@@ -421,6 +467,17 @@ class ExpectationFrame(SplinkDataFrame):
         `label_column`, at the given thresholds or (None) at every distinct score: the exact ROC and
         precision / recall curve.  Shorthand for label_counts(label_column).truth_table(thresholds)."""
         return self.label_counts(label_column).truth_table(thresholds)
+
+    def label_counts_from_pairs(self, labels, match_threshold=0.5):
+        """GammaFrame.label_counts_from_pairs with the match_probability of every pattern under this frame's
+        parameters: its labelled_pairs() and prediction_errors(threshold) carry the scores."""
+        return _pair_label_counts(self.gammas, labels, match_threshold, self.lam, self.level_probs)
+
+    def truth_table_from_pairs(self, labels, thresholds=None, match_threshold=0.5):
+        """truth_table against a table of labelled pairs: tp, fp, tn, fn over the labelled candidate pairs,
+        recall_of_all_true_pairs over all labelled matches.  Shorthand for
+        label_counts_from_pairs(labels, match_threshold).truth_table(thresholds)."""
+        return self.label_counts_from_pairs(labels, match_threshold).truth_table(thresholds)
 
 
 class FilteredFrame(SplinkDataFrame):

@@ -6,10 +6,15 @@ match_probability is a function of a pair's comparison pattern alone, so one dev
 the exact confusion matrix at every threshold, the true pairs blocking never produced, and the supervised estimate
 of m / u / λ -- one M-step with match_probability replaced by the label.  Scores that are decided per pair
 (tf_adjusted_match_prob, the pairs a filter or a best-match step kept) are counted per (truth state, threshold bin)
-instead (spk_label_scores_*, ScoreLabelCounts).  This module is the host side: pure numpy / pandas, importable
-without a device.
+instead (spk_label_scores_*, ScoreLabelCounts).  Labels may also come as a table of pairs that a person marked match
+or non-match (a clerical-review sample; later releases: truth_space_table_from_labels_table,
+prediction_errors_from_labels_table, estimate_m_from_pairwise_labels): pair_label_rows turns it into device rows,
+spk_label_pairs_histogram counts the candidate pairs against it, PairLabelCounts is what follows.  This module is the
+host side: pure numpy / pandas, importable without a device.
 """
 from __future__ import annotations
+
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import pandas as pd
@@ -251,6 +256,171 @@ def estimate_from_labels(df_gammas: object, params, settings: dict, spark: objec
     counts = gf.label_counts(label_column)
     if int(counts.counts[:UNKNOWN].sum()) == 0:
         raise ValueError(f"estimate_from_labels: no pair has a label on both sides in column {label_column!r}")
+    lam, rows = counts.m_step()
+    params._update_params(lam, rows)
+    return run_expectation_step(gf, params, settings, spark)
+
+
+# ---- labels given as a table of pairs ------------------------------------------------------------------------------
+class PairLabelSides(NamedTuple):
+    """What pair_label_rows needs to know of a job (frames.pair_label_sides makes one from a Job)."""
+    link_type: str
+    uid: str                               # the settings' unique_id_column_name
+    uids: Sequence[np.ndarray]             # the unique ids in device row order: [table 0], or [left, right] (link_only)
+    source: Optional[np.ndarray] = None    # link_and_dedupe: 'left' / 'right' per device row of the concatenated table
+
+
+def _rows_text(mask, limit=8) -> str:
+    at = np.flatnonzero(mask)
+    more = f" (and {len(at) - limit} more)" if len(at) > limit else ""
+    return "row" + ("s " if len(at) != 1 else " ") + ", ".join(str(int(i)) for i in at[:limit]) + more
+
+
+def _rows_of_ids(uids, values) -> np.ndarray:
+    """The position in `uids` of every value: -1 = not among them, -2 = it occurs there more than once."""
+    uids = np.asarray(uids)
+    index = pd.Index(uids)
+    if index.is_unique:
+        return np.asarray(index.get_indexer(values), dtype=np.int64)
+    dup = np.asarray(index.duplicated(keep=False))
+    once = np.flatnonzero(~dup)
+    at = np.asarray(pd.Index(uids[once]).get_indexer(values), dtype=np.int64)
+    out = np.where(at >= 0, once[np.maximum(at, 0)], -1) if len(once) else np.full(len(values), -1, dtype=np.int64)
+    out[np.asarray(pd.Index(values).isin(uids[dup]))] = -2
+    return out
+
+
+def pair_label_rows(job_like: PairLabelSides, labels: pd.DataFrame, match_threshold: float = 0.5):
+    """(rows_l int32, rows_r int32, is_match uint8): the labelled pairs of `labels` as device rows, in its row order.
+
+    labels: `<uid>_l`, `<uid>_r` and `clerical_match_score` (a number or a bool); a pair is a match iff its score >=
+    match_threshold (the later releases' threshold_actual).  Under link_only `_l` names a record of df_l and `_r` one
+    of df_r; under link_and_dedupe the optional `_source_table_l` / `_source_table_r` ('left' / 'right') say which
+    input each id belongs to, and are required for an id that both inputs hold; otherwise the order of a pair does not
+    matter.  ValueError, naming the rows of `labels` at fault (positions, from 0): a missing column, a NULL id or
+    score, an id that is not in the table, a pair of a record with itself, a pair given twice (in either order where
+    the order does not matter, whether or not the scores agree)."""
+    uid = job_like.uid
+    col_l, col_r, col_s = f"{uid}_l", f"{uid}_r", "clerical_match_score"
+    missing = [c for c in (col_l, col_r, col_s) if c not in labels.columns]
+    if missing:
+        raise ValueError(f"pair labels: the labels table has no column {', '.join(map(repr, missing))}")
+    a, b, score = labels[col_l], labels[col_r], labels[col_s]
+    null = (a.isna() | b.isna() | score.isna()).to_numpy()
+    if null.any():
+        raise ValueError(f"pair labels: a NULL id or score in {_rows_text(null)}")
+    is_match = (score.to_numpy(dtype=np.float64) >= float(match_threshold)).astype(np.uint8)
+    a, b = a.to_numpy(), b.to_numpy()
+    one_table = job_like.link_type != "link_only"
+    src_cols = [c for c in ("_source_table_l", "_source_table_r") if c in labels.columns]
+    if job_like.link_type == "link_and_dedupe" and src_cols:
+        if len(src_cols) != 2:
+            raise ValueError("pair labels: _source_table_l and _source_table_r come together")
+        source = np.asarray(job_like.source)
+        halves = {s: np.flatnonzero(source == s) for s in ("left", "right")}
+        rows = []
+        for values, col in ((a, "_source_table_l"), (b, "_source_table_r")):
+            src = labels[col].to_numpy()
+            other = ~np.isin(src, ("left", "right"))
+            if other.any():
+                raise ValueError(f"pair labels: {col} is neither 'left' nor 'right' in {_rows_text(other)}")
+            out = np.full(len(values), -1, dtype=np.int64)
+            for s, half in halves.items():
+                pick = src == s
+                at = _rows_of_ids(np.asarray(job_like.uids[0])[half], values[pick])
+                out[pick] = np.where(at >= 0, half[np.maximum(at, 0)], at) if len(half) else -1
+            rows.append(out)
+        rows_l, rows_r = rows
+    else:
+        rows_l = _rows_of_ids(job_like.uids[0], a)
+        rows_r = _rows_of_ids(job_like.uids[0 if one_table else 1], b)
+    twice = (rows_l == -2) | (rows_r == -2)
+    if twice.any():
+        hint = (": give _source_table_l / _source_table_r ('left' / 'right')"
+                if job_like.link_type == "link_and_dedupe" and not src_cols else "")
+        raise ValueError(f"pair labels: an id that more than one input record carries in {_rows_text(twice)}{hint}")
+    absent = (rows_l < 0) | (rows_r < 0)
+    if absent.any():
+        raise ValueError(f"pair labels: an id that is not in the input table in {_rows_text(absent)}")
+    if one_table:
+        same = rows_l == rows_r
+        if same.any():
+            raise ValueError(f"pair labels: a pair of a record with itself in {_rows_text(same)}")
+        lo, hi = np.minimum(rows_l, rows_r), np.maximum(rows_l, rows_r)
+    else:
+        lo, hi = rows_l, rows_r
+    _, inverse, n_given = np.unique((lo << 32) | hi, return_inverse=True, return_counts=True)
+    again = n_given[inverse.reshape(-1)] > 1
+    if again.any():
+        raise ValueError(f"pair labels: the same pair more than once in {_rows_text(again)}")
+    return rows_l.astype(np.int32), rows_r.astype(np.int32), is_match
+
+
+class PairLabelCounts(LabelCounts):
+    """LabelCounts of the candidate pairs against a table of labelled pairs (spk_label_pairs_histogram): MATCH and
+    NON_MATCH hold the labelled candidate pairs, UNKNOWN the candidate pairs without a label.
+
+    labels: the labels table; is_match [len(labels)]: its thresholded scores; label_code [len(labels)]: the packed
+    code of the candidate pair each label names, -1 when blocking did not produce it.  true_pairs_total is the number
+    of labelled matches, so missed_by_blocking counts the labelled matches that are not among the candidates and
+    recall_of_all_true_pairs is taken over all labelled matches; truth_table(), patterns() and m_step() are
+    LabelCounts' own."""
+
+    def __init__(self, names, n_levels, counts, mp, link_type, labels, is_match, label_code):
+        self.labels = labels
+        self.is_match = np.ascontiguousarray(is_match).astype(bool)
+        self.label_code = np.ascontiguousarray(label_code, dtype=np.int64)
+        if not len(labels) == len(self.is_match) == len(self.label_code):
+            raise ValueError("PairLabelCounts: labels, is_match and label_code differ in length")
+        super().__init__(names, n_levels, counts, mp, link_type, true_pairs_total=int(self.is_match.sum()))
+        if len(self.label_code) and int(self.label_code.max()) >= self.n_patterns:
+            raise ValueError("PairLabelCounts: a label_code outside the pattern space")
+        self.non_matches_missed_by_blocking = int((~self.is_match).sum()) - int(self.counts[NON_MATCH].sum())
+
+    def labelled_pairs(self) -> pd.DataFrame:
+        """The labels table in its own row order plus found_by_blocking, the gamma_* levels of the candidate pair and,
+        if scored, its match_probability (both NULL when blocking did not produce the pair)."""
+        found = self.label_code >= 0
+        out = self.labels.copy()
+        out["found_by_blocking"] = found
+        lev = self.levels(np.where(found, self.label_code, 0))
+        for k, name in enumerate(self.names):
+            out[name] = pd.arrays.IntegerArray(lev[:, k].astype(np.int32), mask=~found)
+        if self.mp is not None:
+            mp = np.full(len(found), np.nan, dtype=np.float64)
+            mp[found] = self.mp[self.label_code[found]]
+            out["match_probability"] = mp
+        return out
+
+    def prediction_errors(self, threshold: float) -> pd.DataFrame:
+        """The rows of labelled_pairs() that `match_probability > threshold` gets wrong, with a column `error`: "fp"
+        for a labelled non-match above the threshold, "fn" for a labelled match that is not -- a NULL score is never
+        predicted a match, so a labelled match that blocking did not produce is an "fn"."""
+        if self.mp is None:
+            raise ValueError("prediction_errors: these counts carry no match_probability: take them from the frame "
+                             "run_expectation_step returns")
+        pairs = self.labelled_pairs()
+        predicted = pairs["match_probability"].to_numpy() > float(threshold)
+        fp, fn = predicted & ~self.is_match, ~predicted & self.is_match
+        out = pairs[fp | fn].copy()
+        out["error"] = np.where(fp[fp | fn], "fp", "fn")
+        return out
+
+
+def estimate_from_pair_labels(df_gammas: object, params, settings: dict, spark: object, labels: pd.DataFrame,
+                              match_threshold: float = 0.5):
+    """estimate_from_labels with the truth taken from a table of labelled pairs (pair_label_rows' columns): one M-step
+    over the labelled candidate pairs, then the E-step under the new parameters.  Returns that scored frame."""
+    from .expectation_step import run_expectation_step
+    from .frames import ExpectationFrame, GammaFrame, reject_filtered
+    reject_filtered(df_gammas, "estimate_from_pair_labels")
+    gf = df_gammas.gammas if isinstance(df_gammas, ExpectationFrame) else df_gammas
+    if not isinstance(gf, GammaFrame):
+        raise ValueError("estimate_from_pair_labels needs the records: pass the frame add_gammas returns (a gamma "
+                         "table has pairs without rows)")
+    counts = gf.label_counts_from_pairs(labels, match_threshold)
+    if int(counts.counts[:UNKNOWN].sum()) == 0:
+        raise ValueError("estimate_from_pair_labels: no labelled pair is among the candidate pairs")
     lam, rows = counts.m_step()
     params._update_params(lam, rows)
     return run_expectation_step(gf, params, settings, spark)
