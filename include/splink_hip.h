@@ -555,6 +555,41 @@ int spk_select_tf_columns(spk_ctx *ctx, double lambda, double one_minus, const d
 int spk_select_copy_tf(spk_ctx *ctx, int64_t start, int64_t count, double *out_tf_mp,
                        double *out_adj /* [count x n_tf_cols] or NULL */);
 
+/* ---- a stratified random sample of the scored pairs (replaces df_e.toPandas() followed by a pandas
+ *      groupby(score band).sample(k), the clerical-review sample the reference's users label by hand) ---- */
+#define SPK_SAMPLE_MAX_STRATA 64
+/* Keeps, per score band, the quota[b] pairs with the smallest random keys.  The result is this set, whatever the
+ * launch shape:
+ *   mix(x):       x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31
+ *   key(seed, p): mix(mix(seed) + 0x9E3779B97F4A7C15 * (p + 1)) in 64-bit wrap-around arithmetic, p the pair's ordinal
+ *                 (as spk_select_copy reports it); a bijection of p, so no two pairs share a key
+ *   strata:       n_strata + 1 finite, strictly ascending edges, 1 <= n_strata <= SPK_SAMPLE_MAX_STRATA; a pair whose
+ *                 match_probability x (under lambda / m / u, as spk_score) is not NULL and lies in
+ *                 [edges[0], edges[n_strata]] is in the stratum b with edges[b] <= x < edges[b + 1], the last stratum
+ *                 also taking x == edges[n_strata]; any other pair is in no stratum
+ *   eligible:     in a stratum, and every term TRUE (spk_select's conjunction and three-valued logic; fields SPK_SEL_MP
+ *                 and SPK_SEL_GAMMA; n_terms = 0: all)
+ *   kept:         in stratum b the min(quota[b], population[b]) eligible pairs with the smallest keys
+ * So a larger quota under the same seed keeps a superset, and a stratum with population <= quota is kept whole.
+ * This is a selecting call: it drops the previous selection first, and on success the context's one selection holds
+ * the kept pairs in ascending ordinal (rows when the pair set has them, codes, the mp table); spk_select_copy,
+ * spk_select_info, spk_select_release, spk_select_best, spk_components* and spk_label_scores_selection work on it
+ * unchanged, and it goes stale as spk_select's does.  m and u are required.  The thresholds are found by a radix select
+ * over the keys, 8 passes of 8 bits over the codes with one histogram per stratum, then spk_select's count, scan and
+ * emit: nothing of P elements is allocated but the chunk counts.  SPK_E_INVALID: edges not finite or not strictly
+ * ascending, n_strata out of range, a negative quota, an unknown field (SPK_SEL_TF_MP included) or operator, and
+ * spk_select's argument errors.  SPK_E_STATE: no gammas.  A failing call leaves no selection.  Does not touch the
+ * scores of spk_score, tf state or EM state. */
+int spk_select_sample(spk_ctx *ctx, double lambda, double one_minus, const double *m, const double *u, int n_terms,
+                      const spk_select_term *terms, int n_strata, const double *edges /* [n_strata + 1] */,
+                      const int64_t *quota /* [n_strata] */, uint64_t seed, int64_t *out_n_selected);
+/* The last spk_select_sample: its strata (-1: none yet, or the last call failed; nothing else is written then), per
+ * stratum the eligible pairs and the pairs kept (the first n_strata entries; either may be NULL), and with timing on
+ * (spk_ctx_enable_timing) the device milliseconds of its launches (pattern stage, histogram passes and digit picks,
+ * count pass and scan, emit pass; the host round trip between them is not in it), -1 otherwise. */
+int spk_select_sample_info(spk_ctx *ctx, int *out_n_strata, int64_t *out_population /* [n_strata] */,
+                           int64_t *out_kept /* [n_strata] */, double *out_ms);
+
 /* ---- best match per record (replaces the window query the reference's users run over the frame
  *      expectation_step.py returns: row_number() over (partition by unique_id_l order by match_probability desc) = 1,
  *      often once per side and then joined, to link each record to its best candidate) ---- */

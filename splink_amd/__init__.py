@@ -20,7 +20,7 @@ from .comparison_evaluation import (DEFAULT_MAX_ENUMERATE, BlockingProfile, get_
                                     profile_blocking_rules)
 from .expectation_step import run_expectation_step
 from .frames import (BestMatchFrame, ClusterBridges, ClusterFrame, ClusterMetrics, ClusterSweepFrame, FilteredFrame,
-                     SplinkDataFrame)
+                     SampleFrame, SplinkDataFrame)
 from .gammas import add_gammas
 from .iterate import iterate
 from .labels import (LabelCounts, PairLabelCounts, ScoreLabelCounts, estimate_from_labels,
@@ -34,7 +34,7 @@ from .validate import validate_settings
 
 __all__ = ["Splink", "load_from_json", "AmdSession", "session", "Params", "block_using_rules", "add_gammas",
            "iterate", "run_expectation_step", "make_adjustment_for_term_frequencies", "complete_settings_dict",
-           "ClusterFrame", "ClusterSweepFrame", "ClusterMetrics", "ClusterBridges", "FilteredFrame", "BestMatchFrame", "LabelCounts", "ScoreLabelCounts", "estimate_from_labels",
+           "ClusterFrame", "ClusterSweepFrame", "ClusterMetrics", "ClusterBridges", "FilteredFrame", "BestMatchFrame", "SampleFrame", "LabelCounts", "ScoreLabelCounts", "estimate_from_labels",
            "PairLabelCounts", "estimate_from_pair_labels",
            "estimate_u_using_random_sampling", "random_pairs", "get_largest_blocks", "profile_blocking_rules",
            "BlockingProfile"]

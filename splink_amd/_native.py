@@ -44,6 +44,7 @@ SWEEP_MAX_LEVELS = 32  # SPK_SWEEP_MAX_LEVELS
 SEL_OP = {"<": 0, "<=": 1, ">": 2, ">=": 3, "=": 4, "!=": 5, "is null": 6, "is not null": 7}  # SPK_SEL_LT ..
 SELECT_MAX_TERMS = 8  # SPK_SELECT_MAX_TERMS
 BEST_L, BEST_R, BEST_EITHER, BEST_MUTUAL = 0, 1, 2, 3  # SPK_BEST_L .. SPK_BEST_MUTUAL (select_best's modes)
+SAMPLE_MAX_STRATA = 64  # SPK_SAMPLE_MAX_STRATA
 # Pair ordinals per count of the selection's compaction.  Mirrored from SEL_CHUNK in csrc/spk_select.hip (the
 # library exports no call for it); only the tests' edge sizes depend on it.
 SELECT_CHUNK = 2048
@@ -80,6 +81,7 @@ EXPORTS = [
     "spk_select", "spk_select_copy", "spk_select_info", "spk_select_release",
     "spk_select_tf", "spk_select_tf_columns", "spk_select_copy_tf",
     "spk_select_best", "spk_select_best_info",
+    "spk_select_sample", "spk_select_sample_info",
     "spk_components", "spk_components_edges", "spk_components_copy", "spk_components_info", "spk_components_release",
     "spk_components_sweep", "spk_components_sweep_edges", "spk_components_sweep_copy", "spk_components_sweep_info",
     "spk_components_sweep_release", "spk_components_sweep_set_mode",
@@ -762,6 +764,37 @@ class Context:
         check(self._lib.spk_select_best_info(self._h, ctypes.byref(b), ctypes.byref(k), ctypes.byref(ms)),
               "spk_select_best_info")
         return b.value, k.value, ms.value
+
+    def select_sample(self, lam, one_minus, m, u, terms, edges, quota, seed) -> int:
+        """spk_select_sample: per stratum of match_probability (len(edges) - 1 strata, ascending edges) keep the
+        quota[b] pairs with the smallest keys of `seed` among those for which every term is TRUE; returns how many.
+        They become the context's selection (select_copy, select_info, select_best, components work on them)."""
+        edges = np.ascontiguousarray(edges, dtype=np.float64)
+        quota = np.ascontiguousarray(quota, dtype=np.int64)
+        if edges.ndim != 1 or quota.ndim != 1 or len(edges) != len(quota) + 1:
+            raise ValueError("select_sample: one quota per stratum, and one edge more than strata")
+        t = self._select_terms(terms)
+        m = np.ascontiguousarray(m, dtype=np.float64)
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        n = ctypes.c_int64(0)
+        check(self._lib.spk_select_sample(self._h, ctypes.c_double(lam), ctypes.c_double(one_minus), _ptr(m), _ptr(u),
+                                          ctypes.c_int(len(t)), _ptr(t) if len(t) else ctypes.c_void_p(0),
+                                          ctypes.c_int(len(quota)), _ptr(edges),
+                                          _ptr(quota) if len(quota) else ctypes.c_void_p(0),
+                                          ctypes.c_uint64(int(seed)), ctypes.byref(n)), "spk_select_sample")
+        return n.value
+
+    def select_sample_info(self):
+        """The last select_sample: (strata or -1, eligible pairs per stratum, pairs kept per stratum, ms of its
+        launches with timing on or -1); the arrays are empty when there is none."""
+        k = ctypes.c_int(-1)
+        pop = np.zeros(SAMPLE_MAX_STRATA, dtype=np.int64)
+        kept = np.zeros(SAMPLE_MAX_STRATA, dtype=np.int64)
+        ms = ctypes.c_double(-1.0)
+        check(self._lib.spk_select_sample_info(self._h, ctypes.byref(k), _ptr(pop), _ptr(kept), ctypes.byref(ms)),
+              "spk_select_sample_info")
+        n = max(k.value, 0)
+        return k.value, pop[:n].copy(), kept[:n].copy(), ms.value
 
     # ---- connected components of the kept pairs -----------------------------------------------
     def components(self):

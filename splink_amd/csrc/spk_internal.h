@@ -518,6 +518,10 @@ struct spk_ctx {
     // the last spk_select_best (spk_best.hip): survivors before, pairs kept (-1: none, or it failed), device milliseconds
     int64_t best_before = -1, best_kept = -1;
     double best_ms = -1.0;
+    // the last spk_select_sample (spk_select.hip): per stratum the eligible pairs and the pairs kept (empty: none, or it
+    // failed), device milliseconds
+    std::vector<int64_t> strata_pop, strata_kept;
+    double strata_ms = -1.0;
     // spk_components*: the last labels
     spk::Components comp;
     // spk_components_sweep*: the last sweep, and which edges a level's rounds hook: 0 the level's new edges plus a star

@@ -19,6 +19,11 @@
 // pairs (tf_pair's arithmetic, spk_tf_pair.h), counts, and writes one 64-bit ballot word per (chunk, slab, element):
 // a keep bitmap of P / 8 bytes.  k_select_tf_emit takes the ranks from those words and recomputes
 // tf_adjusted_match_prob and the adjustments for the survivors only.
+//
+// spk_select_sample keeps, per stratum of match_probability, the quota pairs with the smallest counter-based random
+// keys: the stratum is a function of the pattern (a byte per pattern beside the keep bit's logic), the thresholds come
+// from a radix select over the keys that stores nothing per pair, and the survivors from the same count, scan and emit
+// (see "spk_select_sample" below).
 #include <algorithm>
 #include <cmath>
 
@@ -61,26 +66,30 @@ __device__ inline bool sel_term_true(int op, bool null, double v, double x) {
     }
 }
 
-// One thread per pattern: decode the levels the terms read (PatArgs' strides), evaluate the conjunction, and write
-// the wave's 64 keep bits as one word.  keep has (n_pat + 63) / 64 words; mpat may be null (no SPK_SEL_MP term).
+// The conjunction of A's terms for pattern p < n_pat: the levels the terms read are decoded with PatArgs' strides.
+__device__ inline bool sel_pattern_true(const SelPatArgs &A, const double *__restrict__ mpat, int64_t p) {
+    bool k = true;
+    for (int t = 0; t < A.n_terms; ++t) {
+        const spk_select_term T = A.terms[t];
+        bool null = false;
+        double v;
+        if (T.field == SPK_SEL_MP) {
+            v = mpat[p];
+            null = v != v;
+        } else {
+            v = (double)((int)((p / A.stride[T.col]) % (A.nlev[T.col] + 1)) - 1);
+        }
+        k = k && sel_term_true(T.op, null, v, T.value);
+    }
+    return k;
+}
+
+// One thread per pattern: evaluate the conjunction, and write the wave's 64 keep bits as one word.  keep has
+// (n_pat + 63) / 64 words; mpat may be null (no SPK_SEL_MP term).
 __global__ __launch_bounds__(SEL_THREADS) void k_select_patterns(SelPatArgs A, const double *__restrict__ mpat,
                                                                  unsigned long long *__restrict__ keep) {
     const int64_t p = (int64_t)blockIdx.x * SEL_THREADS + threadIdx.x;
-    bool k = p < A.n_pat;
-    if (k) {
-        for (int t = 0; t < A.n_terms; ++t) {
-            const spk_select_term T = A.terms[t];
-            bool null = false;
-            double v;
-            if (T.field == SPK_SEL_MP) {
-                v = mpat[p];
-                null = v != v;
-            } else {
-                v = (double)((int)((p / A.stride[T.col]) % (A.nlev[T.col] + 1)) - 1);
-            }
-            k = k && sel_term_true(T.op, null, v, T.value);
-        }
-    }
+    const bool k = p < A.n_pat && sel_pattern_true(A, mpat, p);
     const unsigned long long m = __ballot(k);
     if ((threadIdx.x & 63) == 0 && (p >> 6) < (A.n_pat + 63) / 64) keep[p >> 6] = m;
 }
@@ -421,6 +430,248 @@ __global__ __launch_bounds__(256) void k_select_decode(SelDecodeArgs A) {
     if (A.out_mp) A.out_mp[i] = A.mpat[c];
 }
 
+// ---- spk_select_sample: per stratum of match_probability, the quota[b] eligible pairs with the smallest keys ----
+// The stratum is a function of the pattern, like the keep bit: k_sample_patterns writes one byte per pattern (SMP_NONE:
+// fails a term, NULL score, or outside the edges).  The quota[b]-th smallest key of every stratum is found by a radix
+// select, most significant digit first, with nothing stored per pair: pass d of k_sample<SMP_HIST> streams the codes in
+// k_select's chunk layout, recomputes each pair's key from its ordinal, and counts digit d of the keys that agree with
+// their stratum's prefix in the digits above it, into an LDS histogram [n_strata][256] that is added to the global one
+// at the end; k_sample_pick (one workgroup) then takes, per stratum, the digit at which the running count reaches what
+// is left of the quota, extends the prefix by it and reduces the remainder by the count below it.  After 8 passes the
+// prefix is the threshold: exactly quota[b] keys of the stratum are <= it.  A stratum with population <= quota is
+// settled in pass 0 (threshold all ones: kept whole), so is quota 0 (none kept), and once no stratum is left the later
+// histogram passes return at their first load.  Histograms are integer sums, so nothing depends on arrival order.
+// k_sample<SMP_COUNT> and <SMP_EMIT> are k_select's two passes under `in a stratum and key <= its threshold`.
+constexpr int SMP_MAX = SPK_SAMPLE_MAX_STRATA;
+constexpr int SMP_NONE = 255;                  // the stratum byte of a pattern that is never sampled
+constexpr int SMP_DIGITS = 256, SMP_PASSES = 8;  // 8 bits per pass over the 64-bit key
+constexpr int SMP_WG_PER_CU = 2;               // histogram passes: fewer workgroups, fewer histograms to add up
+constexpr int64_t SMP_LDS_BYTES = 80 * 1024;   // two workgroups of a CU's 160 KiB stay resident: the histogram (64 KiB at
+                                               // 64 strata) and, while it fits beside it, the stratum table
+constexpr int64_t SMP_STATIC_BYTES = 1024;     // reserved for k_sample's static LDS (s_key, s_flag)
+static_assert(SMP_MAX < SMP_NONE && SMP_MAX % SEL_WAVES == 0, "stratum byte, k_sample_pick's strata per wave");
+
+// The per-stratum state of one call, 64-bit words on the device: [ST_x + b] for stratum b.
+enum { ST_PREFIX = 0, ST_REMAIN = SMP_MAX, ST_THR = 2 * SMP_MAX, ST_FLAG = 3 * SMP_MAX, ST_POP = 4 * SMP_MAX,
+       ST_KEPT = 5 * SMP_MAX, ST_ACTIVE = 6 * SMP_MAX, ST_WORDS = 6 * SMP_MAX + 1 };
+enum { SMP_ACTIVE = 0, SMP_ALL = 1, SMP_EMPTY = 2 };  // ST_FLAG: still selecting / kept whole / none kept
+
+// spk_sample.hip's sm_mix, restated (spk_select_sample's keys are part of the ABI: the values must not change).
+__host__ __device__ inline uint64_t smp_mix(uint64_t x) {
+    x ^= x >> 30;
+    x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27;
+    x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+__device__ inline uint64_t smp_key(uint64_t seed_mix, int64_t p) {
+    return smp_mix(seed_mix + 0x9E3779B97F4A7C15ull * ((uint64_t)p + 1ull));
+}
+
+struct SmpPatArgs {
+    int n_strata;
+    double edges[SMP_MAX + 1];
+};
+
+// One thread per pattern: its stratum, or SMP_NONE.  tab [n_pat]; mpat is the call's mp table (never null).
+__global__ __launch_bounds__(SEL_THREADS) void k_sample_patterns(SelPatArgs A, SmpPatArgs E,
+                                                                 const double *__restrict__ mpat,
+                                                                 uint8_t *__restrict__ tab) {
+    const int64_t p = (int64_t)blockIdx.x * SEL_THREADS + threadIdx.x;
+    if (p >= A.n_pat) return;
+    const double x = mpat[p];
+    int b = SMP_NONE;
+    // a NaN fails both comparisons; the last stratum is closed on the right, so edges[n_strata] is no boundary below
+    if (x >= E.edges[0] && x <= E.edges[E.n_strata] && sel_pattern_true(A, mpat, p)) {
+        b = 0;
+        for (int i = 1; i < E.n_strata; ++i) b += x >= E.edges[i] ? 1 : 0;
+    }
+    tab[p] = (uint8_t)b;
+}
+
+enum { SMP_HIST = 0, SMP_COUNT = 1, SMP_EMIT = 2 };
+
+struct SmpArgs {
+    const void *codes;          // uint16 or uint32, one per pair
+    int64_t P, n_chunks;
+    const uint8_t *tab;         // stratum per pattern
+    int64_t n_pat;
+    int tab_words;              // 32-bit words of tab staged in LDS (LDS form)
+    int n_strata, pass;         // pass: SMP_HIST's digit, 0 = the most significant
+    uint64_t seed_mix;          // mix(seed)
+    const unsigned long long *st;  // the strata's state (SMP_HIST: read from pass 1 on)
+    unsigned long long *hist;   // SMP_HIST: [n_strata x SMP_DIGITS], zero at launch
+    const int32_t *pl, *pr;     // as SelectArgs from here on
+    int64_t *chunk_count;
+    const int64_t *chunk_off;
+    int64_t *out_ord;
+    int32_t *out_l, *out_r;
+    uint32_t *out_code;
+};
+
+template <typename CodeT, bool LDS, int MODE>
+__global__ __launch_bounds__(SEL_THREADS) void k_sample(SmpArgs A) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];  // SMP_HIST: the histogram; then the table (LDS)
+    __shared__ unsigned long long s_key[SMP_MAX];  // SMP_HIST: the stratum's prefix; otherwise its threshold
+    __shared__ int s_flag[SMP_MAX];
+    if (MODE == SMP_HIST && A.pass > 0 && A.st[ST_ACTIVE] == 0ull) return;  // every stratum is settled (grid-uniform)
+    const int hist_words = MODE == SMP_HIST ? A.n_strata * SMP_DIGITS : 0;
+    uint32_t *s_hist = s_dyn;
+    uint32_t *s_tab = s_dyn + hist_words;
+    for (int i = threadIdx.x; i < hist_words; i += SEL_THREADS) s_hist[i] = 0u;
+    if (LDS)
+        for (int i = threadIdx.x; i < A.tab_words; i += SEL_THREADS)
+            s_tab[i] = reinterpret_cast<const uint32_t *>(A.tab)[i];
+    const bool state = MODE != SMP_HIST || A.pass > 0;  // pass 0 counts every pair in a stratum
+    if (state && threadIdx.x < A.n_strata) {
+        s_key[threadIdx.x] = A.st[(MODE == SMP_HIST ? ST_PREFIX : ST_THR) + threadIdx.x];
+        s_flag[threadIdx.x] = (int)A.st[ST_FLAG + threadIdx.x];
+    }
+    __syncthreads();
+    const uint8_t *T = LDS ? reinterpret_cast<const uint8_t *>(s_tab) : A.tab;
+    constexpr int V = 16 / (int)sizeof(CodeT);            // codes per lane and slab
+    constexpr int SLABS = (int)(SEL_CHUNK / (64 * V));    // slabs per chunk
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int digit_shift = 56 - 8 * A.pass;  // SMP_HIST: the digit; the bits above it are digit_shift + 8 .. 63
+    const CodeT *codes = reinterpret_cast<const CodeT *>(A.codes);
+    const int64_t n_waves = (int64_t)gridDim.x * SEL_WAVES;
+    for (int64_t c = (int64_t)blockIdx.x * SEL_WAVES + wave; c < A.n_chunks; c += n_waves) {
+        int64_t run = 0;
+        if (MODE == SMP_EMIT) {
+            run = A.chunk_off[c];
+            if (A.chunk_off[c + 1] == run) continue;  // nothing kept here (wave-uniform)
+        }
+        const int64_t base = c * SEL_CHUNK;
+        sel_u32x4 v[SLABS];
+        sel_load_chunk<CodeT>(codes, base, A.P, lane, v);
+        int wave_total = 0;
+#pragma unroll
+        for (int s = 0; s < SLABS; ++s) {
+            const int64_t p0 = base + ((int64_t)s * 64 + lane) * V;  // this lane's first pair of the slab
+            uint32_t code[V];
+            unsigned km = 0;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const uint32_t x = sel_code<CodeT>(v[s], j);
+                code[j] = x;
+                const int b = p0 + j < A.P && (int64_t)x < A.n_pat ? (int)T[x] : SMP_NONE;
+                if (b >= A.n_strata) continue;  // SMP_NONE
+                const uint64_t key = smp_key(A.seed_mix, p0 + j);
+                if (MODE == SMP_HIST) {
+                    // digit_shift + 8 is 16 .. 56 here: pass 0 reads no state
+                    const bool in = !state || (s_flag[b] == SMP_ACTIVE &&
+                                               (key >> (digit_shift + 8)) == (s_key[b] >> (digit_shift + 8)));
+                    if (in) atomicAdd(&s_hist[b * SMP_DIGITS + (int)((key >> digit_shift) & 255u)], 1u);
+                } else {
+                    km |= (s_flag[b] != SMP_EMPTY && key <= s_key[b] ? 1u : 0u) << j;
+                }
+            }
+            if (MODE == SMP_HIST) continue;
+            int before = 0, all = 0;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const unsigned long long m = __ballot((km >> j) & 1u);
+                all += __popcll(m);
+                before += __popcll(m & below);
+            }
+            if (MODE == SMP_COUNT) {
+                wave_total += all;
+                continue;
+            }
+            int64_t q = run + before;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                if ((km >> j) & 1u) {
+                    const int64_t p = p0 + j;
+                    A.out_ord[q] = p;
+                    A.out_code[q] = code[j];
+                    if (A.pl) {
+                        A.out_l[q] = A.pl[p];
+                        A.out_r[q] = A.pr[p];
+                    }
+                    ++q;
+                }
+            }
+            run += all;
+        }
+        if (MODE == SMP_COUNT && lane == 0) A.chunk_count[c] = wave_total;
+    }
+    if (MODE == SMP_HIST) {  // a workgroup's count of a bin fits 32 bits: it sees at most n_chunks / gridDim.x + 1 chunks
+        __syncthreads();
+        for (int i = threadIdx.x; i < hist_words; i += SEL_THREADS) {
+            const uint32_t n = s_hist[i];
+            if (n) atomicAdd(&A.hist[i], (unsigned long long)n);
+        }
+    }
+}
+
+struct SmpPickArgs {
+    int n_strata, pass;
+    unsigned long long *hist;  // [n_strata x SMP_DIGITS] of this pass; left zero for the next
+    unsigned long long *st;
+    int64_t quota[SMP_MAX];
+};
+
+// One workgroup, a wave per stratum at a time, a lane per 4 digits.  Pass 0 also settles population, kept count and
+// the strata that need no selecting.  For an active stratum, 1 <= remainder <= the keys under its prefix, so exactly one
+// lane's digits contain the remainder-th key.
+__global__ __launch_bounds__(SEL_THREADS) void k_sample_pick(SmpPickArgs A) {
+    __shared__ int s_active;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) s_active = 0;
+    __syncthreads();
+    for (int r = 0; r < SMP_MAX / SEL_WAVES; ++r) {
+        const int b = r * SEL_WAVES + wave;
+        if (b >= A.n_strata) break;  // wave-uniform
+        unsigned long long *h = A.hist + (size_t)b * SMP_DIGITS + 4 * lane;
+        unsigned long long c[4], own = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            c[j] = h[j];
+            h[j] = 0ull;
+            own += c[j];
+        }
+        unsigned long long incl = own;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned long long t = __shfl_up(incl, d);
+            if (lane >= d) incl += t;
+        }
+        const unsigned long long total = __shfl(incl, 63);
+        unsigned long long k;
+        int flag;
+        if (A.pass == 0) {
+            k = (unsigned long long)A.quota[b] < total ? (unsigned long long)A.quota[b] : total;
+            flag = k == 0ull ? SMP_EMPTY : k == total ? SMP_ALL : SMP_ACTIVE;
+            if (lane == 0) {
+                A.st[ST_POP + b] = total;
+                A.st[ST_KEPT + b] = k;
+                A.st[ST_FLAG + b] = (unsigned long long)flag;
+                A.st[ST_THR + b] = ~0ull;
+                if (flag == SMP_ACTIVE) atomicAdd(&s_active, 1);
+            }
+        } else {
+            flag = (int)A.st[ST_FLAG + b];
+            k = A.st[ST_REMAIN + b];
+        }
+        if (flag != SMP_ACTIVE) continue;  // wave-uniform
+        unsigned long long before = incl - own;
+        if (before < k && k <= incl) {
+            int j = 0;
+            while (j < 3 && before + c[j] < k) before += c[j++];
+            const unsigned long long prefix =
+                (A.pass == 0 ? 0ull : A.st[ST_PREFIX + b]) | ((unsigned long long)(4 * lane + j) << (56 - 8 * A.pass));
+            A.st[ST_PREFIX + b] = prefix;
+            A.st[ST_REMAIN + b] = k - before;
+            if (A.pass == SMP_PASSES - 1) A.st[ST_THR + b] = prefix;
+        }
+    }
+    __syncthreads();
+    if (A.pass == 0 && threadIdx.x == 0) A.st[ST_ACTIVE] = (unsigned long long)s_active;
+}
+
 // The grid of every per-pair kernel here: capped, the waves stride over the chunks.
 static unsigned select_grid(spk_ctx *ctx, int64_t n_chunks) {
     int64_t g = (n_chunks + SEL_WAVES - 1) / SEL_WAVES;
@@ -460,6 +711,31 @@ static int launch_tf_emit(spk_ctx *ctx, const SelectArgs &A, const SelTfArgs &F,
     return SPK_OK;
 }
 
+// What every selection records of the context it is taken from: the pattern space, whether the pairs have rows, and
+// the counters that say when it goes stale.
+static void selection_header(spk_ctx *ctx, bool has_mp, Selection &S) {
+    const size_t P = (size_t)ctx->n_pairs;
+    S.K = ctx->K;
+    S.n_levels = ctx->n_levels;
+    S.stride = ctx->stride;
+    S.has_mp = has_mp;
+    S.has_rows = ctx->pairs_valid && ctx->pl.p && ctx->pr.p && ctx->pl.n >= P && ctx->pr.n >= P;
+    S.pairs_epoch = ctx->pairs_epoch;
+    S.gamma_seq = ctx->gamma_seq;
+    S.fix_seq = ctx->codes_fix_seq;
+}
+
+// The emit pass's outputs for n_sel survivors.
+static int selection_alloc(Selection &S, int64_t n_sel) {
+    SPK_TRY(S.ord.alloc((size_t)n_sel + 1));
+    SPK_TRY(S.code.alloc((size_t)n_sel + 1));
+    if (S.has_rows) {
+        SPK_TRY(S.l.alloc((size_t)n_sel + 1));
+        SPK_TRY(S.r.alloc((size_t)n_sel + 1));
+    }
+    return SPK_OK;
+}
+
 // The selection into S (a local of spk_select*: a failure on the way leaves the context without one).  tf: the staged
 // id arrays and tables of spk_select_tf* (the SPK_SEL_TF_MP terms are evaluated per pair, the others per pattern), or
 // null for spk_select.
@@ -489,14 +765,7 @@ static int build_selection(spk_ctx *ctx, double lambda, double one_minus, const 
         S.has_tf = true;
         S.n_tf = tf->n;
     }
-    S.K = K;
-    S.n_levels = ctx->n_levels;
-    S.stride = ctx->stride;
-    S.has_mp = m && u;
-    S.has_rows = ctx->pairs_valid && ctx->pl.p && ctx->pr.p && ctx->pl.n >= (size_t)P && ctx->pr.n >= (size_t)P;
-    S.pairs_epoch = ctx->pairs_epoch;
-    S.gamma_seq = ctx->gamma_seq;
-    S.fix_seq = ctx->codes_fix_seq;
+    selection_header(ctx, m && u, S);
     StageTimer T{ctx};
     const int64_t words64 = (n_pat + 63) / 64;
     DevBuf<unsigned long long> keep;
@@ -538,12 +807,7 @@ static int build_selection(spk_ctx *ctx, double lambda, double one_minus, const 
     const int64_t n_sel = chunks.total;
     SPK_REQUIRE(n_sel >= 0 && n_sel <= P, SPK_E_STATE, "spk_select: survivor count");
     // ---- the survivors
-    SPK_TRY(S.ord.alloc((size_t)n_sel + 1));
-    SPK_TRY(S.code.alloc((size_t)n_sel + 1));
-    if (S.has_rows) {
-        SPK_TRY(S.l.alloc((size_t)n_sel + 1));
-        SPK_TRY(S.r.alloc((size_t)n_sel + 1));
-    }
+    SPK_TRY(selection_alloc(S, n_sel));
     if (tf) {
         SPK_TRY(S.tf_mp.alloc((size_t)n_sel + 1));
         SPK_TRY(S.adj.alloc((size_t)n_sel * tf->n + 1));
@@ -561,6 +825,128 @@ static int build_selection(spk_ctx *ctx, double lambda, double one_minus, const 
         if (!tf) SPK_TRY(launch_select_codes<true>(ctx, A, lds));
         else if (ctx->code_bytes == 2) SPK_TRY(launch_tf_emit<uint16_t>(ctx, A, F, lds, tf_terms));
         else SPK_TRY(launch_tf_emit<uint32_t>(ctx, A, F, lds, tf_terms));
+        SPK_TRY(T.close());
+    }
+    S.n = n_sel;
+    S.ms = T.result();
+    S.valid = true;
+    return SPK_OK;
+}
+
+template <typename CodeT, int MODE>
+static int launch_sample(spk_ctx *ctx, const SmpArgs &A, bool lds) {
+    const int64_t cap = (MODE == SMP_HIST ? SMP_WG_PER_CU : SEL_WG_PER_CU) * (int64_t)ctx->n_cu;
+    const int64_t g = std::max<int64_t>(std::min<int64_t>((A.n_chunks + SEL_WAVES - 1) / SEL_WAVES, cap), 1);
+    // a workgroup's 32-bit LDS counters: the pairs its waves see
+    const int64_t per_wg = ((A.n_chunks + g * SEL_WAVES - 1) / (g * SEL_WAVES)) * SEL_WAVES * SEL_CHUNK;
+    SPK_REQUIRE(MODE != SMP_HIST || per_wg < ((int64_t)1 << 32), SPK_E_LIMIT, "spk_select_sample: too many pairs");
+    const size_t bytes = (MODE == SMP_HIST ? (size_t)A.n_strata * SMP_DIGITS * 4 : 0) + (lds ? (size_t)A.tab_words * 4 : 0);
+    if (lds) k_sample<CodeT, true, MODE><<<(unsigned)g, SEL_THREADS, bytes, ctx->stream>>>(A);
+    else k_sample<CodeT, false, MODE><<<(unsigned)g, SEL_THREADS, bytes, ctx->stream>>>(A);
+    SPK_HIP(hipGetLastError());
+    return SPK_OK;
+}
+
+template <int MODE>
+static int launch_sample_codes(spk_ctx *ctx, const SmpArgs &A, bool lds) {
+    return ctx->code_bytes == 2 ? launch_sample<uint16_t, MODE>(ctx, A, lds) : launch_sample<uint32_t, MODE>(ctx, A, lds);
+}
+
+// spk_select_sample's selection into S, and the strata's eligible and kept pairs into pop / kept [n_strata].  One host
+// round trip, build_selection's: the strata's counts come back with the scan's total.
+static int build_sample(spk_ctx *ctx, double lambda, double one_minus, const double *m, const double *u, int n_terms,
+                        const spk_select_term *terms, int n_strata, const double *edges, const int64_t *quota,
+                        uint64_t seed, Selection &S, std::vector<int64_t> &pop, std::vector<int64_t> &kept) {
+    const int64_t P = ctx->n_pairs, n_pat = ctx->n_patterns;
+    SelPatArgs PA{};
+    SmpPatArgs E{};
+    SmpPickArgs K{};
+    PA.K = ctx->K;
+    PA.n_pat = n_pat;
+    for (int k = 0; k < ctx->K; ++k) {
+        PA.stride[k] = (int32_t)ctx->stride[k];
+        PA.nlev[k] = (uint8_t)ctx->n_levels[k];
+    }
+    for (int t = 0; t < n_terms; ++t) PA.terms[PA.n_terms++] = terms[t];
+    E.n_strata = K.n_strata = n_strata;
+    for (int b = 0; b <= n_strata; ++b) E.edges[b] = edges[b];
+    for (int b = 0; b < n_strata; ++b) K.quota[b] = quota[b];
+    selection_header(ctx, true, S);
+    const int64_t hist_bytes = (int64_t)n_strata * SMP_DIGITS * 4, tab_bytes = (n_pat + 3) / 4 * 4;
+    const int64_t budget = std::min<int64_t>(SMP_LDS_BYTES, ctx->lds_per_block) - SMP_STATIC_BYTES;
+    SPK_REQUIRE(hist_bytes <= budget, SPK_E_LIMIT, "spk_select_sample: the strata's histogram exceeds the device's LDS");
+    const bool lds = hist_bytes + tab_bytes <= budget;
+    StageTimer T{ctx};
+    DevBuf<uint8_t> tab, tmp;
+    DevBuf<unsigned long long> hist, st;
+    CountScan chunks;
+    SPK_TRY(tab.alloc((size_t)tab_bytes + 4));
+    SPK_TRY(hist.alloc((size_t)n_strata * SMP_DIGITS));
+    SPK_TRY(st.alloc(ST_WORDS));
+    SPK_TRY(S.mpat.alloc((size_t)n_pat + 1));
+    const int64_t n_chunks = (P + SEL_CHUNK - 1) / SEL_CHUNK;
+    SPK_TRY(chunks.alloc(ctx, n_chunks));
+    K.hist = hist.p;
+    K.st = st.p;
+    // ---- per pattern: mp table, stratum; the strata's thresholds; per chunk: the kept pairs; their scan
+    SPK_TRY(T.open());
+    SPK_HIP(hipMemsetAsync(tab.p, SMP_NONE, (size_t)tab_bytes + 4, ctx->stream));
+    SPK_HIP(hipMemsetAsync(hist.p, 0, (size_t)n_strata * SMP_DIGITS * 8, ctx->stream));
+    SPK_HIP(hipMemsetAsync(st.p, 0, (size_t)ST_WORDS * 8, ctx->stream));
+    SPK_TRY(pattern_mp_table(ctx, lambda, one_minus, m, u, S.mpat.p));
+    if (n_pat > 0) {
+        k_sample_patterns<<<(unsigned)((n_pat + SEL_THREADS - 1) / SEL_THREADS), SEL_THREADS, 0, ctx->stream>>>(
+            PA, E, S.mpat.p, tab.p);
+        SPK_HIP(hipGetLastError());
+    }
+    SmpArgs A{};
+    A.codes = ctx->codes.p;
+    A.P = P;
+    A.n_chunks = n_chunks;
+    A.tab = tab.p;
+    A.n_pat = n_pat;
+    A.tab_words = (int)(tab_bytes / 4);
+    A.n_strata = n_strata;
+    A.seed_mix = smp_mix(seed);
+    A.st = st.p;
+    A.hist = hist.p;
+    A.pl = S.has_rows ? ctx->pl.p : nullptr;
+    A.pr = S.has_rows ? ctx->pr.p : nullptr;
+    for (int pass = 0; pass < SMP_PASSES; ++pass) {
+        A.pass = K.pass = pass;
+        if (n_chunks > 0) SPK_TRY(launch_sample_codes<SMP_HIST>(ctx, A, lds));
+        k_sample_pick<<<1, SEL_THREADS, 0, ctx->stream>>>(K);
+        SPK_HIP(hipGetLastError());
+    }
+    A.pass = 0;
+    if (n_chunks > 0) {
+        A.chunk_count = chunks.count.p;
+        SPK_TRY(launch_sample_codes<SMP_COUNT>(ctx, A, lds));
+    }
+    std::vector<unsigned long long> counts(2 * SMP_MAX);  // ST_POP and ST_KEPT are adjacent
+    SPK_HIP(hipMemcpyAsync(counts.data(), st.p + ST_POP, counts.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SPK_TRY(scan_total(ctx, chunks, tmp, &T));  // synchronises
+    const int64_t n_sel = chunks.total;
+    int64_t want = 0;
+    pop.assign(n_strata, 0);
+    kept.assign(n_strata, 0);
+    for (int b = 0; b < n_strata; ++b) {
+        pop[b] = (int64_t)counts[b];
+        kept[b] = (int64_t)counts[SMP_MAX + b];
+        want += kept[b];
+    }
+    SPK_REQUIRE(n_sel == want && n_sel <= P, SPK_E_STATE, "spk_select_sample: survivor count");
+    // ---- the survivors
+    SPK_TRY(selection_alloc(S, n_sel));
+    if (n_sel > 0) {
+        A.chunk_count = nullptr;
+        A.chunk_off = chunks.off.p;
+        A.out_ord = S.ord.p;
+        A.out_code = S.code.p;
+        A.out_l = S.l.p;
+        A.out_r = S.r.p;
+        SPK_TRY(T.open());
+        SPK_TRY(launch_sample_codes<SMP_EMIT>(ctx, A, lds));
         SPK_TRY(T.close());
     }
     S.n = n_sel;
@@ -655,6 +1041,47 @@ extern "C" int spk_select_tf_columns(spk_ctx *ctx, double lambda, double one_min
     SPK_TRY(build_selection(ctx, lambda, one_minus, m, u, n_terms, terms, &G.T, S));
     ctx->sel = std::move(S);
     if (out_n_selected) *out_n_selected = ctx->sel.n;
+    return SPK_OK;
+}
+
+extern "C" int spk_select_sample(spk_ctx *ctx, double lambda, double one_minus, const double *m, const double *u,
+                                 int n_terms, const spk_select_term *terms, int n_strata, const double *edges,
+                                 const int64_t *quota, uint64_t seed, int64_t *out_n_selected) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_select_sample: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    ctx->sel.clear();  // a failing call leaves no selection, and no figures for spk_select_sample_info
+    ctx->strata_pop.clear();
+    ctx->strata_kept.clear();
+    ctx->strata_ms = -1.0;
+    SPK_REQUIRE(n_strata >= 1 && n_strata <= SPK_SAMPLE_MAX_STRATA, SPK_E_INVALID,
+                "spk_select_sample: 1..SPK_SAMPLE_MAX_STRATA (64) strata");
+    SPK_REQUIRE(edges && quota, SPK_E_INVALID, "spk_select_sample: null arg");
+    for (int b = 0; b <= n_strata; ++b) {
+        SPK_REQUIRE(std::isfinite(edges[b]), SPK_E_INVALID, "spk_select_sample: an edge is not finite");
+        SPK_REQUIRE(b == 0 || edges[b - 1] < edges[b], SPK_E_INVALID, "spk_select_sample: edges not strictly ascending");
+    }
+    for (int b = 0; b < n_strata; ++b) SPK_REQUIRE(quota[b] >= 0, SPK_E_INVALID, "spk_select_sample: negative quota");
+    SPK_REQUIRE(m && u, SPK_E_INVALID, "spk_select_sample: m and u are required");
+    SPK_TRY(select_begin(ctx, "spk_select_sample", m, u, n_terms, terms, false));
+    Selection S;
+    std::vector<int64_t> pop, kept;
+    SPK_TRY(build_sample(ctx, lambda, one_minus, m, u, n_terms, terms, n_strata, edges, quota, seed, S, pop, kept));
+    ctx->sel = std::move(S);
+    ctx->strata_pop = std::move(pop);
+    ctx->strata_kept = std::move(kept);
+    ctx->strata_ms = ctx->sel.ms;
+    if (out_n_selected) *out_n_selected = ctx->sel.n;
+    return SPK_OK;
+}
+
+extern "C" int spk_select_sample_info(spk_ctx *ctx, int *out_n_strata, int64_t *out_population, int64_t *out_kept,
+                                      double *out_ms) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_select_sample_info: null ctx");
+    const size_t n = ctx->strata_pop.size();
+    if (out_n_strata) *out_n_strata = n ? (int)n : -1;
+    if (out_population) std::copy(ctx->strata_pop.begin(), ctx->strata_pop.end(), out_population);
+    if (out_kept) std::copy(ctx->strata_kept.begin(), ctx->strata_kept.end(), out_kept);
+    if (out_ms) *out_ms = n ? ctx->strata_ms : -1.0;
     return SPK_OK;
 }
 

@@ -458,6 +458,12 @@ class ExpectationFrame(SplinkDataFrame):
         f = FilteredFrame(self, Predicate()) if threshold is None else self.filter(f"match_probability > {threshold!r}")
         return f.best_matches(per=per, ties=ties)
 
+    def sample_pairs(self, per_stratum=200, strata=10, seed=0):
+        """A stratified random sample of this frame's pairs for clerical review, drawn on the device: shorthand for
+        the same call on the unfiltered FilteredFrame."""
+        from .select import Predicate
+        return FilteredFrame(self, Predicate()).sample_pairs(per_stratum=per_stratum, strata=strata, seed=seed)
+
     def label_counts(self, label_column):
         """GammaFrame.label_counts with the match_probability of every pattern under this frame's parameters."""
         return _label_counts(self.gammas, label_column, self.lam, self.level_probs)
@@ -603,6 +609,15 @@ class FilteredFrame(SplinkDataFrame):
         ties="first" keeps the pair that comes first in the frame, ties="all" every pair at the maximum."""
         return BestMatchFrame(self, per, ties, self._best_by[0] if by is None else by)
 
+    def sample_pairs(self, per_stratum=200, strata=10, seed=0):
+        """A stratified random sample of this frame's pairs for clerical review, drawn on the device
+        (spk_select_sample): a `SampleFrame`.  strata: that many equal-width bands of match_probability over [0, 1],
+        or the bands' edges (left-closed, the last one closed on both sides; a pair with a NULL score or one outside
+        the edges is never drawn).  per_stratum: the pairs to draw from every band, or one number per band; a band
+        with fewer pairs is taken whole.  The draw is without replacement and a function of `seed` and the pairs'
+        positions in the frame alone: the same seed with a larger per_stratum gives a superset."""
+        return SampleFrame(self, per_stratum, strata, seed)
+
     def _score_names(self):
         """The scores this frame's pairs carry, the default first."""
         return self._best_by
@@ -674,6 +689,11 @@ class BestMatchFrame(FilteredFrame):
 
     filter = where = best_matches = _refuse
 
+    def sample_pairs(self, *args, **kwargs):
+        raise ValueError("sample_pairs() on a best-match frame: the strata are those of the pairs' own "
+                         "match_probability, decided per comparison pattern before any narrowing (sample the filtered "
+                         "frame instead)")
+
     def _select(self):
         """Make the context's selection this frame's: the inner frame's selection (its own re-select rules: it
         selects again unless the context still holds its survivors), narrowed to the best pair per record."""
@@ -689,6 +709,73 @@ class BestMatchFrame(FilteredFrame):
         self._seq = job.codes_seq
         self._n = int(n)
         return self._n
+
+
+class SampleFrame(FilteredFrame):
+    """`filtered.sample_pairs(per_stratum, strata, seed)`: lazily drawn on the device.  The frame has the filtered
+    frame's columns and a subset of its rows, in its order, plus `stratum` (int32) and `sampling_weight` (float64: the
+    stratum's pairs / its sampled pairs, so a labelled sample weights back to the whole frame); strata() gives the
+    bands with their populations."""
+
+    def __init__(self, inner: FilteredFrame, per_stratum, strata, seed):
+        from .select import sample_args
+        self._edges, self._quota, self._seed = sample_args(per_stratum, strata, seed)
+        if inner._scored_parent() is None:
+            raise ValueError("sample_pairs: this frame has no match_probability to stratify the pairs by (it was "
+                             "filtered from an unscored frame): sample the frame run_expectation_step returns")
+        if inner.job.n_shards > 1:
+            raise ValueError("sample_pairs() on a sharded job: a stratum's pairs span the shards (sample every shard "
+                             "and merge the samples on the host)")
+        super().__init__(inner.parent, inner.predicate)
+        self.inner = inner
+        self.gammas = inner.gammas
+        self._pop = self._kept = None
+
+    def _column_order(self):
+        return self.inner._column_order() + ["stratum", "sampling_weight"]
+
+    def _refuse(self, *args, **kwargs):
+        raise ValueError("a sample frame takes no further filter(), best_matches(), clusters() or sample_pairs(): "
+                         "filter first, then sample (its rows are a random subset, and anything derived from them "
+                         "would describe the draw, not the linkage)")
+
+    filter = where = best_matches = clusters = clusters_at_thresholds = sample_pairs = _refuse
+
+    def _select(self):
+        """Make the context's selection this frame's, under the ownership rules of FilteredFrame._select."""
+        job, parent = self.job, self.parent
+        self.gammas.ensure_codes()
+        if self._n is not None and job.selection_owner is self and self._seq == job.codes_seq:
+            return self._n
+        m, u = job.flat_tables(parent.level_probs)
+        job.selection_owner = None  # the call drops the context's selection first, and leaves none if it fails
+        n = job.ctx.select_sample(float(parent.lam), float(1 - parent.lam), m, u, self.predicate.native_terms(),
+                                  self._edges, self._quota, self._seed)
+        _, self._pop, self._kept, _ = job.ctx.select_sample_info()
+        job.selection_owner = self
+        self._seq = job.codes_seq
+        self._n = int(n)
+        return self._n
+
+    def strata(self):
+        """One row per stratum: stratum, low, high (its edges), pairs (the frame's pairs in it), sampled."""
+        self.count()
+        n = len(self._quota)
+        return pd.DataFrame({"stratum": np.arange(n, dtype=np.int32), "low": np.array(self._edges[:-1]),
+                             "high": np.array(self._edges[1:]), "pairs": self._pop.astype(np.int64),
+                             "sampled": self._kept.astype(np.int64)})
+
+    def _extra_columns(self, n):
+        """stratum from the survivors' own match_probability and the call's edges (the doubles the device compared),
+        sampling_weight from the strata's counts."""
+        from .select import sample_strata
+        if n:
+            mp = self.job.ctx.select_copy(0, n, len(self.gammas.meta[0]), rows=False, gammas=False, mp=True)[4]
+        else:
+            mp = np.empty(0, dtype=np.float64)
+        b = sample_strata(mp, self._edges)
+        weight = self._pop[b].astype(np.float64) / self._kept[b].astype(np.float64)
+        return {"stratum": b.astype(np.int32), "sampling_weight": weight}
 
 
 COPY_NODES = 1 << 26  # labels per spk_components_copy

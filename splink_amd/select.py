@@ -9,8 +9,12 @@ ValueError naming what it met.
 """
 from __future__ import annotations
 
+import math
+import numbers
 from dataclasses import dataclass
 from typing import Sequence, Tuple
+
+import numpy as np
 
 from . import _native as N
 from . import sqlexpr as S
@@ -43,6 +47,62 @@ def best_match_args(per="l", ties="first", by="match_probability", allowed_by=("
     keep_ties = pick("ties", ties, BEST_TIES, tuple(BEST_TIES))
     field = pick("by", by, BEST_BY, tuple(b for b in BEST_BY if b in allowed_by))
     return field, mode, keep_ties
+
+
+SAMPLE_MAX_STRATA = N.SAMPLE_MAX_STRATA
+
+
+def _plain_int(x):
+    return isinstance(x, numbers.Integral) and not isinstance(x, bool)
+
+
+def sample_args(per_stratum=200, strata=10, seed=0):
+    """(edges, quota, seed) of spk_select_sample for sample_pairs(per_stratum=, strata=, seed=): `strata` is a number
+    of equal-width bins over [0, 1] or a sequence of finite, strictly ascending edges (1 to SAMPLE_MAX_STRATA
+    strata), `per_stratum` one non-negative int or one per stratum, `seed` an int in [0, 2**64).  Anything else raises
+    ValueError."""
+    if _plain_int(strata):
+        if not 1 <= strata <= SAMPLE_MAX_STRATA:
+            raise ValueError(f"sample_pairs: strata={strata!r}; 1 to {SAMPLE_MAX_STRATA} strata")
+        edges = [i / int(strata) for i in range(int(strata) + 1)]
+    else:
+        try:
+            edges = [float(e) for e in strata]
+        except (TypeError, ValueError):
+            raise ValueError(f"sample_pairs: strata={strata!r}; an int (equal-width bins over [0, 1]) or a sequence "
+                             "of edges") from None
+        if not 2 <= len(edges) <= SAMPLE_MAX_STRATA + 1:
+            raise ValueError(f"sample_pairs: {len(edges)} edges; 2 to {SAMPLE_MAX_STRATA + 1} edges (1 to "
+                             f"{SAMPLE_MAX_STRATA} strata)")
+        if not all(math.isfinite(e) for e in edges):
+            raise ValueError(f"sample_pairs: the edges must be finite, got {edges!r}")
+        if any(a >= b for a, b in zip(edges, edges[1:])):
+            raise ValueError(f"sample_pairs: the edges must be strictly ascending, got {edges!r}")
+    n = len(edges) - 1
+    if _plain_int(per_stratum):
+        quota = [int(per_stratum)] * n
+    else:
+        try:
+            quota = list(per_stratum)
+        except TypeError:
+            raise ValueError(f"sample_pairs: per_stratum={per_stratum!r}; an int or one int per stratum") from None
+        if not all(_plain_int(q) for q in quota):
+            raise ValueError(f"sample_pairs: per_stratum={per_stratum!r}; an int or one int per stratum")
+        if len(quota) != n:
+            raise ValueError(f"sample_pairs: {len(quota)} quotas for {n} strata")
+        quota = [int(q) for q in quota]
+    if any(q < 0 or q >= 1 << 63 for q in quota):
+        raise ValueError(f"sample_pairs: a quota is negative or too large, got {per_stratum!r}")
+    if not _plain_int(seed) or not 0 <= seed < 1 << 64:
+        raise ValueError(f"sample_pairs: seed={seed!r}; an int in [0, 2**64)")
+    return edges, quota, int(seed)
+
+
+def sample_strata(mp, edges):
+    """The stratum of every sampled pair's match_probability under the call's edges, as the device decides it: the
+    number of inner edges <= x (left-closed strata, the last one closed on the right as well).  Sampled pairs lie
+    inside the edges, so there is no "none" here."""
+    return np.searchsorted(np.asarray(edges[1:-1], dtype=np.float64), np.asarray(mp, dtype=np.float64), side="right")
 
 
 @dataclass(frozen=True)

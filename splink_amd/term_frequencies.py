@@ -163,6 +163,11 @@ class TfFilteredFrame(FilteredFrame):
     def _scored_parent(self):
         return self.parent.df_e
 
+    def sample_pairs(self, *args, **kwargs):
+        raise ValueError("sample_pairs() on a term-frequency frame: tf_adjusted_match_prob is decided per pair, and "
+                         "the strata are decided per comparison pattern (sample the frame "
+                         "run_expectation_step returns, on match_probability)")
+
     def _select(self):
         job, tf = self.job, self.parent
         self.gammas.ensure_codes()
