@@ -232,6 +232,19 @@ typedef struct {
 #define SPK_OP_OR 21
 #define SPK_OP_NOT 22
 #define SPK_OP_LEN 11       /* length(a) cmp t */
+/* The set / token measures of the reference's UDF jar (jars/scala-udf-similarity-0.0.6.jar, registered by name in
+ * tests/test_spark.py:44-56), over UTF-16 units as Java Strings; restated from the class files, parity unpinned (the
+ * jar is not executable where this was built).  A NULL operand makes either test NULL.
+ * jaccard_sim (uk/gov/moj/dash/linkage/JaccardSimilarity.call -> commons-text 1.4 JaccardSimilarity.apply): 0.0 if
+ * either string is empty, else Math.round(|A n B| / |A u B| * 100.0) / 100.0 over the sets of distinct units, fp64,
+ * round half up.
+ * cosine_distance (uk/gov/moj/dash/linkage/CosineDistance.call -> commons-text 1.4 CosineDistance.apply,
+ * RegexTokenizer, Counter, CosineSimilarity): tokens are the maximal runs of [A-Za-z0-9_]; 1.0 - dot / (sqrt(d1) *
+ * sqrt(d2)) over the per-token counts (cos = 0.0 when a text has no token), not short-cut for equal texts.  A blank
+ * text (empty or Character.isWhitespace units only) makes the reference's query throw; here the test is NULL (the one
+ * deliberate deviation). */
+#define SPK_OP_JACCARD 12   /* jaccard_sim(a, b) cmp t */
+#define SPK_OP_COSINE 13    /* cosine_distance(a, b) cmp t */
 
 #define SPK_CMP_EQ 0
 #define SPK_CMP_NE 1
@@ -432,6 +445,12 @@ int spk_jaro_winkler_sim(spk_ctx *ctx, int64_t n, const int64_t *l_offsets, cons
                          const int64_t *r_offsets, const uint8_t *r_utf8, double *out);
 int spk_levenshtein(spk_ctx *ctx, int64_t n, const int64_t *l_offsets, const uint8_t *l_utf8,
                     const int64_t *r_offsets, const uint8_t *r_utf8, double *out);
+/* The jar's jaccard_sim and cosine_distance (SPK_OP_JACCARD / SPK_OP_COSINE above state the semantics), same
+ * arguments.  spk_cosine_distance writes NaN for a pair with a blank text, where the reference throws. */
+int spk_jaccard_sim(spk_ctx *ctx, int64_t n, const int64_t *l_offsets, const uint8_t *l_utf8,
+                    const int64_t *r_offsets, const uint8_t *r_utf8, double *out);
+int spk_cosine_distance(spk_ctx *ctx, int64_t n, const int64_t *l_offsets, const uint8_t *l_utf8,
+                        const int64_t *r_offsets, const uint8_t *r_utf8, double *out);
 
 /* ---- EM (replaces run_expectation_step + run_maximisation_step's aggregate,
  *      expectation_step.py:25-221, maximisation_step.py:41-90) ------------------ */

@@ -58,7 +58,7 @@ COMPONENTS_MAX_PEERS = 64  # SPK_COMPONENTS_MAX_PEERS: label arrays per componen
 assert OPERAND_DTYPE.itemsize == 40 and INSTR_DTYPE.itemsize == 32 and PROGRAM_DTYPE.itemsize == 16
 
 OP = {"ISNULL": 1, "NOTNULL": 2, "STR_CMP": 3, "NUM_CMP": 4, "JW": 5, "LEV": 6, "LEVRATIO": 7, "ABSDIFF": 8,
-      "PERCDIFF": 9, "CONST": 10, "LEN": 11, "AND": 20, "OR": 21, "NOT": 22}
+      "PERCDIFF": 9, "CONST": 10, "LEN": 11, "JACCARD": 12, "COSINE": 13, "AND": 20, "OR": 21, "NOT": 22}
 CMP = {"=": 0, "==": 0, "!=": 1, "<>": 1, "<": 2, "<=": 3, ">": 4, ">=": 5}
 
 EXPORTS = [
@@ -68,6 +68,7 @@ EXPORTS = [
     "spk_pairs_count", "spk_pairs_copy", "spk_pairs_load", "spk_gammas", "spk_gammas_copy", "spk_gammas_load",
     "spk_n_patterns", "spk_gammas_deferred", "spk_em_histogram", "spk_em_finalize", "spk_em_iteration", "spk_score",
     "spk_tf_accumulate", "spk_tf_apply", "spk_jaro_winkler_sim", "spk_levenshtein", "spk_gammas_exact_counts",
+    "spk_jaccard_sim", "spk_cosine_distance",
     "spk_gammas_set_simple", "spk_gammas_exact_list", "spk_gammas_simple_count", "spk_em_set_lane_histogram", "spk_table_set_rank_null",
     "spk_gammas_view_regions", "spk_ctx_lds_per_block", "spk_ctx_memory", "spk_raw_utf8", "spk_raw_i64", "spk_key_build", "spk_rank_from_raw", "spk_cluster", "spk_table_add_raw_utf8",
     "spk_gammas_implied_pairs", "spk_tf_column_values", "spk_tf_accumulate_column", "spk_tf_apply_columns", "spk_tf_copy", "spk_tf_set_mode",
@@ -1252,6 +1253,14 @@ class Context:
 
     def levenshtein(self, left, right):
         return self._udf("spk_levenshtein", left, right)
+
+    def jaccard_sim(self, left, right):
+        """The jar's jaccard_sim per pair (fp64, two decimals)."""
+        return self._udf("spk_jaccard_sim", left, right)
+
+    def cosine_distance(self, left, right):
+        """The jar's cosine_distance per pair (fp64); NaN where a text is blank (the reference's query fails there)."""
+        return self._udf("spk_cosine_distance", left, right)
 
     def tf_accumulate(self, n_values, ids0, ids1):
         ids0 = np.ascontiguousarray(ids0, dtype=np.int64)

@@ -3,6 +3,7 @@
 * Comparison columns: each completed `case_expression` (a CASE over `<col>_l` / `<col>_r`,
   case_statements.py:62-277 or user-written) becomes a column program: WHEN branches whose
   predicates are RPN sequences of leaf tests (IS NULL, =, jaro_winkler_sim(..) cmp t,
+  jaccard_sim(..) cmp t, cosine_distance(..) cmp t,
   levenshtein(..)/((length(..)+length(..))/2) cmp t, abs(a-b) cmp t, abs(a-b)/abs(max) cmp t,
   substr / ifnull operands) combined with Kleene AND / OR / NOT.  An operand may be a Spark built-in
   over ONE record's columns (lower / upper / trim / ltrim / rtrim / concat / concat_ws / cast, nested,
@@ -262,6 +263,9 @@ class _ProgramBuilder:
         if kind == "jw":
             a, b = self.operand(v[1], "str"), self.operand(v[2], "str")
             self.emit("JW", self._op(a), self._op(b), op, t=t)
+        elif kind in ("jaccard", "cosine"):
+            a, b = self.operand(v[1], "str"), self.operand(v[2], "str")
+            self.emit(kind.upper(), self._op(a), self._op(b), op, t=t)
         elif kind in ("lev", "levratio"):
             a, b = self.operand(v[1], "str"), self.operand(v[2], "str")
             self.emit("LEV" if kind == "lev" else "LEVRATIO", self._op(a), self._op(b), op, t=t)
@@ -322,10 +326,12 @@ def _strip_abs_diff(node):
 
 
 def _classify(node):
-    """('jw'|'lev'|'levratio'|'len'|'absdiff'|'percdiff', ...) or ('operand',)."""
+    """('jw'|'jaccard'|'cosine'|'lev'|'levratio'|'len'|'absdiff'|'percdiff', ...) or ('operand',)."""
     if isinstance(node, Func):
         if node.name == "jaro_winkler_sim" and len(node.args) == 2:
             return ("jw", node.args[0], node.args[1])
+        if node.name in ("jaccard_sim", "cosine_distance") and len(node.args) == 2:
+            return ("jaccard" if node.name == "jaccard_sim" else "cosine", node.args[0], node.args[1])
         if node.name == "levenshtein" and len(node.args) == 2:
             return ("lev", node.args[0], node.args[1])
         if node.name in ("length", "char_length", "character_length") and len(node.args) == 1:

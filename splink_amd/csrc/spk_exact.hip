@@ -326,9 +326,9 @@ __global__ __launch_bounds__(CL_THREADS) void k_compact_lev(GammaArgs A, int k, 
     for (int64_t i = kept + threadIdx.x; i < n; i += CL_THREADS) dst[i] = -1;
 }
 
-// Exact pass over column k through the interpreter.
-__global__ __launch_bounds__(X_THREADS) void k_gamma_exact(GammaArgs A, int k, const int32_t *xlist,
-                                                            const int64_t *xinfo) {
+// Exact pass over column k through the interpreter.  SET: eval_pred's (spk_interp.h).
+template <bool SET>
+__device__ __forceinline__ void gamma_exact_body(const GammaArgs &A, int k, const int32_t *xlist, const int64_t *xinfo) {
     const int64_t n = exact_count(A, xinfo, k);
     const int32_t *items = xlist + xinfo[k];
     const int64_t stride = (int64_t)gridDim.x * X_THREADS;
@@ -339,12 +339,20 @@ __global__ __launch_bounds__(X_THREADS) void k_gamma_exact(GammaArgs A, int k, c
         if (i < n) {
             p = items[i];
             int level = 0;
-            const int st = eval_column<M_EXACT>(A, k, A.pl[p], A.pr[p], level);
+            const int st = eval_column<M_EXACT, SET>(A, k, A.pl[p], A.pr[p], level);
             if (st == ST_DONE) code_add(A, p, (uint32_t)(level + 1) * (uint32_t)A.stride[k]);
             else to_slow = true;
         }
         wave_append(A.slow + A.slow_off[k], A.slow_count + k, to_slow, p);
     }
+}
+__global__ __launch_bounds__(X_THREADS) void k_gamma_exact(GammaArgs A, int k, const int32_t *xlist,
+                                                            const int64_t *xinfo) {
+    gamma_exact_body<false>(A, k, xlist, xinfo);
+}
+__global__ __launch_bounds__(X_THREADS) void k_gamma_exact_set(GammaArgs A, int k, const int32_t *xlist,
+                                                                const int64_t *xinfo) {
+    gamma_exact_body<true>(A, k, xlist, xinfo);
 }
 
 // Per len_l + len_r (S < S_MAX): the scan's cut and each test's largest passing distance for unequal strings
@@ -1202,7 +1210,8 @@ __global__ __launch_bounds__(X_THREADS, NP == 8 ? 3 : LEVQ_WAVES) void k_lev_ref
 // Global-memory pass over column k's slow list (length on the device; usually empty).  Cells with a
 // string past SLOW_LIMIT units go on to the huge pass: their list (counter slow_count[2K + k]) takes
 // column k's exact-list region, free once the exact pass ran and at least as long as the slow list.
-__global__ __launch_bounds__(64) void k_gamma_slow(GammaArgs A, ColSet cs, int32_t *xlist, const int64_t *xinfo) {
+template <bool SET>
+__device__ __forceinline__ void gamma_slow_body(const GammaArgs &A, const ColSet &cs, int32_t *xlist, const int64_t *xinfo) {
     const int k = cs.k[blockIdx.y];
     const int64_t n = A.slow_count[k];
     const int32_t *items = A.slow + A.slow_off[k];
@@ -1210,24 +1219,37 @@ __global__ __launch_bounds__(64) void k_gamma_slow(GammaArgs A, ColSet cs, int32
     for (int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 64) {
         const int32_t p = items[i];
         int level = 0;
-        const bool done = eval_column<M_SLOW>(A, k, A.pl[p], A.pr[p], level) == ST_DONE;
+        const bool done = eval_column<M_SLOW, SET>(A, k, A.pl[p], A.pr[p], level) == ST_DONE;
         // several columns in one launch (the fused JW lists) can hold the same pair: their adds to its code race
         if (done && cs.n > 1) code_add_atomic(A, p, (uint32_t)(level + 1) * (uint32_t)A.stride[k]);
         else if (done) code_add(A, p, (uint32_t)(level + 1) * (uint32_t)A.stride[k]);
         wave_append(huge, A.slow_count + 2 * A.K + k, !done, p);
     }
 }
+__global__ __launch_bounds__(64) void k_gamma_slow(GammaArgs A, ColSet cs, int32_t *xlist, const int64_t *xinfo) {
+    gamma_slow_body<false>(A, cs, xlist, xinfo);
+}
+__global__ __launch_bounds__(64) void k_gamma_slow_set(GammaArgs A, ColSet cs, int32_t *xlist, const int64_t *xinfo) {
+    gamma_slow_body<true>(A, cs, xlist, xinfo);
+}
 
 // Huge pass: cells with a string longer than SLOW_LIMIT units, one lane per cell, DP rows and flag
 // words in device scratch sized by the host to the longest string the column's program can meet.
-__global__ __launch_bounds__(64) void k_gamma_huge(GammaArgs A, int k, const int32_t *items, int64_t n, Scratch S) {
+template <bool SET>
+__device__ __forceinline__ void gamma_huge_body(const GammaArgs &A, int k, const int32_t *items, int64_t n, Scratch &S) {
     S.slot = (int64_t)blockIdx.x * 64 + threadIdx.x;
     for (int64_t i = S.slot; i < n; i += S.n_slots) {
         const int32_t p = items[i];
         int level = 0;
-        eval_column<M_HUGE>(A, k, A.pl[p], A.pr[p], level, S);
+        eval_column<M_HUGE, SET>(A, k, A.pl[p], A.pr[p], level, S);
         code_add(A, p, (uint32_t)(level + 1) * (uint32_t)A.stride[k]);
     }
+}
+__global__ __launch_bounds__(64) void k_gamma_huge(GammaArgs A, int k, const int32_t *items, int64_t n, Scratch S) {
+    gamma_huge_body<false>(A, k, items, n, S);
+}
+__global__ __launch_bounds__(64) void k_gamma_huge_set(GammaArgs A, int k, const int32_t *items, int64_t n, Scratch S) {
+    gamma_huge_body<true>(A, k, items, n, S);
 }
 
 // Slow list of a Levenshtein template column: cells whose rows are Latin-1 and at most
@@ -1362,13 +1384,13 @@ __global__ __launch_bounds__(64) void k_gamma_rest(GammaArgs A, int k, const int
 
 // ---- launch logic (host) -----------------------------------------------------------------------------
 // Device scratch of a huge pass over `cells` cells whose strings have at most `units` UTF-16 units: a
-// slot per lane (JW: two flag-word arrays; Levenshtein: code points + one DP row), lanes = one per
-// cell, at most ~1 GiB of slots, at least one wave.
+// slot per lane (JW: two flag-word arrays; Levenshtein: code points + one DP row; jaccard_sim: two
+// presence bitmaps over the unit values), lanes = one per cell, at most ~1 GiB of slots, at least one wave.
 int huge_scratch(int64_t units, int64_t cells, DevBuf<uint8_t> &buf, Scratch &S) {
     SPK_REQUIRE(units < INT32_MAX / 2, SPK_E_LIMIT, "a compared string is longer than 2^30 UTF-16 units");
     S.units = (int32_t)units;
     S.words = (int32_t)((units + 63) / 64);
-    const int64_t slot_bytes = std::max<int64_t>(16 * (int64_t)S.words, 4 * (2 * units + 1));
+    const int64_t slot_bytes = std::max<int64_t>({16 * (int64_t)S.words, 4 * (2 * units + 1), 16 * (int64_t)JACCARD_WORDS});
     const int64_t budget = std::max<int64_t>(64, ((int64_t)1 << 30) / slot_bytes / 64 * 64);
     S.n_slots = std::min<int64_t>(budget, (cells + 63) / 64 * 64);
     SPK_TRY(buf.alloc((size_t)(S.n_slots * slot_bytes)));
@@ -1538,8 +1560,14 @@ int enqueue_phase(spk_ctx *ctx, Slot &S, int64_t cap, bool skip) {
             if (quiet(k)) G.slow_skipped[k] = 1;
             else SPK_TRY(enqueue_slow(ctx, S, k, nullptr));
         } else {
-            k_gamma_exact<<<(unsigned)G.g_exact, X_THREADS, 0, S.stream>>>(A, k, S.xlist.p, S.xinfo.p);
-            k_gamma_slow<<<(unsigned)(4 * ctx->n_cu), 64, 0, S.stream>>>(A, one_k, S.xlist.p, S.xinfo.p);
+            // an interpreter column: the instantiations with jaccard_sim / cosine_distance only where it names them
+            if (C.setsim[k]) {
+                k_gamma_exact_set<<<(unsigned)G.g_exact, X_THREADS, 0, S.stream>>>(A, k, S.xlist.p, S.xinfo.p);
+                k_gamma_slow_set<<<(unsigned)(4 * ctx->n_cu), 64, 0, S.stream>>>(A, one_k, S.xlist.p, S.xinfo.p);
+            } else {
+                k_gamma_exact<<<(unsigned)G.g_exact, X_THREADS, 0, S.stream>>>(A, k, S.xlist.p, S.xinfo.p);
+                k_gamma_slow<<<(unsigned)(4 * ctx->n_cu), 64, 0, S.stream>>>(A, one_k, S.xlist.p, S.xinfo.p);
+            }
         }
     }
     SPK_HIP(hipGetLastError());
@@ -1559,7 +1587,8 @@ int run_huge(spk_ctx *ctx, Slot &S, const unsigned int *n_huge) {
     for (int k = 0; k < C.K; ++k) {
         if (!n_huge[k]) continue;
         const int32_t *items = (C.huge_in_slow[k] ? G.A.slow : S.xlist.p) + S.h_info.p[k];
-        k_gamma_huge<<<(unsigned)(Sc.n_slots / 64), 64, 0, S.stream>>>(G.A, k, items, n_huge[k], Sc);
+        if (C.setsim[k]) k_gamma_huge_set<<<(unsigned)(Sc.n_slots / 64), 64, 0, S.stream>>>(G.A, k, items, n_huge[k], Sc);
+        else k_gamma_huge<<<(unsigned)(Sc.n_slots / 64), 64, 0, S.stream>>>(G.A, k, items, n_huge[k], Sc);
         SPK_HIP(hipGetLastError());
     }
     SPK_HIP(hipStreamSynchronize(S.stream));  // the scratch lives until here

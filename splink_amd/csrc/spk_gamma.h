@@ -323,6 +323,7 @@ struct GammaCols {
     std::vector<SimpleCol> simple;
     std::vector<int> simple_of;
     std::vector<char> may_exact, huge_in_slow, free_text, bag;
+    std::vector<char> setsim;  // the column's program names jaccard_sim / cosine_distance (spk_interp.h eval_pred SET)
     int K = 0, n_info = 0, n_cnt = 0, n_all = 0;
     int64_t max_units = 1;
 };

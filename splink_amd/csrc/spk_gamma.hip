@@ -820,6 +820,11 @@ static int plan_columns(spk_ctx *ctx, const Program &p, const Literals &lits, Ta
         C.bag[sc.k] = (C.free_text[sc.k] && sc.cls == SC_LEV && a->bag.n && b->bag.n && ctx->lev_bag) ? 1 : 0;
         out->long_exact = out->long_exact || (sc.cls == SC_LEV && C.free_text[sc.k]);
     }
+    C.setsim.assign(K, 0);
+    for (int k = 0; k < K; ++k)
+        for (int w = p.cols[k].first_when; w < p.cols[k].first_when + p.cols[k].n_when; ++w)
+            for (int i = p.when_first_instr[w]; i < p.when_first_instr[w] + p.when_n_instr[w]; ++i)
+                if (p.instr[i].op == SPK_OP_JACCARD || p.instr[i].op == SPK_OP_COSINE) C.setsim[k] = 1;
     C.huge_in_slow.assign(K, 0);  // column k's huge list: slow-list region (Levenshtein) or exact-list region
     for (int k = 0; k < K; ++k)
         C.huge_in_slow[k] = (C.may_exact[k] && C.simple_of[k] >= 0 && simple[C.simple_of[k]].cls == SC_LEV) ? 1 : 0;

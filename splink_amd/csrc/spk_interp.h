@@ -107,14 +107,32 @@ __device__ inline int str_order(const StrView &a, const StrView &b) {
     return 0;
 }
 
+// The last fp64 value (jaro_winkler_sim, jaccard_sim or cosine_distance: the key carries the function above
+// the operand pair) and the last Levenshtein distance of a column, so several WHENs over one operand pair
+// compute each once.
 struct Memo {
     int jw_key, lev_key;
     double jw;
     int lev;
 };
 
-// One WHEN predicate.  Sets *slow when the exact pass needs the global-memory pass.
+// jaccard_sim(a, b) / cosine_distance(a, b) of two non-NULL strings in global memory (NaN: a blank text under
+// cosine_distance).  S: the huge pass's scratch (two presence bitmaps for jaccard_sim), unused otherwise.
 template <int MODE>
+__device__ inline double setsim_value(int op, const StrView &a, const StrView &b, const Scratch &S) {
+    const GlbAcc ga{a.p}, gb{b.p};
+    if (op == SPK_OP_COSINE) return cosine_tokens(ga, a.n, gb, b.n);
+    if (MODE == M_HUGE)
+        return jaccard_bitmap(ga, a.n, gb, b.n, S.at<uint64_t>(0), S.at<uint64_t>(JACCARD_WORDS));
+    return jaccard_units(ga, a.n, gb, b.n);
+}
+
+// One WHEN predicate.  Sets *slow when the exact pass needs the global-memory pass.
+// SET: the instantiation evaluates jaccard_sim / cosine_distance.  The exact, slow and huge kernels exist in
+// both forms, and a column whose program names neither function (GammaCols.setsim) runs the form without, which
+// keeps the register and private-segment budget it had before these functions existed (profiles/ab_setsim.log);
+// there the opcodes are an error like any unknown one.  The filter pass has one form: it only bounds them.
+template <int MODE, bool SET = MODE == M_FILTER>
 __device__ int eval_pred(const GammaArgs &A, int first, int count, int32_t x, int32_t y, Memo &mm,
                          bool *slow, const Scratch &S) {
     uint32_t st = 0;  // stack of truth values, 2 bits per entry
@@ -213,6 +231,35 @@ __device__ int eval_pred(const GammaArgs &A, int first, int count, int32_t x, in
                 r = cmpd(mm.jw, in.t, in.cmp);
                 break;
             }
+            case SPK_OP_JACCARD:
+            case SPK_OP_COSINE: {
+                if (!SET) { atomicOr(A.err, 2); r = KN; break; }
+                StrView a = get_str(A, A.ops[in.a], x, y), b = get_str(A, A.ops[in.b], x, y);
+                if (a.null || b.null) { r = KN; break; }
+                const int key = ((in.op - SPK_OP_JACCARD + 1) << 24) + in.a * 4096 + in.b;
+                if (mm.jw_key != key) {
+                    double v;
+                    if (in.op == SPK_OP_JACCARD && a.n == b.n && units_equal(a, b)) {
+                        v = a.n > 0 ? 1.0 : 0.0;  // A = B: Math.round(1.0 * 100.0) / 100.0; two empty strings: 0.0
+                    } else if (MODE == M_FILTER) {
+                        // the function's range alone: jaccard_sim in [0, 1]; cosine_distance = 1 - cos with cos in
+                        // [0, 1] up to rounding, once a first unit that is no whitespace shows neither text is blank
+                        if (in.op == SPK_OP_JACCARD) r = decide(0.0, 1.0, in.cmp, in.t);
+                        else if (a.n > 0 && b.n > 0 && !whitespace_unit(a.p[0]) && !whitespace_unit(b.p[0]))
+                            r = decide(-1e-9, 1.0 + 1e-9, in.cmp, in.t);
+                        else r = KU;
+                        break;
+                    } else {
+                        const int lim = MODE == M_SLOW ? SLOW_LIMIT : MAXU;
+                        if (MODE != M_HUGE && (a.n > lim || b.n > lim)) { *slow = true; return KN; }
+                        v = setsim_value<MODE>(in.op, a, b, S);
+                    }
+                    mm.jw = v;
+                    mm.jw_key = key;
+                }
+                r = mm.jw != mm.jw ? KN : cmpd(mm.jw, in.t, in.cmp);
+                break;
+            }
             case SPK_OP_LEV:
             case SPK_OP_LEVRATIO: {
                 StrView a = get_str(A, A.ops[in.a], x, y), b = get_str(A, A.ops[in.b], x, y);
@@ -252,7 +299,7 @@ __device__ int eval_pred(const GammaArgs &A, int first, int count, int32_t x, in
     return (int)(st & 3);
 }
 
-template <int MODE>
+template <int MODE, bool SET = MODE == M_FILTER>
 __device__ int eval_column(const GammaArgs &A, int k, int32_t x, int32_t y, int &level,
                            const Scratch &S = Scratch{}) {
     const spk_column_program prog = A.progs[k];
@@ -260,7 +307,7 @@ __device__ int eval_column(const GammaArgs &A, int k, int32_t x, int32_t y, int 
     for (int w = 0; w < prog.n_when; ++w) {
         const int wi = prog.first_when + w;
         bool slow = false;
-        const int r = eval_pred<MODE>(A, A.when_first[wi], A.when_n[wi], x, y, mm, &slow, S);
+        const int r = eval_pred<MODE, SET>(A, A.when_first[wi], A.when_n[wi], x, y, mm, &slow, S);
         if (slow) return ST_NEEDS_SLOW;
         if (r == KU) return ST_UNDECIDED;
         if (r == KT) {

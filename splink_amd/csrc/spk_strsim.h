@@ -1072,4 +1072,171 @@ __device__ inline int lev_exact(const StrView &a, const StrView &b, int cut = 1 
     return lev_myers(GlbAcc{a.p + pre}, la, GlbAcc{b.p + pre}, lb);
 }
 
+// ---- jaccard_sim / cosine_distance (the jar's set and token measures) ----------
+// Both are restated from the class files (parity unpinned: the jar is not executable here); every
+// step is fp64 in the reference's operation order.
+
+// Math.round(x * 100.0) / 100.0 for x = inter / uni: round half up without floor(v + 0.5), which
+// differs from Java's Math.round at 0.49999999999999994.
+__device__ inline double jaccard_finish(int inter, int uni) {
+    const double x = (double)inter / (double)uni;
+    const double v = x * 100.0;
+    double r = floor(v);
+    if (v - r >= 0.5) r += 1.0;
+    return r / 100.0;
+}
+
+// commons-text 1.4 JaccardSimilarity.calculateJaccardSimilarity over UTF-16 units: |A ∩ B| / |A ∪ B| of
+// the sets of distinct units, 0.0 when either string is empty.  First-occurrence scans, no storage:
+// O(na² + na·nb + nb²) unit reads, from LDS slots or global memory.
+template <class AccA, class AccB>
+__device__ double jaccard_units(AccA a, int na, AccB b, int nb) {
+    if (na == 0 || nb == 0) return 0.0;
+    int ca = 0, cb = 0, inter = 0;
+    for (int i = 0; i < na; ++i) {
+        const uint16_t c = a[i];
+        int j = 0;
+        while (j < i && a[j] != c) ++j;
+        if (j < i) continue;  // seen before
+        ++ca;
+        j = 0;
+        while (j < nb && b[j] != c) ++j;
+        inter += j < nb ? 1 : 0;
+    }
+    for (int i = 0; i < nb; ++i) {
+        const uint16_t c = b[i];
+        int j = 0;
+        while (j < i && b[j] != c) ++j;
+        cb += j == i ? 1 : 0;
+    }
+    return jaccard_finish(inter, ca + cb - inter);
+}
+
+// The same for any length: one presence bitmap per string over the 65536 unit values, in caller storage
+// (JACCARD_WORDS words each: the huge pass's device scratch).  O(na + nb).
+constexpr int JACCARD_WORDS = 65536 / 64;
+template <class Words>
+__device__ inline double jaccard_bitmap(GlbAcc a, int na, GlbAcc b, int nb, Words in_a, Words in_b) {
+    if (na == 0 || nb == 0) return 0.0;
+    for (int i = 0; i < JACCARD_WORDS; ++i) {
+        in_a[i] = 0;
+        in_b[i] = 0;
+    }
+    int ca = 0, cb = 0, inter = 0;
+    for (int i = 0; i < na; ++i) {
+        const uint32_t c = a[i];
+        const uint64_t bit = 1ull << (c & 63), w = in_a[c >> 6];
+        ca += (w & bit) ? 0 : 1;
+        in_a[c >> 6] = w | bit;
+    }
+    for (int i = 0; i < nb; ++i) {
+        const uint32_t c = b[i];
+        const uint64_t bit = 1ull << (c & 63), w = in_b[c >> 6];
+        if (!(w & bit)) {
+            in_b[c >> 6] = w | bit;
+            ++cb;
+            inter += (in_a[c >> 6] & bit) ? 1 : 0;
+        }
+    }
+    return jaccard_finish(inter, ca + cb - inter);
+}
+
+// java.util.regex \w without UNICODE_CHARACTER_CLASS: [A-Za-z0-9_]
+__device__ inline bool word_unit(uint32_t c) {
+    return (c - 'a' < 26u) || (c - 'A' < 26u) || (c - '0' < 10u) || c == '_';
+}
+
+// Character.isWhitespace over one UTF-16 unit (every such character is in the BMP)
+__device__ inline bool whitespace_unit(uint32_t c) {
+    return (c >= 9 && c <= 13) || (c >= 28 && c <= 32) || c == 0x1680 || (c >= 0x2000 && c <= 0x2006) ||
+           (c >= 0x2008 && c <= 0x200A) || c == 0x2028 || c == 0x2029 || c == 0x205F || c == 0x3000;
+}
+
+// StringUtils.isBlank: empty or whitespace only (commons-text CosineDistance throws on such a text)
+template <class Acc>
+__device__ inline bool text_blank(Acc s, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!whitespace_unit(s[i])) return false;
+    return true;
+}
+
+// The token (maximal run of word units) that starts at or after `pos`: its start in *ts and its length
+// as the result, 0 when there is none.
+template <class Acc>
+__device__ inline int next_token(Acc s, int n, int pos, int *ts) {
+    while (pos < n && !word_unit(s[pos])) ++pos;
+    int e = pos;
+    while (e < n && word_unit(s[e])) ++e;
+    *ts = pos;
+    return e - pos;
+}
+
+template <class AccX, class AccY>
+__device__ inline bool token_equal(AccX x, int xs, AccY y, int ys, int len) {
+    for (int i = 0; i < len; ++i)
+        if (x[xs + i] != y[ys + i]) return false;
+    return true;
+}
+
+// Occurrences in y of the token x[xs, xs + len).
+template <class AccX, class AccY>
+__device__ inline int token_count(AccX x, int xs, int len, AccY y, int ny) {
+    int cnt = 0, ys = 0;
+    for (int pos = 0;;) {
+        const int l = next_token(y, ny, pos, &ys);
+        if (l == 0) return cnt;
+        cnt += (l == len && token_equal(x, xs, y, ys, len)) ? 1 : 0;
+        pos = ys + l;
+    }
+}
+
+// Occurrences of the token s[ts, ts + len) in its own string s when it is the first of them, else 0.
+template <class Acc>
+__device__ inline int token_count_first(Acc s, int n, int ts, int len) {
+    int cnt = 0, ys = 0;
+    for (int pos = 0;;) {
+        const int l = next_token(s, n, pos, &ys);
+        if (l == 0) return cnt;
+        if (l == len && token_equal(s, ts, s, ys, len)) {
+            if (ys < ts) return 0;
+            ++cnt;
+        }
+        pos = ys + l;
+    }
+}
+
+// commons-text 1.4 CosineDistance.apply: tokens are the maximal runs of [A-Za-z0-9_] (RegexTokenizer
+// "(\w)+"), counted per text (Counter.of); dot = Σ over the tokens of both of cA·cB (a long), d1 = Σ cA²,
+// d2 = Σ cB² (exact in fp64); cos = dot / (sqrt(d1)·sqrt(d2)), 0.0 when a text has no token; the result
+// is 1.0 - cos, with no shortcut for equal texts (the reference returns ±2.2e-16 there).  A blank text
+// (the reference throws IllegalArgumentException) gives NaN.  The tokens are not stored: each distinct
+// token of a text is counted by walking both texts again, O(tokens · units) reads and no scratch at any
+// length, so the interpreter's instantiations hold no token lists.
+template <class AccA, class AccB>
+__device__ double cosine_tokens(AccA a, int na, AccB b, int nb) {
+    if (text_blank(a, na) || text_blank(b, nb)) return __builtin_nan("");
+    long long dot = 0, s1 = 0, s2 = 0;
+    int ts = 0;
+    for (int pos = 0;;) {
+        const int l = next_token(a, na, pos, &ts);
+        if (l == 0) break;
+        const long long ca = token_count_first(a, na, ts, l);
+        if (ca) {
+            s1 += ca * ca;
+            dot += ca * (long long)token_count(a, ts, l, b, nb);
+        }
+        pos = ts + l;
+    }
+    for (int pos = 0;;) {
+        const int l = next_token(b, nb, pos, &ts);
+        if (l == 0) break;
+        const long long cb = token_count_first(b, nb, ts, l);
+        s2 += cb * cb;
+        pos = ts + l;
+    }
+    const double d1 = (double)s1, d2 = (double)s2;
+    const double cos = (d1 <= 0.0 || d2 <= 0.0) ? 0.0 : (double)dot / (sqrt(d1) * sqrt(d2));
+    return 1.0 - cos;
+}
+
 }  // namespace spk

@@ -48,8 +48,11 @@ try:
 except ImportError:  # pragma: no cover
     pa = pc = None
 
+# the UDF jar's q-gram tokenisers (QgramTokeniser = Q2gramTokeniser; the parser lower-cases function names) -> q
+QGRAM_FUNCS = {"qgramtokeniser": 2, "q2gramtokeniser": 2, "q3gramtokeniser": 3, "q4gramtokeniser": 4,
+               "q5gramtokeniser": 5, "q6gramtokeniser": 6}
 STR_FUNCS = ("lower", "lcase", "upper", "ucase", "trim", "ltrim", "rtrim", "concat", "concat_ws", "soundex",
-             "regexp_replace", "regexp_extract")
+             "regexp_replace", "regexp_extract") + tuple(QGRAM_FUNCS)
 # date functions of one record: their values are dates, kept on the device as numbers (days since 1970-01-01)
 DATE_FUNCS = ("to_date", "date_add", "date_sub", "datediff")
 CAST_TYPES = {"string": "str", "varchar": "str", "int": "int", "integer": "int", "bigint": "long",
@@ -168,6 +171,8 @@ def check_args(n: Func):
         raise ValueError("datediff() takes two dates")
     elif n.name in ("to_date", "soundex") and len(n.args) != 1:
         raise ValueError(f"{n.name}() takes one argument (to_date with a format is not supported)")
+    elif n.name in QGRAM_FUNCS and len(n.args) != 1:
+        raise ValueError(f"{n.name}() takes one argument")
 
 
 # ---- Spark semantics: soundex, regular expressions, dates ---------------------------------------------
@@ -200,6 +205,34 @@ def spark_soundex(s: str) -> str:
                 break
         last = code
     return "".join(sx).ljust(4, "0")
+
+
+def qgram_tokenise(s: str, q: int) -> str:
+    """The jar's QgramTokeniser / Q<q>gramTokeniser (`new StringOps(x).sliding(q).toList.mkString(" ")`, restated
+    from the class files; parity unpinned): the windows of q UTF-16 units joined by one space -- '' for the empty
+    string, the whole string when it has at most q units.  A window that splits a surrogate pair leaves an unpaired
+    surrogate, which Spark's UTF-8 encoding of the result writes as '?'."""
+    b = s.encode("utf-16-le", "surrogatepass")
+    units = [b[i] | (b[i + 1] << 8) for i in range(0, len(b), 2)]
+    n = len(units)
+    if n == 0:
+        return ""
+
+    def text(w):
+        out, i = [], 0
+        while i < len(w):
+            u = w[i]
+            if 0xD800 <= u < 0xDC00 and i + 1 < len(w) and 0xDC00 <= w[i + 1] < 0xE000:
+                out.append(chr(0x10000 + ((u - 0xD800) << 10) + (w[i + 1] - 0xDC00)))
+                i += 2
+                continue
+            out.append("?" if 0xD800 <= u < 0xE000 else chr(u))
+            i += 1
+        return "".join(out)
+
+    if n <= q:
+        return text(units)
+    return " ".join(text(units[i:i + q]) for i in range(n - q + 1))
 
 
 _REGEX_CACHE: Dict[str, "re.Pattern"] = {}
@@ -512,6 +545,8 @@ def eval_row(node, row) -> object:
         return s.rstrip(" ")
     if name == "soundex":
         return spark_soundex(s)
+    if name in QGRAM_FUNCS:
+        return qgram_tokenise(s, QGRAM_FUNCS[name])
     raise ValueError(f"unsupported function {name}()")
 
 

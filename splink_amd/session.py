@@ -12,7 +12,8 @@ from .engine import default_device
 
 Function = namedtuple("Function", ["name", "description", "className", "isTemporary"])
 
-NATIVE_FUNCTIONS = ("jaro_winkler_sim", "levenshtein", "length", "substr", "ifnull", "abs")
+NATIVE_FUNCTIONS = ("jaro_winkler_sim", "jaccard_sim", "cosine_distance", "levenshtein", "length", "substr", "ifnull",
+                    "abs")
 
 
 class _Catalog:

@@ -9,7 +9,7 @@ import argparse
 import csv
 
 PASS = ("k_filter", "k_gamma_filter", "k_prefix", "k_compact", "k_gamma_exact", "k_lev_refill", "k_gamma_slow",
-        "k_gamma_rest", "k_gamma_huge", "k_bag_rows")
+        "k_gamma_rest", "k_gamma_huge", "k_bag_rows", "k_gamma_exact_set", "k_gamma_slow_set", "k_gamma_huge_set")
 
 
 def spans(path):
