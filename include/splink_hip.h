@@ -641,6 +641,58 @@ int spk_select_best(spk_ctx *ctx, int field /* SPK_SEL_MP | SPK_SEL_TF_MP */, in
  * flags and scan, emit; the host round trip between them is not in it), -1 otherwise. */
 int spk_select_best_info(spk_ctx *ctx, int64_t *out_n_before, int64_t *out_n_kept, double *out_ms);
 
+/* ---- the first k pairs in score order (replaces df_e.orderBy("match_probability", ascending=False).limit(k) on the
+ *      frame expectation_step.py returns, which here would be toPandas() and a host sort of every pair) ---- */
+#define SPK_TOP_FIRST 0   /* frame order: the first k by ordinal */
+#define SPK_TOP_ASC   1
+#define SPK_TOP_DESC  2
+/* The result is this set, whatever the algorithm, chunking or launch shape.  The score is a double and NaN means NULL.
+ * Values are ordered as Spark orders them by default: NULL is smaller than every number, numbers compare as doubles
+ * (-0.0 equals +0.0).  SPK_TOP_ASC: pair a comes before pair b iff score(a) < score(b), or the scores are equal (two
+ * NULLs are) and ordinal(a) < ordinal(b); SPK_TOP_DESC: the same with score(a) > score(b), so NULLs come first
+ * ascending and last descending, and the ordinal (as spk_select_copy reports it) breaks ties in both directions: a
+ * strict total order.  SPK_TOP_FIRST: ascending ordinal alone.  Kept: the first min(k, eligible) eligible pairs in
+ * that order; k = 0 keeps none.  When 0 < k < eligible under a score order, the cut is the score of the k-th pair,
+ * `tied` the eligible pairs with that score (the eligible NULL pairs when it is NULL) and `tied_kept` how many of them
+ * are kept, the ones with the smallest ordinals; otherwise there is no cut and both are 0.
+ *
+ * spk_select_top is a selecting call, called like spk_select_sample: eligible = every term TRUE (spk_select's
+ * conjunction and three-valued logic; fields SPK_SEL_MP and SPK_SEL_GAMMA; n_terms = 0: all), the score is
+ * match_probability under lambda / m / u (as spk_score).  m / u may be NULL only with SPK_TOP_FIRST and no SPK_SEL_MP
+ * term.  It drops the previous selection first, and on success the context's one selection holds the kept pairs in
+ * ascending ordinal (not in score order); spk_select_copy, spk_select_info, spk_select_release, spk_select_best,
+ * spk_components* and spk_label_scores_selection work on it unchanged, and it goes stale as spk_select's does.  The
+ * score is a function of the pattern, so the cut is found on the pattern table: one pass over the codes counts the
+ * pairs per pattern, a weighted radix select over the eligible patterns' score keys (8 passes of 8 bits over
+ * n_patterns entries) finds the cut score and how many pairs at the cut are kept, one byte per pattern says above the
+ * cut / at the cut / out, and spk_select's count, scan and emit run with two counts per chunk: a pair at the cut is
+ * emitted iff fewer than tied_kept pairs at the cut precede it.  Nothing of P elements is allocated but the chunk
+ * counts; no workgroup waits for another, every loop has a fixed bound and the histograms are integer sums, so nothing
+ * depends on the order in which atomics arrive.  SPK_E_INVALID: unknown order, negative k, a score order without m / u,
+ * an unknown field (SPK_SEL_TF_MP included) or operator, and spk_select's argument errors.  SPK_E_STATE: no gammas.  A
+ * failing call leaves no selection.  Does not touch the scores of spk_score, tf state, EM state or component labels. */
+int spk_select_top(spk_ctx *ctx, double lambda, double one_minus, const double *m, const double *u, int n_terms,
+                   const spk_select_term *terms, int order, int64_t k, int64_t *out_n_selected);
+/* Narrows the context's selection, as spk_select_best does, to its first k survivors under `order`; eligible = every
+ * survivor, the score is the selection's own stored one: SPK_SEL_MP (its match_probability) or SPK_SEL_TF_MP (its
+ * tf_adjusted_match_prob); `field` is ignored for SPK_TOP_FIRST.  The kept pairs stay in ascending pair ordinal and
+ * REPLACE the selection: spk_select_copy, spk_select_copy_tf, spk_select_info (whose milliseconds stay those of the
+ * selecting call) and spk_components* work on them unchanged.  The cut comes from a radix select over an
+ * order-preserving 64-bit key of the survivors' scores, most significant byte first, one histogram and one pick launch
+ * per pass, then the two-count count, scan and emit over the survivors.  An empty selection is legal and keeps 0.
+ * SPK_E_INVALID: unknown order or field, negative k.  SPK_E_STATE: no selection; a stale one; SPK_SEL_MP on a selection
+ * made without m / u; SPK_SEL_TF_MP on one not made by spk_select_tf*.  A failing call leaves no selection.  Does not
+ * touch the scores of spk_score, tf state, EM state or component labels. */
+int spk_select_top_of(spk_ctx *ctx, int field /* SPK_SEL_MP | SPK_SEL_TF_MP; ignored for SPK_TOP_FIRST */, int order,
+                      int64_t k, int64_t *out_n_kept);
+/* The last spk_select_top / spk_select_top_of: eligible pairs, pairs kept, pairs at the cut and how many of those are
+ * kept (-1 each: none yet, or the last call failed), the cut score (NaN when there is no cut, and when the cut is NULL:
+ * out_tied is 0 in the first case and positive in the second), and with timing on (spk_ctx_enable_timing) the device
+ * milliseconds of its launches (pattern stage and histogram, digit passes and picks, count pass and scans, emit pass;
+ * the host round trip between them is not in it), -1 otherwise. */
+int spk_select_top_info(spk_ctx *ctx, int64_t *out_eligible, int64_t *out_kept, double *out_cut_score,
+                        int64_t *out_tied, int64_t *out_tied_kept, double *out_ms);
+
 /* ---- connected components of the kept pairs (replaces handing df_e.filter(...) to GraphFrames'
  *      connectedComponents; later reference releases: cluster_pairwise_predictions_at_threshold) ---- */
 /* label[v] = the smallest node id of v's component in the graph whose edges are the survivors of the last spk_select;

@@ -20,13 +20,14 @@ from .comparison_evaluation import (DEFAULT_MAX_ENUMERATE, BlockingProfile, get_
                                     profile_blocking_rules)
 from .expectation_step import run_expectation_step
 from .frames import (BestMatchFrame, ClusterBridges, ClusterFrame, ClusterMetrics, ClusterSweepFrame, FilteredFrame,
-                     SampleFrame, SplinkDataFrame)
+                     SampleFrame, SplinkDataFrame, TopFrame)
 from .gammas import add_gammas
 from .iterate import iterate
 from .labels import (LabelCounts, PairLabelCounts, ScoreLabelCounts, estimate_from_labels,
                      estimate_from_pair_labels)
 from .params import Params, load_params_from_json
 from .sampling import estimate_u_using_random_sampling, random_pairs
+from .select import asc, desc
 from .session import AmdSession, session
 from .settings import complete_settings_dict
 from .term_frequencies import make_adjustment_for_term_frequencies
@@ -34,7 +35,7 @@ from .validate import validate_settings
 
 __all__ = ["Splink", "load_from_json", "AmdSession", "session", "Params", "block_using_rules", "add_gammas",
            "iterate", "run_expectation_step", "make_adjustment_for_term_frequencies", "complete_settings_dict",
-           "ClusterFrame", "ClusterSweepFrame", "ClusterMetrics", "ClusterBridges", "FilteredFrame", "BestMatchFrame", "SampleFrame", "LabelCounts", "ScoreLabelCounts", "estimate_from_labels",
+           "ClusterFrame", "ClusterSweepFrame", "ClusterMetrics", "ClusterBridges", "FilteredFrame", "BestMatchFrame", "SampleFrame", "TopFrame", "asc", "desc", "LabelCounts", "ScoreLabelCounts", "estimate_from_labels",
            "PairLabelCounts", "estimate_from_pair_labels",
            "estimate_u_using_random_sampling", "random_pairs", "get_largest_blocks", "profile_blocking_rules",
            "BlockingProfile"]

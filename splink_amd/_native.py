@@ -45,6 +45,7 @@ SEL_OP = {"<": 0, "<=": 1, ">": 2, ">=": 3, "=": 4, "!=": 5, "is null": 6, "is n
 SELECT_MAX_TERMS = 8  # SPK_SELECT_MAX_TERMS
 BEST_L, BEST_R, BEST_EITHER, BEST_MUTUAL = 0, 1, 2, 3  # SPK_BEST_L .. SPK_BEST_MUTUAL (select_best's modes)
 SAMPLE_MAX_STRATA = 64  # SPK_SAMPLE_MAX_STRATA
+TOP_FIRST, TOP_ASC, TOP_DESC = 0, 1, 2  # SPK_TOP_FIRST, SPK_TOP_ASC, SPK_TOP_DESC (select_top's orders)
 # Pair ordinals per count of the selection's compaction.  Mirrored from SEL_CHUNK in csrc/spk_select.hip (the
 # library exports no call for it); only the tests' edge sizes depend on it.
 SELECT_CHUNK = 2048
@@ -83,6 +84,7 @@ EXPORTS = [
     "spk_select_tf", "spk_select_tf_columns", "spk_select_copy_tf",
     "spk_select_best", "spk_select_best_info",
     "spk_select_sample", "spk_select_sample_info",
+    "spk_select_top", "spk_select_top_of", "spk_select_top_info",
     "spk_components", "spk_components_edges", "spk_components_copy", "spk_components_info", "spk_components_release",
     "spk_components_sweep", "spk_components_sweep_edges", "spk_components_sweep_copy", "spk_components_sweep_info",
     "spk_components_sweep_release", "spk_components_sweep_set_mode",
@@ -796,6 +798,40 @@ class Context:
               "spk_select_sample_info")
         n = max(k.value, 0)
         return k.value, pop[:n].copy(), kept[:n].copy(), ms.value
+
+    def select_top(self, lam, one_minus, m, u, terms, order: int, k: int) -> int:
+        """spk_select_top: among the pairs for which every term is TRUE keep the first k under `order` (TOP_FIRST: by
+        ordinal; TOP_ASC / TOP_DESC: by match_probability, NULL lowest, ties by ordinal); returns how many.  They become
+        the context's selection, in ascending ordinal.  m = u = None only with TOP_FIRST and no match_probability term."""
+        t = self._select_terms(terms)
+        m = None if m is None else np.ascontiguousarray(m, dtype=np.float64)
+        u = None if u is None else np.ascontiguousarray(u, dtype=np.float64)
+        n = ctypes.c_int64(0)
+        check(self._lib.spk_select_top(self._h, ctypes.c_double(lam), ctypes.c_double(one_minus), _ptr(m), _ptr(u),
+                                       ctypes.c_int(len(t)), _ptr(t) if len(t) else ctypes.c_void_p(0),
+                                       ctypes.c_int(int(order)), ctypes.c_int64(int(k)), ctypes.byref(n)),
+              "spk_select_top")
+        return n.value
+
+    def select_top_of(self, field: int, order: int, k: int) -> int:
+        """spk_select_top_of: narrow the last select to its first k survivors under `order` by `field` (SEL_MP or
+        SEL_TF_MP; ignored for TOP_FIRST).  Returns how many are kept; they replace the selection."""
+        n = ctypes.c_int64(0)
+        check(self._lib.spk_select_top_of(self._h, ctypes.c_int(int(field)), ctypes.c_int(int(order)),
+                                          ctypes.c_int64(int(k)), ctypes.byref(n)), "spk_select_top_of")
+        return n.value
+
+    def select_top_info(self):
+        """The last select_top / select_top_of: (eligible, kept, cut score, tied, tied_kept, ms).  The counts are -1 when
+        there is none or it failed; the cut score is NaN without a cut (tied = 0) and for a NULL cut (tied > 0); ms is
+        that of its launches with timing on, or -1."""
+        e, k, t, tk = (ctypes.c_int64(-1) for _ in range(4))
+        cut = ctypes.c_double(float("nan"))
+        ms = ctypes.c_double(-1.0)
+        check(self._lib.spk_select_top_info(self._h, ctypes.byref(e), ctypes.byref(k), ctypes.byref(cut),
+                                            ctypes.byref(t), ctypes.byref(tk), ctypes.byref(ms)),
+              "spk_select_top_info")
+        return e.value, k.value, cut.value, t.value, tk.value, ms.value
 
     # ---- connected components of the kept pairs -----------------------------------------------
     def components(self):

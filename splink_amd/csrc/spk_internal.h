@@ -522,6 +522,10 @@ struct spk_ctx {
     // failed), device milliseconds
     std::vector<int64_t> strata_pop, strata_kept;
     double strata_ms = -1.0;
+    // the last spk_select_top / spk_select_top_of (spk_select.hip): eligible pairs, pairs kept, pairs at the cut and
+    // how many of them are kept (-1 each: none, or it failed), the cut score (NaN: no cut, or a NULL cut), device milliseconds
+    int64_t top_eligible = -1, top_kept = -1, top_tied = -1, top_tied_kept = -1;
+    double top_cut = __builtin_nan(""), top_ms = -1.0;
     // spk_components*: the last labels
     spk::Components comp;
     // spk_components_sweep*: the last sweep, and which edges a level's rounds hook: 0 the level's new edges plus a star

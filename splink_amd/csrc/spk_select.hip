@@ -24,6 +24,11 @@
 // keys: the stratum is a function of the pattern (a byte per pattern beside the keep bit's logic), the thresholds come
 // from a radix select over the keys that stores nothing per pair, and the survivors from the same count, scan and emit
 // (see "spk_select_sample" below).
+//
+// spk_select_top keeps the first k eligible pairs in score order (NULL lowest, ties by ordinal): the score is a function
+// of the pattern, so the cut is found on the pattern table by a weighted radix select, a byte per pattern says above the
+// cut / at the cut / out, and the count, scan and emit run with two counts per chunk; spk_select_top_of does the same
+// over a selection's survivors and their stored scores (see "spk_select_top" below).
 #include <algorithm>
 #include <cmath>
 
@@ -955,6 +960,700 @@ static int build_sample(spk_ctx *ctx, double lambda, double one_minus, const dou
     return SPK_OK;
 }
 
+// ---- spk_select_top / spk_select_top_of: the first k eligible pairs in score order ----
+// Both orders become "smallest key first": top_key maps a score to an unsigned 64-bit key that is monotone in the
+// order asked for (NULL = NaN lowest ascending, so last descending; -0.0 and +0.0 share a key).  A radix select, most
+// significant byte first, finds the key of the k-th element: pass d counts digit d of the keys that agree with the
+// prefix in the digits above it (256 integer bins; the order of the atomics does not matter), and k_top_pick (one
+// wave) takes the digit at which the running count reaches what is left of k, extends the prefix by it and reduces the
+// remainder by the count below it.  After 8 passes the prefix is the cut key, the remainder is how many elements at
+// the cut are kept, and the chosen bin's count is how many there are.  Pass 0 also settles the total, and k = 0 or
+// k >= total (nothing to select: none or all kept), after which the later histogram passes return at once.
+//   spk_select_top: the score is a function of the pattern, so the elements are the eligible patterns, weighted by
+//     their pairs (k_top_hist: one pass over the codes), and a byte per pattern (k_top_classes) says above the cut, at
+//     the cut or out.  k_top<EMIT = false> counts both classes per chunk, both counts are scanned, and k_top<EMIT =
+//     true> emits the pairs above the cut and the pairs at the cut whose exclusive rank among the at-the-cut pairs, in
+//     ordinal order across the chunks, is below the remainder: a chunk's output starts at (above before it) +
+//     min(at the cut before it, remainder).
+//   spk_select_top_of: the elements are the selection's survivors with their stored scores (k_topof_hist), and
+//     k_topof<EMIT> is the same two-count compaction over them, in spk_select_best's chunk layout.
+// SPK_TOP_FIRST is the same compaction with every eligible pair at the cut and remainder k; no score is read.
+enum { TOP_OUT = 0, TOP_ABOVE = 1, TOP_AT = 2 };                               // a pattern's / survivor's class
+enum { TS_PREFIX = 0, TS_REMAIN, TS_FLAG, TS_TOTAL, TS_TIED, TS_WORDS };      // the call's state, 64-bit device words
+enum { TOP_ACTIVE = 0, TOP_ALL = 1, TOP_EMPTY = 2, TOP_FIRSTK = 3 };          // TS_FLAG
+constexpr int TOP_DIGITS = 256, TOP_PASSES = 8;
+constexpr int64_t TOP_LDS_HIST = 8192;    // k_top_hist: 32-bit counters in LDS up to this many patterns (32 KiB)
+constexpr int64_t TOP_LDS_TAB = 32768;    // k_top: the class bytes in LDS up to this many patterns (32 KiB)
+constexpr int TOP_PAT_WG_PER_CU = 4;
+
+__host__ __device__ inline unsigned long long top_key(double s, bool desc) {
+    unsigned long long img = 0ull;  // NULL
+    if (s == s) {
+        unsigned long long u;
+#if defined(__HIP_DEVICE_COMPILE__)
+        u = (unsigned long long)__double_as_longlong(s);
+#else
+        __builtin_memcpy(&u, &s, 8);
+#endif
+        if ((u << 1) == 0ull) u = 0ull;  // -0.0 -> +0.0
+        img = (u >> 63) ? ~u : (u | 0x8000000000000000ull);  // never 0: -inf is 0x000F...F
+    }
+    return desc ? ~img : img;
+}
+
+// The score a key stands for (NaN: NULL).
+static double top_key_score(unsigned long long key, bool desc) {
+    const unsigned long long img = desc ? ~key : key;
+    if (img == 0ull) return __builtin_nan("");
+    const unsigned long long u = (img >> 63) ? (img & 0x7FFFFFFFFFFFFFFFull) : ~img;
+    double s;
+    __builtin_memcpy(&s, &u, 8);
+    return s;
+}
+
+__device__ inline int top_class(int flag, unsigned long long cut, unsigned long long key) {
+    if (flag == TOP_ALL) return TOP_ABOVE;
+    if (flag == TOP_EMPTY) return TOP_OUT;
+    if (flag == TOP_FIRSTK) return TOP_AT;
+    return key < cut ? TOP_ABOVE : key == cut ? TOP_AT : TOP_OUT;
+}
+
+// The pairs per pattern: hist [n_pat], zero at launch.  k_select's chunk layout.  LDS: 32-bit counters per workgroup,
+// added to the global ones at the end (a workgroup sees fewer than 2^32 pairs: launch_top_hist checks).
+template <typename CodeT, bool LDS>
+__global__ __launch_bounds__(SEL_THREADS) void k_top_hist(const void *codes_, int64_t P, int64_t n_chunks, int64_t n_pat,
+                                                          unsigned long long *__restrict__ hist) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_cnt[];
+    if (LDS) {
+        for (int i = threadIdx.x; i < (int)n_pat; i += SEL_THREADS) s_cnt[i] = 0u;
+        __syncthreads();
+    }
+    constexpr int V = 16 / (int)sizeof(CodeT);
+    constexpr int SLABS = (int)(SEL_CHUNK / (64 * V));
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const CodeT *codes = reinterpret_cast<const CodeT *>(codes_);
+    const int64_t n_waves = (int64_t)gridDim.x * SEL_WAVES;
+    for (int64_t c = (int64_t)blockIdx.x * SEL_WAVES + wave; c < n_chunks; c += n_waves) {
+        const int64_t base = c * SEL_CHUNK;
+        sel_u32x4 v[SLABS];
+        sel_load_chunk<CodeT>(codes, base, P, lane, v);
+#pragma unroll
+        for (int s = 0; s < SLABS; ++s) {
+            const int64_t p0 = base + ((int64_t)s * 64 + lane) * V;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                // one pattern holds most pairs (every column disagrees): the lanes whose code is the first lane's are
+                // counted with one ballot and added once, so a hot counter sees one atomic per wave, not 64
+                const uint32_t x = sel_code<CodeT>(v[s], j);
+                const bool valid = p0 + j < P && (int64_t)x < n_pat;
+                const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)x);
+                const bool same = valid && x == first;
+                const unsigned long long m = __ballot(same);
+                if (valid && (!same || lane == __ffsll((long long)m) - 1)) {
+                    const uint32_t n = same ? (uint32_t)__popcll(m) : 1u;
+                    if (LDS) atomicAdd(&s_cnt[x], n);
+                    else atomicAdd(&hist[x], (unsigned long long)n);
+                }
+            }
+        }
+    }
+    if (LDS) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < (int)n_pat; i += SEL_THREADS) {
+            const uint32_t n = s_cnt[i];
+            if (n) atomicAdd(&hist[i], (unsigned long long)n);
+        }
+    }
+}
+
+struct TopPatArgs {
+    int64_t n_pat;
+    const unsigned long long *keep;  // the eligible patterns (k_select_patterns)
+    const unsigned long long *cnt;   // pairs per pattern (k_top_hist)
+    const double *mpat;
+    int desc, pass;
+    unsigned long long *hist;        // [TOP_DIGITS], zero at launch
+    const unsigned long long *st;
+};
+
+// Pass `pass` of the weighted select: digit `pass` of the eligible patterns' keys under the prefix, weighted by their
+// pairs.  The workgroups stride over the patterns.
+__global__ __launch_bounds__(SEL_THREADS) void k_top_pat_hist(TopPatArgs A) {
+    __shared__ unsigned long long s_h[TOP_DIGITS];
+    if (A.pass > 0 && A.st[TS_FLAG] != (unsigned long long)TOP_ACTIVE) return;  // settled (grid-uniform)
+    for (int i = threadIdx.x; i < TOP_DIGITS; i += SEL_THREADS) s_h[i] = 0ull;
+    __syncthreads();
+    const unsigned long long prefix = A.pass > 0 ? A.st[TS_PREFIX] : 0ull;
+    const int shift = 56 - 8 * A.pass;  // the bits above the digit are shift + 8 .. 63 (pass 0: none)
+    for (int64_t p = (int64_t)blockIdx.x * SEL_THREADS + threadIdx.x; p < A.n_pat; p += (int64_t)gridDim.x * SEL_THREADS) {
+        if (!((A.keep[p >> 6] >> (p & 63)) & 1ull)) continue;
+        const unsigned long long w = A.cnt[p];
+        if (w == 0ull) continue;
+        const unsigned long long key = top_key(A.mpat[p], A.desc != 0);
+        if (A.pass > 0 && (key >> (shift + 8)) != (prefix >> (shift + 8))) continue;
+        atomicAdd(&s_h[(int)((key >> shift) & 255ull)], w);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < TOP_DIGITS; i += SEL_THREADS) {
+        const unsigned long long n = s_h[i];
+        if (n) atomicAdd(&A.hist[i], n);
+    }
+}
+
+// One wave, a lane per 4 digits (k_sample_pick for one stratum with quota k).  While active, 1 <= remainder <= the
+// elements under the prefix, so exactly one lane's digits contain the remainder-th element.  Leaves hist zero.
+__global__ __launch_bounds__(64) void k_top_pick(unsigned long long *__restrict__ hist, unsigned long long *__restrict__ st,
+                                                 int64_t k, int pass) {
+    const int lane = threadIdx.x;
+    unsigned long long c[4], own = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        c[j] = hist[4 * lane + j];
+        hist[4 * lane + j] = 0ull;
+        own += c[j];
+    }
+    unsigned long long incl = own;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long t = __shfl_up(incl, d);
+        if (lane >= d) incl += t;
+    }
+    const unsigned long long total = __shfl(incl, 63);
+    unsigned long long rem, prefix = 0ull;
+    int flag;
+    if (pass == 0) {
+        rem = (unsigned long long)k < total ? (unsigned long long)k : total;
+        flag = rem == 0ull ? TOP_EMPTY : rem == total ? TOP_ALL : TOP_ACTIVE;
+        if (lane == 0) {
+            st[TS_TOTAL] = total;
+            st[TS_FLAG] = (unsigned long long)flag;
+        }
+    } else {
+        flag = (int)st[TS_FLAG];
+        rem = st[TS_REMAIN];
+        prefix = st[TS_PREFIX];
+    }
+    if (flag != TOP_ACTIVE) return;  // wave-uniform
+    unsigned long long before = incl - own;
+    if (before < rem && rem <= incl) {
+        int j = 0;
+        while (j < 3 && before + c[j] < rem) before += c[j++];
+        st[TS_PREFIX] = prefix | ((unsigned long long)(4 * lane + j) << (56 - 8 * pass));
+        st[TS_REMAIN] = rem - before;
+        if (pass == TOP_PASSES - 1) st[TS_TIED] = c[j];
+    }
+}
+
+// One thread per pattern: its class byte.  mpat may be null under TOP_FIRSTK (no score is read).
+__global__ __launch_bounds__(SEL_THREADS) void k_top_classes(int64_t n_pat, const unsigned long long *__restrict__ keep,
+                                                             const double *__restrict__ mpat, int desc,
+                                                             const unsigned long long *__restrict__ st,
+                                                             uint8_t *__restrict__ tab) {
+    const int64_t p = (int64_t)blockIdx.x * SEL_THREADS + threadIdx.x;
+    if (p >= n_pat) return;
+    const int flag = (int)st[TS_FLAG];
+    int cls = TOP_OUT;
+    if ((keep[p >> 6] >> (p & 63)) & 1ull)
+        cls = top_class(flag, st[TS_PREFIX], flag == TOP_ACTIVE ? top_key(mpat[p], desc != 0) : 0ull);
+    tab[p] = (uint8_t)cls;
+}
+
+struct TopArgs {
+    const void *codes;          // uint16 or uint32, one per pair
+    int64_t P, n_chunks;
+    const uint8_t *tab;         // class per pattern
+    int64_t n_pat;
+    int tab_words;              // 32-bit words of tab staged in LDS (LDS form)
+    int64_t r;                  // emit pass: the at-the-cut pairs kept
+    const int32_t *pl, *pr;     // the pairs' rows, or null (no pair set)
+    int64_t *above_count, *at_count;        // count pass output
+    const int64_t *above_off, *at_off;      // emit pass input [n_chunks + 1]
+    int64_t *out_ord;
+    int32_t *out_l, *out_r;
+    uint32_t *out_code;
+};
+
+__device__ inline int64_t top_min(int64_t a, int64_t b) { return a < b ? a : b; }
+
+template <typename CodeT, bool LDS, bool EMIT>
+__global__ __launch_bounds__(SEL_THREADS) void k_top(TopArgs A) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];
+    if (LDS) {
+        for (int i = threadIdx.x; i < A.tab_words; i += SEL_THREADS) s_tab[i] = reinterpret_cast<const uint32_t *>(A.tab)[i];
+        __syncthreads();
+    }
+    const uint8_t *T = LDS ? reinterpret_cast<const uint8_t *>(s_tab) : A.tab;
+    constexpr int V = 16 / (int)sizeof(CodeT);            // codes per lane and slab
+    constexpr int SLABS = (int)(SEL_CHUNK / (64 * V));    // slabs per chunk
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const CodeT *codes = reinterpret_cast<const CodeT *>(A.codes);
+    const int64_t n_waves = (int64_t)gridDim.x * SEL_WAVES;
+    for (int64_t c = (int64_t)blockIdx.x * SEL_WAVES + wave; c < A.n_chunks; c += n_waves) {
+        int64_t run = 0, at_run = 0;
+        if (EMIT) {
+            at_run = A.at_off[c];
+            run = A.above_off[c] + top_min(at_run, A.r);
+            if (A.above_off[c + 1] + top_min(A.at_off[c + 1], A.r) == run) continue;  // nothing kept here (wave-uniform)
+        }
+        const int64_t base = c * SEL_CHUNK;
+        sel_u32x4 v[SLABS];
+        sel_load_chunk<CodeT>(codes, base, A.P, lane, v);
+        int n_above = 0, n_at = 0;
+#pragma unroll
+        for (int s = 0; s < SLABS; ++s) {
+            const int64_t p0 = base + ((int64_t)s * 64 + lane) * V;  // this lane's first pair of the slab
+            uint32_t code[V];
+            unsigned am = 0, tm = 0;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const uint32_t x = sel_code<CodeT>(v[s], j);
+                code[j] = x;
+                const int cls = p0 + j < A.P && (int64_t)x < A.n_pat ? (int)T[x] : TOP_OUT;
+                am |= (cls == TOP_ABOVE ? 1u : 0u) << j;
+                tm |= (cls == TOP_AT ? 1u : 0u) << j;
+            }
+            int at_before = 0, at_all = 0;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const unsigned long long m = __ballot((tm >> j) & 1u);
+                at_all += __popcll(m);
+                at_before += __popcll(m & below);
+            }
+            if (!EMIT) {
+#pragma unroll
+                for (int j = 0; j < V; ++j) n_above += __popcll(__ballot((am >> j) & 1u));
+                n_at += at_all;
+                continue;
+            }
+            unsigned km = am;
+            int64_t rank = at_run + at_before;  // at-the-cut pairs before this lane's first, over the whole pair set
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                if ((tm >> j) & 1u) {
+                    if (rank < A.r) km |= 1u << j;
+                    ++rank;
+                }
+            }
+            int before = 0, all = 0;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const unsigned long long m = __ballot((km >> j) & 1u);
+                all += __popcll(m);
+                before += __popcll(m & below);
+            }
+            int64_t q = run + before;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                if ((km >> j) & 1u) {
+                    const int64_t p = p0 + j;
+                    A.out_ord[q] = p;
+                    A.out_code[q] = code[j];
+                    if (A.pl) {
+                        A.out_l[q] = A.pl[p];
+                        A.out_r[q] = A.pr[p];
+                    }
+                    ++q;
+                }
+            }
+            run += all;
+            at_run += at_all;
+        }
+        if (!EMIT && lane == 0) {
+            A.above_count[c] = n_above;
+            A.at_count[c] = n_at;
+        }
+    }
+}
+
+template <typename CodeT>
+static int launch_top_hist(spk_ctx *ctx, int64_t n_chunks, unsigned long long *hist) {
+    const int64_t P = ctx->n_pairs, n_pat = ctx->n_patterns;
+    const bool lds = n_pat <= TOP_LDS_HIST;
+    const int64_t cap = (lds ? SMP_WG_PER_CU : SEL_WG_PER_CU) * (int64_t)ctx->n_cu;  // LDS: fewer histograms to add up
+    const int64_t g = std::max<int64_t>(std::min<int64_t>((n_chunks + SEL_WAVES - 1) / SEL_WAVES, cap), 1);
+    const int64_t per_wg = ((n_chunks + g * SEL_WAVES - 1) / (g * SEL_WAVES)) * SEL_WAVES * SEL_CHUNK;
+    SPK_REQUIRE(per_wg < ((int64_t)1 << 32), SPK_E_LIMIT, "spk_select_top: too many pairs");
+    if (lds) k_top_hist<CodeT, true><<<(unsigned)g, SEL_THREADS, (size_t)n_pat * 4, ctx->stream>>>(ctx->codes.p, P, n_chunks, n_pat, hist);
+    else k_top_hist<CodeT, false><<<(unsigned)g, SEL_THREADS, 0, ctx->stream>>>(ctx->codes.p, P, n_chunks, n_pat, hist);
+    SPK_HIP(hipGetLastError());
+    return SPK_OK;
+}
+
+template <typename CodeT, bool EMIT>
+static int launch_top(spk_ctx *ctx, const TopArgs &A, bool lds) {
+    const unsigned g = select_grid(ctx, A.n_chunks);
+    if (lds) k_top<CodeT, true, EMIT><<<g, SEL_THREADS, (size_t)A.tab_words * 4, ctx->stream>>>(A);
+    else k_top<CodeT, false, EMIT><<<g, SEL_THREADS, 0, ctx->stream>>>(A);
+    SPK_HIP(hipGetLastError());
+    return SPK_OK;
+}
+
+template <bool EMIT>
+static int launch_top_codes(spk_ctx *ctx, const TopArgs &A, bool lds) {
+    return ctx->code_bytes == 2 ? launch_top<uint16_t, EMIT>(ctx, A, lds) : launch_top<uint32_t, EMIT>(ctx, A, lds);
+}
+
+// What a top call found, for spk_select_top_info.
+struct TopResult {
+    int64_t eligible = 0, kept = 0, tied = 0, tied_kept = 0;
+    double cut = __builtin_nan("");
+    double ms = -1.0;
+};
+
+// The state after the picks, read back behind the scans: the at-the-cut pairs the emit pass keeps, and R's cut figures.
+// at_total: the at-the-cut pairs the count pass found.
+static int top_settle(int order, int64_t k, const unsigned long long *h_st, int64_t above_total, int64_t at_total,
+                      TopResult &R, int64_t &r) {
+    if (order == SPK_TOP_FIRST) {
+        R.eligible = at_total;
+        r = k;
+    } else {
+        R.eligible = (int64_t)h_st[TS_TOTAL];
+        const int flag = (int)h_st[TS_FLAG];
+        r = 0;
+        if (flag == TOP_ACTIVE) {
+            r = (int64_t)h_st[TS_REMAIN];
+            R.tied = (int64_t)h_st[TS_TIED];
+            R.tied_kept = r;
+            R.cut = top_key_score(h_st[TS_PREFIX], order == SPK_TOP_DESC);
+            SPK_REQUIRE(R.tied == at_total && r >= 1 && r <= R.tied, SPK_E_STATE, "spk_select_top: pairs at the cut");
+        }
+    }
+    R.kept = above_total + std::min(at_total, r);
+    SPK_REQUIRE(R.kept == std::min(k, R.eligible), SPK_E_STATE, "spk_select_top: kept count");
+    return SPK_OK;
+}
+
+// spk_select_top's selection into S.  One host round trip, behind the scans.
+static int build_top(spk_ctx *ctx, double lambda, double one_minus, const double *m, const double *u, int n_terms,
+                     const spk_select_term *terms, int order, int64_t k, Selection &S, TopResult &R) {
+    const int64_t P = ctx->n_pairs, n_pat = ctx->n_patterns;
+    SelPatArgs PA{};
+    PA.K = ctx->K;
+    PA.n_pat = n_pat;
+    for (int i = 0; i < ctx->K; ++i) {
+        PA.stride[i] = (int32_t)ctx->stride[i];
+        PA.nlev[i] = (uint8_t)ctx->n_levels[i];
+    }
+    for (int t = 0; t < n_terms; ++t) PA.terms[PA.n_terms++] = terms[t];
+    selection_header(ctx, m && u, S);
+    const bool scored = order != SPK_TOP_FIRST;
+    StageTimer T{ctx};
+    const int64_t words64 = (n_pat + 63) / 64, tab_bytes = (n_pat + 3) / 4 * 4;
+    DevBuf<unsigned long long> keep, cnt, hist, st;
+    DevBuf<uint8_t> tab, tmp, tmp_at;
+    CountScan above, at;
+    SPK_TRY(keep.alloc((size_t)words64 + 1));
+    SPK_TRY(tab.alloc((size_t)tab_bytes + 4));
+    SPK_TRY(st.alloc(TS_WORDS));
+    SPK_TRY(hist.alloc(TOP_DIGITS));
+    if (scored) SPK_TRY(cnt.alloc((size_t)n_pat + 1));
+    if (S.has_mp) SPK_TRY(S.mpat.alloc((size_t)n_pat + 1));
+    const int64_t n_chunks = (P + SEL_CHUNK - 1) / SEL_CHUNK;
+    SPK_TRY(above.alloc(ctx, n_chunks));
+    SPK_TRY(at.alloc(ctx, n_chunks));
+    // ---- per pattern: mp table, keep bitset, pairs; the cut; the classes; per chunk: both counts; their scans
+    const unsigned long long h_init[TS_WORDS] = {0ull, 0ull, (unsigned long long)(scored ? TOP_ACTIVE : TOP_FIRSTK), 0ull, 0ull};
+    unsigned long long h_st[TS_WORDS] = {};  // read back behind the scans
+    SPK_TRY(T.open());
+    SPK_HIP(hipMemcpyAsync(st.p, h_init, sizeof(h_init), hipMemcpyHostToDevice, ctx->stream));
+    SPK_HIP(hipMemsetAsync(tab.p, TOP_OUT, (size_t)tab_bytes + 4, ctx->stream));
+    SPK_HIP(hipMemsetAsync(hist.p, 0, (size_t)TOP_DIGITS * 8, ctx->stream));
+    if (S.has_mp) SPK_TRY(pattern_mp_table(ctx, lambda, one_minus, m, u, S.mpat.p));
+    const unsigned pat_blocks = (unsigned)((n_pat + SEL_THREADS - 1) / SEL_THREADS);
+    if (n_pat > 0) {
+        k_select_patterns<<<pat_blocks, SEL_THREADS, 0, ctx->stream>>>(PA, S.mpat.p, keep.p);
+        SPK_HIP(hipGetLastError());
+    }
+    if (scored) {
+        SPK_HIP(hipMemsetAsync(cnt.p, 0, ((size_t)n_pat + 1) * 8, ctx->stream));
+        if (n_chunks > 0) {
+            if (ctx->code_bytes == 2) SPK_TRY(launch_top_hist<uint16_t>(ctx, n_chunks, cnt.p));
+            else SPK_TRY(launch_top_hist<uint32_t>(ctx, n_chunks, cnt.p));
+        }
+        TopPatArgs H{};
+        H.n_pat = n_pat;
+        H.keep = keep.p;
+        H.cnt = cnt.p;
+        H.mpat = S.mpat.p;
+        H.desc = order == SPK_TOP_DESC;
+        H.hist = hist.p;
+        H.st = st.p;
+        const unsigned g = (unsigned)std::max<int64_t>(
+            std::min<int64_t>(pat_blocks, TOP_PAT_WG_PER_CU * (int64_t)ctx->n_cu), 1);
+        for (int pass = 0; pass < TOP_PASSES; ++pass) {
+            H.pass = pass;
+            k_top_pat_hist<<<g, SEL_THREADS, 0, ctx->stream>>>(H);
+            SPK_HIP(hipGetLastError());
+            k_top_pick<<<1, 64, 0, ctx->stream>>>(hist.p, st.p, k, pass);
+            SPK_HIP(hipGetLastError());
+        }
+    }
+    if (n_pat > 0) {
+        k_top_classes<<<pat_blocks, SEL_THREADS, 0, ctx->stream>>>(n_pat, keep.p, S.mpat.p, order == SPK_TOP_DESC, st.p,
+                                                                   tab.p);
+        SPK_HIP(hipGetLastError());
+    }
+    TopArgs A{};
+    A.codes = ctx->codes.p;
+    A.P = P;
+    A.n_chunks = n_chunks;
+    A.tab = tab.p;
+    A.n_pat = n_pat;
+    A.tab_words = (int)(tab_bytes / 4);
+    A.pl = S.has_rows ? ctx->pl.p : nullptr;
+    A.pr = S.has_rows ? ctx->pr.p : nullptr;
+    const bool lds = n_pat <= TOP_LDS_TAB;
+    if (n_chunks > 0) {
+        A.above_count = above.count.p;
+        A.at_count = at.count.p;
+        SPK_TRY(launch_top_codes<false>(ctx, A, lds));
+    }
+    SPK_TRY(exclusive_scan(ctx->stream, tmp_at, at.count.p, at.off.p, n_chunks + 1));
+    SPK_HIP(hipMemcpyAsync(&at.total, at.off.p + n_chunks, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    SPK_HIP(hipMemcpyAsync(h_st, st.p, sizeof(h_st), hipMemcpyDeviceToHost, ctx->stream));
+    SPK_TRY(scan_total(ctx, above, tmp, &T));  // synchronises
+    int64_t r = 0;
+    SPK_TRY(top_settle(order, k, h_st, above.total, at.total, R, r));
+    const int64_t n_sel = R.kept;
+    SPK_REQUIRE(n_sel >= 0 && n_sel <= P, SPK_E_STATE, "spk_select_top: survivor count");
+    // ---- the survivors
+    SPK_TRY(selection_alloc(S, n_sel));
+    if (n_sel > 0) {
+        A.above_count = A.at_count = nullptr;
+        A.above_off = above.off.p;
+        A.at_off = at.off.p;
+        A.r = r;
+        A.out_ord = S.ord.p;
+        A.out_code = S.code.p;
+        A.out_l = S.l.p;
+        A.out_r = S.r.p;
+        SPK_TRY(T.open());
+        SPK_TRY(launch_top_codes<true>(ctx, A, lds));
+        SPK_TRY(T.close());
+    }
+    S.n = n_sel;
+    S.ms = R.ms = T.result();
+    S.valid = true;
+    return SPK_OK;
+}
+
+// ---- spk_select_top_of: the same over a selection's survivors ----
+struct TopOfArgs {
+    int64_t n, n_chunks;          // survivors, chunks of SEL_CHUNK
+    const int64_t *ord;
+    const int32_t *l, *r;         // or null (a selection without rows)
+    const uint32_t *code;
+    const double *mpat;           // SPK_SEL_MP: score = mpat[code] ...
+    int64_t n_pat;
+    const double *tf_mp;          // ... SPK_SEL_TF_MP: score = tf_mp[i]; both null: SPK_TOP_FIRST
+    const double *cp_tf, *cp_adj; // emit pass: the selection's tf outputs to copy, or null
+    int n_tf;
+    int desc, pass;
+    unsigned long long *hist;     // [TOP_DIGITS], zero at launch
+    const unsigned long long *st;
+    int64_t r_keep;               // emit pass: the at-the-cut survivors kept
+    int64_t *above_count, *at_count;
+    const int64_t *above_off, *at_off;
+    int64_t *out_ord;
+    int32_t *out_l, *out_r;
+    uint32_t *out_code;
+    double *out_tf, *out_adj;
+};
+
+// Survivor i < n's key.  A code outside the table (spk_select kept no such code) counts as NULL.
+__device__ inline unsigned long long topof_key(const TopOfArgs &A, int64_t i) {
+    double s = __builtin_nan("");
+    if (A.tf_mp) {
+        s = A.tf_mp[i];
+    } else if (A.mpat) {
+        const int64_t c = A.code[i];
+        if (c < A.n_pat) s = A.mpat[c];
+    }
+    return top_key(s, A.desc != 0);
+}
+
+__global__ __launch_bounds__(SEL_THREADS) void k_topof_hist(TopOfArgs A) {
+    __shared__ uint32_t s_h[TOP_DIGITS];
+    if (A.pass > 0 && A.st[TS_FLAG] != (unsigned long long)TOP_ACTIVE) return;  // settled (grid-uniform)
+    for (int i = threadIdx.x; i < TOP_DIGITS; i += SEL_THREADS) s_h[i] = 0u;
+    __syncthreads();
+    const unsigned long long prefix = A.pass > 0 ? A.st[TS_PREFIX] : 0ull;
+    const int shift = 56 - 8 * A.pass;
+    for (int64_t i = (int64_t)blockIdx.x * SEL_THREADS + threadIdx.x; i < A.n; i += (int64_t)gridDim.x * SEL_THREADS) {
+        const unsigned long long key = topof_key(A, i);
+        if (A.pass > 0 && (key >> (shift + 8)) != (prefix >> (shift + 8))) continue;
+        atomicAdd(&s_h[(int)((key >> shift) & 255ull)], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < TOP_DIGITS; i += SEL_THREADS) {
+        const uint32_t n = s_h[i];
+        if (n) atomicAdd(&A.hist[i], (unsigned long long)n);
+    }
+}
+
+// spk_select_best's chunk layout: one wave per chunk of SEL_CHUNK survivors, 64 consecutive survivors per slab.
+template <bool EMIT>
+__global__ __launch_bounds__(SEL_THREADS) void k_topof(TopOfArgs A) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int flag = (int)A.st[TS_FLAG];
+    const unsigned long long cut = A.st[TS_PREFIX];
+    const int64_t n_waves = (int64_t)gridDim.x * SEL_WAVES;
+    for (int64_t c = (int64_t)blockIdx.x * SEL_WAVES + wave; c < A.n_chunks; c += n_waves) {
+        int64_t run = 0, at_run = 0;
+        if (EMIT) {
+            at_run = A.at_off[c];
+            run = A.above_off[c] + top_min(at_run, A.r_keep);
+            if (A.above_off[c + 1] + top_min(A.at_off[c + 1], A.r_keep) == run) continue;  // wave-uniform
+        }
+        const int64_t base = c * SEL_CHUNK;
+        int n_above = 0, n_at = 0;
+        for (int s = 0; s < (int)(SEL_CHUNK / 64); ++s) {
+            const int64_t i0 = base + (int64_t)s * 64;
+            if (i0 >= A.n) break;  // wave-uniform
+            const int64_t i = i0 + lane;
+            int cls = TOP_OUT;
+            if (i < A.n) cls = top_class(flag, cut, flag == TOP_ACTIVE ? topof_key(A, i) : 0ull);
+            const unsigned long long wa = __ballot(cls == TOP_ABOVE), wt = __ballot(cls == TOP_AT);
+            if (!EMIT) {
+                n_above += __popcll(wa);
+                n_at += __popcll(wt);
+                continue;
+            }
+            const bool keep = cls == TOP_ABOVE || (cls == TOP_AT && at_run + __popcll(wt & below) < A.r_keep);
+            const unsigned long long w = __ballot(keep);
+            if (keep) {  // i < n
+                const int64_t q = run + __popcll(w & below);
+                A.out_ord[q] = A.ord[i];
+                A.out_code[q] = A.code[i];
+                if (A.l) {
+                    A.out_l[q] = A.l[i];
+                    A.out_r[q] = A.r[i];
+                }
+                if (A.out_tf) A.out_tf[q] = A.cp_tf[i];
+                if (A.out_adj)
+                    for (int t = 0; t < A.n_tf; ++t) A.out_adj[q * A.n_tf + t] = A.cp_adj[i * A.n_tf + t];
+            }
+            run += __popcll(w);
+            at_run += __popcll(wt);
+        }
+        if (!EMIT && lane == 0) {
+            A.above_count[c] = n_above;
+            A.at_count[c] = n_at;
+        }
+    }
+}
+
+// The narrowing of S (the context's former selection, now a local of spk_select_top_of) into T.
+static int narrow_top(spk_ctx *ctx, Selection &S, int field, int order, int64_t k, Selection &T, TopResult &R) {
+    hipStream_t stream = ctx->stream;
+    const int64_t n = S.n;
+    T.K = S.K;
+    T.n_levels = S.n_levels;
+    T.stride = S.stride;
+    T.has_rows = S.has_rows;
+    T.has_mp = S.has_mp;
+    T.has_tf = S.has_tf;
+    T.n_tf = S.n_tf;
+    T.pairs_epoch = S.pairs_epoch;
+    T.gamma_seq = S.gamma_seq;
+    T.fix_seq = S.fix_seq;
+    T.ms = S.ms;  // spk_select_info keeps its meaning: the time of the selection's own kernels
+    const bool scored = order != SPK_TOP_FIRST;
+    StageTimer watch{ctx};
+    const int64_t n_chunks = (n + SEL_CHUNK - 1) / SEL_CHUNK;
+    TopOfArgs A{};
+    DevBuf<unsigned long long> hist, st;
+    DevBuf<uint8_t> tmp, tmp_at;
+    CountScan above, at;
+    const unsigned long long h_init[TS_WORDS] = {0ull, 0ull, (unsigned long long)(scored ? TOP_ACTIVE : TOP_FIRSTK), 0ull, 0ull};
+    unsigned long long h_st[TS_WORDS] = {};  // read back behind the scans
+    int64_t r = 0;
+    if (n > 0) {
+        SPK_TRY(hist.alloc(TOP_DIGITS));
+        SPK_TRY(st.alloc(TS_WORDS));
+        SPK_TRY(above.alloc(ctx, n_chunks));
+        SPK_TRY(at.alloc(ctx, n_chunks));
+        A.n = n;
+        A.n_chunks = n_chunks;
+        A.ord = S.ord.p;
+        A.l = S.has_rows ? S.l.p : nullptr;
+        A.r = S.has_rows ? S.r.p : nullptr;
+        A.code = S.code.p;
+        if (scored && field == SPK_SEL_MP) {
+            A.mpat = S.mpat.p;
+            A.n_pat = (int64_t)S.mpat.n - 1;  // the selecting calls allocate n_patterns + 1
+        }
+        if (scored && field == SPK_SEL_TF_MP) A.tf_mp = S.tf_mp.p;
+        A.n_tf = S.n_tf;
+        A.desc = order == SPK_TOP_DESC;
+        A.hist = hist.p;
+        A.st = st.p;
+        A.above_count = above.count.p;
+        A.at_count = at.count.p;
+        const unsigned g = select_grid(ctx, n_chunks);
+        SPK_REQUIRE(n < ((int64_t)1 << 32), SPK_E_LIMIT, "spk_select_top_of: too many survivors");  // k_topof_hist's counters
+        SPK_TRY(watch.open());
+        SPK_HIP(hipMemcpyAsync(st.p, h_init, sizeof(h_init), hipMemcpyHostToDevice, stream));
+        SPK_HIP(hipMemsetAsync(hist.p, 0, (size_t)TOP_DIGITS * 8, stream));
+        if (scored) {
+            for (int pass = 0; pass < TOP_PASSES; ++pass) {
+                A.pass = pass;
+                k_topof_hist<<<g, SEL_THREADS, 0, stream>>>(A);
+                SPK_HIP(hipGetLastError());
+                k_top_pick<<<1, 64, 0, stream>>>(hist.p, st.p, k, pass);
+                SPK_HIP(hipGetLastError());
+            }
+        }
+        k_topof<false><<<g, SEL_THREADS, 0, stream>>>(A);
+        SPK_HIP(hipGetLastError());
+        SPK_TRY(exclusive_scan(stream, tmp_at, at.count.p, at.off.p, n_chunks + 1));
+        SPK_HIP(hipMemcpyAsync(&at.total, at.off.p + n_chunks, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+        SPK_HIP(hipMemcpyAsync(h_st, st.p, sizeof(h_st), hipMemcpyDeviceToHost, stream));
+        SPK_TRY(scan_total(ctx, above, tmp, &watch));  // synchronises
+        SPK_TRY(top_settle(order, k, h_st, above.total, at.total, R, r));
+        SPK_REQUIRE(R.eligible == n, SPK_E_STATE, "spk_select_top_of: survivor count");
+    }
+    const int64_t kept = R.kept;
+    SPK_TRY(T.ord.alloc((size_t)kept + 1));
+    SPK_TRY(T.code.alloc((size_t)kept + 1));
+    if (S.has_rows) {
+        SPK_TRY(T.l.alloc((size_t)kept + 1));
+        SPK_TRY(T.r.alloc((size_t)kept + 1));
+    }
+    if (S.has_tf) {
+        SPK_TRY(T.tf_mp.alloc((size_t)kept + 1));
+        SPK_TRY(T.adj.alloc((size_t)kept * S.n_tf + 1));
+    }
+    if (kept > 0) {
+        A.above_count = A.at_count = nullptr;
+        A.above_off = above.off.p;
+        A.at_off = at.off.p;
+        A.r_keep = r;
+        A.out_ord = T.ord.p;
+        A.out_l = T.l.p;
+        A.out_r = T.r.p;
+        A.out_code = T.code.p;
+        if (S.has_tf) {
+            A.cp_tf = S.tf_mp.p;
+            A.cp_adj = S.adj.p;
+            A.out_tf = T.tf_mp.p;
+            A.out_adj = S.n_tf > 0 ? T.adj.p : nullptr;
+        }
+        SPK_TRY(watch.open());
+        k_topof<true><<<select_grid(ctx, n_chunks), SEL_THREADS, 0, stream>>>(A);
+        SPK_HIP(hipGetLastError());
+        SPK_TRY(watch.close());
+    }
+    T.mpat = std::move(S.mpat);
+    T.n = kept;
+    T.valid = true;
+    R.ms = watch.result();
+    return SPK_OK;
+}
+
 }  // namespace spk
 
 using namespace spk;
@@ -1082,6 +1781,82 @@ extern "C" int spk_select_sample_info(spk_ctx *ctx, int *out_n_strata, int64_t *
     if (out_population) std::copy(ctx->strata_pop.begin(), ctx->strata_pop.end(), out_population);
     if (out_kept) std::copy(ctx->strata_kept.begin(), ctx->strata_kept.end(), out_kept);
     if (out_ms) *out_ms = n ? ctx->strata_ms : -1.0;
+    return SPK_OK;
+}
+
+// A top call starts without figures (a failing one leaves none) and ends by recording them.
+static void top_info_clear(spk_ctx *ctx) {
+    ctx->top_eligible = ctx->top_kept = ctx->top_tied = ctx->top_tied_kept = -1;
+    ctx->top_cut = __builtin_nan("");
+    ctx->top_ms = -1.0;
+}
+
+static void top_info_set(spk_ctx *ctx, const TopResult &R) {
+    ctx->top_eligible = R.eligible;
+    ctx->top_kept = R.kept;
+    ctx->top_tied = R.tied;
+    ctx->top_tied_kept = R.tied_kept;
+    ctx->top_cut = R.cut;
+    ctx->top_ms = R.ms;
+}
+
+extern "C" int spk_select_top(spk_ctx *ctx, double lambda, double one_minus, const double *m, const double *u,
+                              int n_terms, const spk_select_term *terms, int order, int64_t k, int64_t *out_n_selected) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_select_top: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    ctx->sel.clear();  // a failing call leaves no selection, and no figures for spk_select_top_info
+    top_info_clear(ctx);
+    SPK_REQUIRE(order >= SPK_TOP_FIRST && order <= SPK_TOP_DESC, SPK_E_INVALID,
+                "spk_select_top: unknown order (SPK_TOP_FIRST, _ASC or _DESC)");
+    SPK_REQUIRE(k >= 0, SPK_E_INVALID, "spk_select_top: negative k");
+    SPK_REQUIRE(order == SPK_TOP_FIRST || (m && u), SPK_E_INVALID, "spk_select_top: a score order needs m and u");
+    SPK_TRY(select_begin(ctx, "spk_select_top", m, u, n_terms, terms, false));
+    Selection S;
+    TopResult R;
+    SPK_TRY(build_top(ctx, lambda, one_minus, m, u, n_terms, terms, order, k, S, R));
+    ctx->sel = std::move(S);
+    top_info_set(ctx, R);
+    if (out_n_selected) *out_n_selected = ctx->sel.n;
+    return SPK_OK;
+}
+
+extern "C" int spk_select_top_of(spk_ctx *ctx, int field, int order, int64_t k, int64_t *out_n_kept) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_select_top_of: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    Selection S = std::move(ctx->sel);  // freed when this call returns, whatever happens below ...
+    ctx->sel.clear();                   // ... and a failing call leaves no selection
+    top_info_clear(ctx);
+    SPK_REQUIRE(order >= SPK_TOP_FIRST && order <= SPK_TOP_DESC, SPK_E_INVALID,
+                "spk_select_top_of: unknown order (SPK_TOP_FIRST, _ASC or _DESC)");
+    SPK_REQUIRE(order == SPK_TOP_FIRST || field == SPK_SEL_MP || field == SPK_SEL_TF_MP, SPK_E_INVALID,
+                "spk_select_top_of: unknown field (SPK_SEL_MP or SPK_SEL_TF_MP)");
+    SPK_REQUIRE(k >= 0, SPK_E_INVALID, "spk_select_top_of: negative k");
+    SPK_REQUIRE(S.valid, SPK_E_STATE, "spk_select_top_of: no selection (run spk_select)");
+    SPK_REQUIRE(S.current(ctx), SPK_E_STATE, "spk_select_top_of: the pairs or codes changed since spk_select");
+    if (order != SPK_TOP_FIRST) {
+        SPK_REQUIRE(field != SPK_SEL_MP || S.has_mp, SPK_E_STATE,
+                    "spk_select_top_of: no match_probability (spk_select got no m / u)");
+        SPK_REQUIRE(field != SPK_SEL_TF_MP || S.has_tf, SPK_E_STATE,
+                    "spk_select_top_of: no tf_adjusted_match_prob (the selection was made without tf tables, spk_select)");
+    }
+    Selection T;
+    TopResult R;
+    SPK_TRY(narrow_top(ctx, S, field, order, k, T, R));
+    ctx->sel = std::move(T);
+    top_info_set(ctx, R);
+    if (out_n_kept) *out_n_kept = ctx->sel.n;
+    return SPK_OK;
+}
+
+extern "C" int spk_select_top_info(spk_ctx *ctx, int64_t *out_eligible, int64_t *out_kept, double *out_cut_score,
+                                   int64_t *out_tied, int64_t *out_tied_kept, double *out_ms) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_select_top_info: null ctx");
+    if (out_eligible) *out_eligible = ctx->top_eligible;
+    if (out_kept) *out_kept = ctx->top_kept;
+    if (out_cut_score) *out_cut_score = ctx->top_cut;
+    if (out_tied) *out_tied = ctx->top_tied;
+    if (out_tied_kept) *out_tied_kept = ctx->top_tied_kept;
+    if (out_ms) *out_ms = ctx->top_ms;
     return SPK_OK;
 }
 

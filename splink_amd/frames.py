@@ -464,6 +464,19 @@ class ExpectationFrame(SplinkDataFrame):
         from .select import Predicate
         return FilteredFrame(self, Predicate()).sample_pairs(per_stratum=per_stratum, strata=strata, seed=seed)
 
+    def orderBy(self, col, ascending=True):  # noqa: N802 (Spark name)
+        """df_e.orderBy("match_probability", ascending=False).limit(k): the first k pairs in score order, selected on
+        the device.  Shorthand for the same call on the unfiltered FilteredFrame."""
+        from .select import Predicate
+        return FilteredFrame(self, Predicate()).orderBy(col, ascending)
+
+    sort = orderBy
+
+    def limit(self, k):
+        """The first k pairs of this frame, in its order: shorthand for the same call on the unfiltered FilteredFrame."""
+        from .select import Predicate
+        return FilteredFrame(self, Predicate()).limit(k)
+
     def label_counts(self, label_column):
         """GammaFrame.label_counts with the match_probability of every pattern under this frame's parameters."""
         return _label_counts(self.gammas, label_column, self.lam, self.level_probs)
@@ -618,6 +631,18 @@ class FilteredFrame(SplinkDataFrame):
         positions in the frame alone: the same seed with a larger per_stratum gives a superset."""
         return SampleFrame(self, per_stratum, strata, seed)
 
+    def orderBy(self, col, ascending=True):  # noqa: N802 (Spark name)
+        """This frame's pairs ordered by one of its score columns (a name, or asc(name) / desc(name)), as Spark orders
+        them: NULLs first ascending and last descending; equal scores in the frame's own order.  A lazy `TopFrame`:
+        .limit(k) keeps the first k, and only those leave the device (spk_select_top / spk_select_top_of)."""
+        return TopFrame(self, col, ascending, None)
+
+    sort = orderBy
+
+    def limit(self, k):
+        """The first k pairs of this frame, in its order: a lazy `TopFrame`."""
+        return TopFrame(self, None, True, k)
+
     def _score_names(self):
         """The scores this frame's pairs carry, the default first."""
         return self._best_by
@@ -741,6 +766,12 @@ class SampleFrame(FilteredFrame):
 
     filter = where = best_matches = clusters = clusters_at_thresholds = sample_pairs = _refuse
 
+    def _refuse_order(self, *args, **kwargs):
+        raise ValueError("a sample frame takes no orderBy() or limit(): its rows are a random subset, and the first k "
+                         "of them would describe the draw, not the linkage (order the filtered frame instead)")
+
+    orderBy = sort = limit = _refuse_order
+
     def _select(self):
         """Make the context's selection this frame's, under the ownership rules of FilteredFrame._select."""
         job, parent = self.job, self.parent
@@ -776,6 +807,98 @@ class SampleFrame(FilteredFrame):
         b = sample_strata(mp, self._edges)
         weight = self._pop[b].astype(np.float64) / self._kept[b].astype(np.float64)
         return {"stratum": b.astype(np.int32), "sampling_weight": weight}
+
+
+class TopFrame(FilteredFrame):
+    """`frame.orderBy(col, ascending).limit(k)` / `frame.limit(k)`: lazily selected on the device.  The frame has the
+    inner frame's columns; its rows are the first k of the inner frame's under the order (NULL scores lowest, equal
+    scores in the inner frame's order; without a column: the inner frame's order), in that order.  Without limit()
+    every pair of the inner frame is kept, sorted.  count() is the kept count, cut() describes the cut, and
+    truth_table(label) scores the first k against labels."""
+
+    def __init__(self, inner: FilteredFrame, column, ascending, k):
+        from .select import top_args
+        scored = inner._scored_parent() is not None
+        self._field, self._order, self._k = top_args(column, ascending, k, inner._score_names() if scored else ())
+        if inner.job.n_shards > 1:
+            raise ValueError("orderBy() / limit() on a sharded job: the first k pairs span the shards (take the first "
+                             "k of every shard and merge them on the host)")
+        super().__init__(inner.parent, inner.predicate)
+        self.inner = inner
+        self.gammas = inner.gammas
+        self._column, self._ascending = column, ascending
+        self._cut = None
+
+    def _column_order(self):
+        return self.inner._column_order()
+
+    def _scored_parent(self):
+        return self.inner._scored_parent()
+
+    def _extra_columns(self, n):
+        return self.inner._extra_columns(n)
+
+    def _score_names(self):
+        return self.inner._score_names()
+
+    def limit(self, k):
+        """The first k rows of this order (a second limit() replaces the first)."""
+        return TopFrame(self.inner, self._column, self._ascending, k)
+
+    def _refuse(self, *args, **kwargs):
+        raise ValueError("an ordered frame takes no further filter(), best_matches(), clusters(), sample_pairs() or "
+                         "orderBy(): filter and narrow first, then order and limit (anything derived from the first k "
+                         "rows would describe the cut, not the linkage)")
+
+    filter = where = best_matches = clusters = clusters_at_thresholds = sample_pairs = orderBy = sort = _refuse
+
+    def _select(self):
+        """Make the context's selection this frame's.  A plain filtered frame goes down as one call with its terms
+        (spk_select_top: no full selection is made); any other inner frame makes its own selection, which is then
+        narrowed (spk_select_top_of)."""
+        from . import _native as N
+        job, inner = self.job, self.inner
+        self.gammas.ensure_codes()
+        if self._n is not None and job.selection_owner is self and self._seq == job.codes_seq:
+            return self._n
+        if type(inner) is FilteredFrame:
+            job.selection_owner = None  # the call drops the context's selection first, and leaves none if it fails
+            terms = self.predicate.native_terms()
+            if isinstance(self.parent, ExpectationFrame):
+                m, u = job.flat_tables(self.parent.level_probs)
+                lam = float(self.parent.lam)
+                n = job.ctx.select_top(lam, float(1 - self.parent.lam), m, u, terms, self._order, self._k)
+            else:
+                n = job.ctx.select_top(0.0, 0.0, None, None, terms, self._order, self._k)
+        else:
+            inner._select()
+            job.selection_owner = None  # the narrowing replaces the inner frame's survivors, or leaves none if it fails
+            n = job.ctx.select_top_of(N.SEL_MP if self._field is None else self._field, self._order, self._k)
+        eligible, kept, score, tied, tied_kept, _ = job.ctx.select_top_info()
+        self._cut = {"eligible": int(eligible), "kept": int(kept),
+                     "score": None if tied == 0 or score != score else float(score),
+                     "tied": int(tied), "tied_kept": int(tied_kept)}
+        job.selection_owner = self
+        self._seq = job.codes_seq
+        self._n = int(n)
+        return self._n
+
+    def cut(self):
+        """{"eligible": the inner frame's pairs, "kept": this frame's, "score": the k-th pair's score (None: no cut,
+        that is k = 0 or k >= eligible or no order, or a NULL score), "tied": the inner frame's pairs with that score,
+        "tied_kept": how many of them are kept (the first ones in the inner frame's order)}."""
+        if self._cut is None:
+            self._select()
+        return dict(self._cut)
+
+    def _materialise(self):
+        from . import _native as N
+        from .select import TOP_FIRST, top_order
+        pdf = super()._materialise()  # the kept pairs in ascending ordinal
+        if self._order == TOP_FIRST:
+            return pdf
+        by = "tf_adjusted_match_prob" if self._field == N.SEL_TF_MP else "match_probability"
+        return pdf.iloc[top_order(pdf[by].to_numpy(), self._order)].reset_index(drop=True)
 
 
 COPY_NODES = 1 << 26  # labels per spk_components_copy

@@ -105,6 +105,64 @@ def sample_strata(mp, edges):
     return np.searchsorted(np.asarray(edges[1:-1], dtype=np.float64), np.asarray(mp, dtype=np.float64), side="right")
 
 
+TOP_FIRST, TOP_ASC, TOP_DESC = N.TOP_FIRST, N.TOP_ASC, N.TOP_DESC
+
+
+@dataclass(frozen=True)
+class SortColumn:
+    """What `asc(name)` / `desc(name)` return: a column name with its direction, for `frame.orderBy(...)`."""
+    name: str
+    ascending: bool = True
+
+
+def asc(name):
+    """`frame.orderBy(asc("match_probability"))`, as in Spark: NULLs first, ties by the pair's ordinal."""
+    return SortColumn(name, True)
+
+
+def desc(name):
+    """`frame.orderBy(desc("match_probability"))`, as in Spark: NULLs last, ties by the pair's ordinal."""
+    return SortColumn(name, False)
+
+
+def top_args(column, ascending, k, allowed):
+    """(field, order, k) of spk_select_top / spk_select_top_of for orderBy(column, ascending).limit(k) on a frame whose
+    score columns are `allowed`.  column None: frame order (limit alone), field is then None; k None: every eligible
+    pair (an orderBy without limit).  `column` is a name or asc(name) / desc(name), which carries its own direction.
+    Anything else raises ValueError naming what is supported."""
+    if k is None:
+        k = (1 << 63) - 1
+    elif not _plain_int(k) or k < 0:
+        raise ValueError(f"limit: k={k!r}; an int >= 0")
+    k = min(int(k), (1 << 63) - 1)
+    if column is None:
+        return None, TOP_FIRST, k
+    if isinstance(column, SortColumn):
+        column, ascending = column.name, column.ascending
+    if not isinstance(ascending, (bool, np.bool_)):
+        raise ValueError(f"orderBy: ascending={ascending!r}; True or False")
+    if not isinstance(column, str) or column not in BEST_BY or column not in allowed:
+        legal = ", ".join(repr(b) for b in BEST_BY if b in allowed) or "none (the frame is not scored)"
+        raise ValueError(f"orderBy: column {column!r}; supported: one score column of the frame ({legal}); ordering "
+                         "by several columns or by gamma columns is not offered")
+    return BEST_BY[column], (TOP_ASC if ascending else TOP_DESC), k
+
+
+def top_order(score, order):
+    """The positions of `score`'s elements (given in ascending ordinal) in the order of spk_select_top: NULL (NaN)
+    lowest, -0.0 equal to +0.0, ties by position.  TOP_FIRST: the positions as they are."""
+    score = np.asarray(score, dtype=np.float64)
+    n = len(score)
+    if order == TOP_FIRST:
+        return np.arange(n, dtype=np.int64)
+    null = np.isnan(score)
+    val = np.where(null, -np.inf, score) + 0.0  # -0.0 + 0.0 = +0.0
+    pos = np.arange(n, dtype=np.int64)
+    if order == TOP_ASC:
+        return np.lexsort((pos, val, ~null))        # NULLs first, then by value, then by position
+    return np.lexsort((pos, -val, null))            # by value descending, NULLs last
+
+
 @dataclass(frozen=True)
 class Term:
     field: int    # FIELD_MP / FIELD_GAMMA / FIELD_TF

@@ -118,6 +118,19 @@ class TermFrequencyFrame(SplinkDataFrame):
              else self.filter(f"tf_adjusted_match_prob > {threshold!r}"))
         return f.best_matches(per=per, ties=ties)
 
+    def orderBy(self, col, ascending=True):  # noqa: N802 (Spark name)
+        """tf.orderBy("tf_adjusted_match_prob", ascending=False).limit(k): the first k pairs by tf_adjusted_match_prob
+        (or match_probability), selected on the device.  Shorthand for the same call on the unfiltered frame."""
+        from .select import Predicate
+        return TfFilteredFrame(self, Predicate()).orderBy(col, ascending)
+
+    sort = orderBy
+
+    def limit(self, k):
+        """The first k pairs of this frame, in its order: shorthand for the same call on the unfiltered frame."""
+        from .select import Predicate
+        return TfFilteredFrame(self, Predicate()).limit(k)
+
     def truth_table(self, label_column, thresholds=None):
         """The confusion matrix of `tf_adjusted_match_prob > threshold` against the labels in the input column
         `label_column`, with df_e.truth_table's columns: the score is decided per pair on the device
