@@ -992,6 +992,61 @@ int spk_label_scores_selection(spk_ctx *ctx, const int64_t *label_ids0, const in
  * the counting kernel; the uploads, the value-id staging and the read-backs are not in it), -1 otherwise. */
 int spk_label_scores_info(spk_ctx *ctx, int64_t *out_pairs, double *out_ms);
 
+/* ---- scores against a table of labelled pairs, per pair (replaces taking every tf-scored pair, or every survivor of
+ *      a filter or a best-match step, to the host and merging it there with a table of reviewed pairs) ---- */
+/* spk_label_scores_*'s counts with the truth state of a pair looked up in a set of n_labels labelled pairs, as
+ * spk_label_pairs_histogram looks it up: the same table, key, orientation rule, hash and capacity rule; MATCH and
+ * NON_MATCH hold the labelled pairs, UNKNOWN every pair without a label; n_labels = 0 is legal and makes every pair
+ * UNKNOWN.  rows_l / rows_r / is_match as for spk_label_pairs_histogram.  The score of a pair and its bin are those of
+ * spk_label_scores_tf* (spk_label_pairs_scores_tf*: every pair of the context, tf_adjusted_match_prob by the one
+ * shared device function, bit for bit what spk_tf_apply* gives, mp from a pattern table built for the call and never
+ * from spk_score's scores) and of spk_label_scores_selection (spk_label_pairs_scores_selection: the survivors of the
+ * selection, `field` SPK_SEL_MP or SPK_SEL_TF_MP): bin(s) = the number of k with s > thresholds[k], a NaN (NULL) score
+ * in bin n_thresholds + 1; out_counts[s * (n_thresholds + 2) + bin], state-major.  The three rows sum, bin for bin, to
+ * what spk_label_scores_* counts for the same pairs with every label id non-NULL.  The counts are exact integers that
+ * do not depend on launch shape or on the arrival order of the atomics: ranks holding shards sum them.
+ * out_label_pair[i] (optional) is the index of the pair that label i names -- the context's pair index for
+ * spk_label_pairs_scores_tf*, the survivor index (spk_select_copy's) for spk_label_pairs_scores_selection -- and -1
+ * when no such pair is among them; if a hand-loaded pair set repeats the pair, the largest index.
+ * out_label_score[i] (optional) is the score of exactly that pair, NaN when there is none or its score is NULL.
+ * SPK_E_INVALID: NULL rows_l / rows_r / is_match with n_labels > 0; NULL out_counts; more than
+ * SPK_LABEL_SCORE_MAX_THRESHOLDS thresholds, a NaN threshold or a descending pair of them; NULL m / u, n_tf_cols outside
+ * 1..8 (the tf calls); an unknown field (the selection call); an is_match other than 0 / 1; a row outside its table;
+ * l == r on a one-table job; a pair given twice (in either order on a one-table job) -- the last four are found on
+ * the device before any pair is counted.  SPK_E_STATE: no comparison codes; no pair rows (a loaded gamma table); a
+ * pair that names a row outside its table or a code outside the pattern space (it is not counted); a damaged table;
+ * the selection call: no selection, a stale one, SPK_SEL_MP on a selection made without m / u, SPK_SEL_TF_MP on one not
+ * made by spk_select_tf*.  SPK_E_LIMIT: more than 2^27 labels.
+ * The calls read the pairs, codes and tables (the selection call: the selection) and write nothing of the context but
+ * the numbers of spk_label_pairs_scores_info: the selection, the scores of spk_score, the device-resident tf results,
+ * the tf sums, EM and component state are untouched, and every device buffer of a call is freed before it returns. */
+int spk_label_pairs_scores_tf(spk_ctx *ctx, int64_t n_labels,
+                              const int32_t *rows_l, const int32_t *rows_r /* host, device row order */,
+                              const uint8_t *is_match                      /* host, 0 / 1 */,
+                              double lambda, double one_minus, const double *m, const double *u, int n_tf_cols,
+                              const int64_t *const *ids_side0, const int64_t *const *ids_side1,
+                              const double *const *adj_tables, const int64_t *table_sizes, int n_thresholds,
+                              const double *thresholds,
+                              uint64_t *out_counts      /* host [SPK_LABEL_STATES x (n_thresholds + 2)], state-major */,
+                              int64_t  *out_label_pair  /* host [n_labels] or NULL */,
+                              double   *out_label_score /* host [n_labels] or NULL */);
+int spk_label_pairs_scores_tf_columns(spk_ctx *ctx, int64_t n_labels, const int32_t *rows_l, const int32_t *rows_r,
+                                      const uint8_t *is_match, double lambda, double one_minus, const double *m,
+                                      const double *u, int n_tf_cols, const int32_t *cols,
+                                      const double *const *adj_tables, const int64_t *table_sizes, int n_thresholds,
+                                      const double *thresholds, uint64_t *out_counts, int64_t *out_label_pair,
+                                      double *out_label_score);
+int spk_label_pairs_scores_selection(spk_ctx *ctx, int64_t n_labels, const int32_t *rows_l, const int32_t *rows_r,
+                                     const uint8_t *is_match, int field /* SPK_SEL_MP | SPK_SEL_TF_MP */,
+                                     int n_thresholds, const double *thresholds, uint64_t *out_counts,
+                                     int64_t *out_label_pair, double *out_label_score);
+/* The last spk_label_pairs_scores_*: pairs counted; with timing on the device milliseconds of its launches (table
+ * clear, build, pattern table, counter clear, the counting kernel and the per-label kernel; the uploads, the value-id
+ * staging and the read-backs are not in it), -1.0 otherwise; the table's capacity in slots; the longest insert probe
+ * (0 without labels).  -1 / -1.0 / -1 / -1: none yet, or the last call failed. */
+int spk_label_pairs_scores_info(spk_ctx *ctx, int64_t *out_pairs, double *out_ms, int64_t *out_capacity,
+                                int *out_max_probe);
+
 /* ---- term-frequency adjustment (term_frequencies.py:122-168) ------------------- */
 /* For value ids of one column (per row, -1 NULL; both sides in one id space) accumulate, over
  * pairs with equal non-null values, Σ mp and count(mp) per value id (n_values slots), after spk_score.

@@ -23,7 +23,7 @@ from .frames import (BestMatchFrame, ClusterBridges, ClusterFrame, ClusterMetric
                      SampleFrame, SplinkDataFrame, TopFrame)
 from .gammas import add_gammas
 from .iterate import iterate
-from .labels import (LabelCounts, PairLabelCounts, ScoreLabelCounts, estimate_from_labels,
+from .labels import (LabelCounts, PairLabelCounts, PairScoreLabelCounts, ScoreLabelCounts, estimate_from_labels,
                      estimate_from_pair_labels)
 from .params import Params, load_params_from_json
 from .sampling import estimate_u_using_random_sampling, random_pairs
@@ -36,7 +36,7 @@ from .validate import validate_settings
 __all__ = ["Splink", "load_from_json", "AmdSession", "session", "Params", "block_using_rules", "add_gammas",
            "iterate", "run_expectation_step", "make_adjustment_for_term_frequencies", "complete_settings_dict",
            "ClusterFrame", "ClusterSweepFrame", "ClusterMetrics", "ClusterBridges", "FilteredFrame", "BestMatchFrame", "SampleFrame", "TopFrame", "asc", "desc", "LabelCounts", "ScoreLabelCounts", "estimate_from_labels",
-           "PairLabelCounts", "estimate_from_pair_labels",
+           "PairLabelCounts", "PairScoreLabelCounts", "estimate_from_pair_labels",
            "estimate_u_using_random_sampling", "random_pairs", "get_largest_blocks", "profile_blocking_rules",
            "BlockingProfile"]
 

@@ -96,6 +96,8 @@ EXPORTS = [
     "spk_label_histogram", "spk_label_info",
     "spk_label_pairs_histogram", "spk_label_pairs_info",
     "spk_label_scores_tf", "spk_label_scores_tf_columns", "spk_label_scores_selection", "spk_label_scores_info",
+    "spk_label_pairs_scores_tf", "spk_label_pairs_scores_tf_columns", "spk_label_pairs_scores_selection",
+    "spk_label_pairs_scores_info",
     "spk_cluster_agreement", "spk_cluster_agreement_info",
     "spk_pairs_sample", "spk_pairs_sample_info",
     "spk_block_profile", "spk_block_profile_info", "spk_block_profile_set_cut",
@@ -124,6 +126,9 @@ LABEL_SCORE_MAX_THRESHOLDS = 1024  # SPK_LABEL_SCORE_MAX_THRESHOLDS
 # the tests' edge sizes depend on them.
 LABEL_SCORE_STEP = 256 * 8
 LABEL_SCORE_WG_PER_CU = 3
+# The same for spk_label_pairs_scores_tf*'s kernel.  Mirrored from LS_THREADS, LPS_PAIRS and LPS_WAVES_PER_SIMD.
+LABEL_PAIR_SCORE_STEP = 256 * 4
+LABEL_PAIR_SCORE_WG_PER_CU = 6
 AGREE_FIELDS = 10  # SPK_AGREE_FIELDS: the columns of cluster_agreement, in labels.AGREEMENT_FIELDS' order
 TF_LIMBS = 14  # SPK_TF_LIMBS
 
@@ -1248,6 +1253,98 @@ class Context:
         ms = ctypes.c_double(-1.0)
         check(self._lib.spk_label_scores_info(self._h, ctypes.byref(n), ctypes.byref(ms)), "spk_label_scores_info")
         return n.value, ms.value
+
+    # ---- scores against a table of labelled pairs, per pair ------------------------------------
+    @staticmethod
+    def _pair_score_args(rows_l, rows_r, is_match, thresholds, what):
+        """(rows_l int32, rows_r int32, is_match uint8, thresholds float64, zeroed counts uint64 [3, T + 2], label_pair
+        int64 [n], label_score float64 [n]) as the spk_label_pairs_scores_* calls take them."""
+        rows_l = np.ascontiguousarray(rows_l, dtype=np.int32).reshape(-1)
+        rows_r = np.ascontiguousarray(rows_r, dtype=np.int32).reshape(-1)
+        is_match = np.ascontiguousarray(is_match, dtype=np.uint8).reshape(-1)
+        if not len(rows_l) == len(rows_r) == len(is_match):
+            raise ValueError(f"{what}: rows_l, rows_r and is_match differ in length")
+        t = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        n = len(rows_l)
+        return (rows_l, rows_r, is_match, t, np.zeros((LABEL_STATES, len(t) + 2), dtype=np.uint64),
+                np.full(max(n, 1), -1, dtype=np.int64), np.full(max(n, 1), np.nan, dtype=np.float64))
+
+    def label_pair_scores_tf(self, rows_l, rows_r, is_match, lam, one_minus, m, u, ids0_list, ids1_list, tables,
+                             thresholds):
+        """spk_label_pairs_scores_tf: (counts int64 [3, T + 2]: every pair per (LABEL_* state looked up in the labelled
+        pairs, bin of tf_adjusted_match_prob), label_pair int64 [n_labels]: the index of the pair each label names or
+        -1, label_score float64 [n_labels]: that pair's score, NaN = none or NULL).  Labelled pairs as for
+        label_pairs_histogram; parameters, host value ids, tables and bins as for label_scores_tf."""
+        n = len(tables)
+        if len(ids0_list) != n or len(ids1_list) != n:
+            raise ValueError("label_pair_scores_tf: one id array per side and table")
+        keep = [np.ascontiguousarray(a, dtype=np.int64) for a in ids0_list] + \
+               [np.ascontiguousarray(a, dtype=np.int64) for a in ids1_list] + \
+               [np.ascontiguousarray(t, dtype=np.float64) if len(t) else np.zeros(1) for t in tables]
+        P = ctypes.c_void_p * max(n, 1)
+        ids0 = P(*[a.ctypes.data for a in keep[:n]])
+        ids1 = P(*[a.ctypes.data for a in keep[n:2 * n]])
+        tabs = P(*[a.ctypes.data for a in keep[2 * n:]])
+        sizes = np.array([len(t) for t in tables] + [0], dtype=np.int64)
+        rows_l, rows_r, is_match, t, counts, pair, score = self._pair_score_args(rows_l, rows_r, is_match, thresholds,
+                                                                                 "label_pair_scores_tf")
+        k = len(rows_l)
+        m = np.ascontiguousarray(m, dtype=np.float64)
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        check(self._lib.spk_label_pairs_scores_tf(self._h, ctypes.c_int64(k), _ptr(rows_l if k else None),
+                                                  _ptr(rows_r if k else None), _ptr(is_match if k else None),
+                                                  ctypes.c_double(lam), ctypes.c_double(one_minus), _ptr(m), _ptr(u),
+                                                  ctypes.c_int(n), ids0, ids1, tabs, _ptr(sizes), ctypes.c_int(len(t)),
+                                                  _ptr(t) if len(t) else ctypes.c_void_p(0), _ptr(counts), _ptr(pair),
+                                                  _ptr(score)), "spk_label_pairs_scores_tf")
+        return counts.astype(np.int64), pair[:k], score[:k]
+
+    def label_pair_scores_tf_columns(self, rows_l, rows_r, is_match, lam, one_minus, m, u, cols, tables, thresholds):
+        """spk_label_pairs_scores_tf_columns: the same with the value ids taken from the device dictionary ids of the
+        string columns `cols` (as select_tf_columns)."""
+        n = len(tables)
+        if len(cols) != n:
+            raise ValueError("label_pair_scores_tf_columns: one column per table")
+        keep = [np.ascontiguousarray(t, dtype=np.float64) if len(t) else np.zeros(1) for t in tables]
+        tabs = (ctypes.c_void_p * max(n, 1))(*[a.ctypes.data for a in keep])
+        sizes = np.array([len(t) for t in tables] + [0], dtype=np.int64)
+        cols = np.ascontiguousarray(list(cols) + [0], dtype=np.int32)
+        rows_l, rows_r, is_match, t, counts, pair, score = self._pair_score_args(rows_l, rows_r, is_match, thresholds,
+                                                                                 "label_pair_scores_tf_columns")
+        k = len(rows_l)
+        m = np.ascontiguousarray(m, dtype=np.float64)
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        check(self._lib.spk_label_pairs_scores_tf_columns(self._h, ctypes.c_int64(k), _ptr(rows_l if k else None),
+                                                          _ptr(rows_r if k else None), _ptr(is_match if k else None),
+                                                          ctypes.c_double(lam), ctypes.c_double(one_minus), _ptr(m),
+                                                          _ptr(u), ctypes.c_int(n), _ptr(cols), tabs, _ptr(sizes),
+                                                          ctypes.c_int(len(t)),
+                                                          _ptr(t) if len(t) else ctypes.c_void_p(0), _ptr(counts),
+                                                          _ptr(pair), _ptr(score)), "spk_label_pairs_scores_tf_columns")
+        return counts.astype(np.int64), pair[:k], score[:k]
+
+    def label_pair_scores_selection(self, rows_l, rows_r, is_match, field: int, thresholds):
+        """spk_label_pairs_scores_selection: the same three over the survivors of the last select* (or select_best),
+        by `field` (SEL_MP or SEL_TF_MP); label_pair is the survivor's index (select_copy's)."""
+        rows_l, rows_r, is_match, t, counts, pair, score = self._pair_score_args(rows_l, rows_r, is_match, thresholds,
+                                                                                 "label_pair_scores_selection")
+        k = len(rows_l)
+        check(self._lib.spk_label_pairs_scores_selection(self._h, ctypes.c_int64(k), _ptr(rows_l if k else None),
+                                                         _ptr(rows_r if k else None), _ptr(is_match if k else None),
+                                                         ctypes.c_int(int(field)), ctypes.c_int(len(t)),
+                                                         _ptr(t) if len(t) else ctypes.c_void_p(0), _ptr(counts),
+                                                         _ptr(pair), _ptr(score)), "spk_label_pairs_scores_selection")
+        return counts.astype(np.int64), pair[:k], score[:k]
+
+    def label_pair_scores_info(self):
+        """(pairs the last label_pair_scores_* counted, ms of its launches with timing on, slots of its hash table, its
+        longest insert probe); (-1, -1.0, -1, -1): none yet, or the last call failed."""
+        n, cap = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        ms = ctypes.c_double(-1.0)
+        probe = ctypes.c_int(-1)
+        check(self._lib.spk_label_pairs_scores_info(self._h, ctypes.byref(n), ctypes.byref(ms), ctypes.byref(cap),
+                                                    ctypes.byref(probe)), "spk_label_pairs_scores_info")
+        return n.value, ms.value, cap.value, probe.value
 
     # ---- clusters against labels --------------------------------------------------------------
     def cluster_agreement(self, ids, n_left: int = 0, cross_only: bool = False) -> np.ndarray:

@@ -545,6 +545,10 @@ struct spk_ctx {
     int64_t lpairs_pairs = -1, lpairs_capacity = -1;
     double lpairs_ms = -1.0;
     int lpairs_max_probe = -1;
+    // the last spk_label_pairs_scores_* (spk_labels.hip): the same four numbers; its buffers live for the call only
+    int64_t lpscore_pairs = -1, lpscore_capacity = -1;
+    double lpscore_ms = -1.0;
+    int lpscore_max_probe = -1;
     // the last spk_cluster_agreement (spk_agreement.hip): levels it scored (-1: none yet), device milliseconds of its
     // launches; a failing call leaves both as they were, and its buffers live for the call only
     int agree_levels = -1;

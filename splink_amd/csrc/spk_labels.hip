@@ -408,6 +408,19 @@ static unsigned score_grid(const spk_ctx *ctx, int64_t P, int per_lane, int wg_p
 
 static size_t score_lds_bytes(int T) { return (size_t)T * 8 + (size_t)3 * (T + 2) * 4; }
 
+// The thresholds of a per-pair scoring call: 0..SPK_LABEL_SCORE_MAX_THRESHOLDS ascending doubles, no NaN.
+static int check_thresholds(const char *what, int n_thresholds, const double *thresholds) {
+    const std::string w(what);
+    SPK_REQUIRE(n_thresholds >= 0 && n_thresholds <= SPK_LABEL_SCORE_MAX_THRESHOLDS, SPK_E_INVALID,
+                w + ": 0..SPK_LABEL_SCORE_MAX_THRESHOLDS (1024) thresholds");
+    SPK_REQUIRE(n_thresholds == 0 || thresholds, SPK_E_INVALID, w + ": null thresholds");
+    for (int k = 0; k < n_thresholds; ++k) {
+        SPK_REQUIRE(thresholds[k] == thresholds[k], SPK_E_INVALID, w + ": a threshold is NaN");
+        SPK_REQUIRE(k == 0 || thresholds[k] >= thresholds[k - 1], SPK_E_INVALID, w + ": the thresholds descend");
+    }
+    return SPK_OK;
+}
+
 // What the spk_label_scores_* entry points share.  check(): the arguments (SPK_E_INVALID).  stage(): the label ids and
 // thresholds on the device and zeroed counters.  finish(): the read-back, behind the interval's end.
 struct ScoreCall {
@@ -427,13 +440,7 @@ struct ScoreCall {
         SPK_REQUIRE(ctx->link_type != SPK_LINK_ONLY || ids1, SPK_E_INVALID,
                     w + ": link_only needs the right table's label_ids1");
         SPK_REQUIRE(out_counts, SPK_E_INVALID, w + ": null out_counts");
-        SPK_REQUIRE(n_thresholds >= 0 && n_thresholds <= SPK_LABEL_SCORE_MAX_THRESHOLDS, SPK_E_INVALID,
-                    w + ": 0..SPK_LABEL_SCORE_MAX_THRESHOLDS (1024) thresholds");
-        SPK_REQUIRE(n_thresholds == 0 || thresholds, SPK_E_INVALID, w + ": null thresholds");
-        for (int k = 0; k < n_thresholds; ++k) {
-            SPK_REQUIRE(thresholds[k] == thresholds[k], SPK_E_INVALID, w + ": a threshold is NaN");
-            SPK_REQUIRE(k == 0 || thresholds[k] >= thresholds[k - 1], SPK_E_INVALID, w + ": the thresholds descend");
-        }
+        SPK_TRY(check_thresholds(what, n_thresholds, thresholds));
         T = n_thresholds;
         return SPK_OK;
     }
@@ -658,6 +665,27 @@ __device__ __forceinline__ uint32_t lp_bin(const PairLabelArgs &A, uint64_t key,
     return 0xFFFFFFFFu;
 }
 
+// The same walk for the kernels that score the pair themselves (spk_label_pairs_scores_*): the pair's truth state and
+// in `at` the label it hit (LP_NO_LABEL: none), or LP_DAMAGED for a table that is damaged.  The same bound.
+constexpr uint32_t LP_NO_LABEL = 0xFFFFFFFFu;
+constexpr uint32_t LP_DAMAGED = (uint32_t)SPK_LABEL_STATES;
+__device__ __forceinline__ uint32_t lp_walk(const PairTable &T, uint64_t key, uint32_t h, unsigned long long w,
+                                            uint32_t &at) {
+    at = LP_NO_LABEL;
+    for (uint32_t left = T.mask; w != LP_EMPTY; --left) {  // left: slots the walk may still move on to
+        if ((w & ~LP_MATCH_BIT) == key) {
+            const uint32_t i = T.index[h];
+            if (i >= T.n_labels) return LP_DAMAGED;  // a slot that names no label
+            at = i;
+            return (uint32_t)((w >> 62) & 1ull);
+        }
+        if (left == 0u) return LP_DAMAGED;  // every slot read
+        h = (h + 1u) & T.mask;
+        w = T.slot[h];
+    }
+    return (uint32_t)SPK_LABEL_UNKNOWN;
+}
+
 // k_label_hist with the two label gathers replaced by the probe: the same 8 pairs per lane and step, the same tail
 // wave, label_add and LDS flush.  Per step a lane first issues the home-slot loads of all its pairs, so that they are in
 // flight together as k_label_hist's gathers are, and only then walks on where a home slot held another key.
@@ -738,6 +766,445 @@ static int launch_label_pairs_hist(spk_ctx *ctx, const PairLabelArgs &A, bool ld
     else k_label_pairs_hist<CodeT, false><<<g, LH_THREADS, 0, ctx->stream>>>(A, codes);
     SPK_HIP(hipGetLastError());
     return SPK_OK;
+}
+
+// The table of labelled pairs of one call on the device: locals of the entry points that look pairs up in it.
+struct PairTableStage {
+    DevBuf<unsigned long long> slot;
+    DevBuf<uint32_t> index;
+    DevBuf<int32_t> d_l, d_r;
+    DevBuf<uint8_t> d_match;
+    DevBuf<unsigned int> flags;  // [0] the bad bits (0 after a good build: the counting kernels' from then on), [1] the
+                                 // longest insert probe
+    int64_t capacity = 0;
+    int max_probe = 0;
+    PairTable tab{};
+};
+
+// Uploads the labels, clears the table and inserts them (k_label_pairs_build, inside T's intervals; the uploads are no
+// launches: outside them), then reads the flags back: what is wrong with the labels is SPK_E_INVALID under `what`,
+// known before a pair is counted.  Leaves S.flags[0] = 0 and the stream synchronised.
+static int stage_pair_table(spk_ctx *ctx, const char *what, int64_t n_labels, const int32_t *rows_l,
+                            const int32_t *rows_r, const uint8_t *is_match, int64_t n0, int64_t n1, StageTimer &T,
+                            PairTableStage &S) {
+    const std::string w(what);
+    hipStream_t st = ctx->stream;
+    S.capacity = 64;
+    while (S.capacity < 2 * n_labels) S.capacity *= 2;
+    SPK_TRY(S.slot.alloc((size_t)S.capacity));
+    SPK_TRY(S.index.alloc((size_t)S.capacity));
+    SPK_TRY(S.flags.alloc(2));
+    S.tab = PairTable{S.slot.p, S.index.p, (uint32_t)(S.capacity - 1), (uint32_t)n_labels,
+                      ctx->link_type == SPK_LINK_ONLY};
+    if (n_labels > 0) {
+        SPK_TRY(S.d_l.alloc((size_t)n_labels));
+        SPK_TRY(S.d_r.alloc((size_t)n_labels));
+        SPK_TRY(S.d_match.alloc((size_t)n_labels));
+        SPK_HIP(hipMemcpyAsync(S.d_l.p, rows_l, (size_t)n_labels * 4, hipMemcpyHostToDevice, st));
+        SPK_HIP(hipMemcpyAsync(S.d_r.p, rows_r, (size_t)n_labels * 4, hipMemcpyHostToDevice, st));
+        SPK_HIP(hipMemcpyAsync(S.d_match.p, is_match, (size_t)n_labels, hipMemcpyHostToDevice, st));
+    }
+    SPK_TRY(T.open());
+    SPK_HIP(hipMemsetAsync(S.flags.p, 0, 2 * sizeof(unsigned int), st));
+    SPK_HIP(hipMemsetAsync(S.slot.p, 0xFF, (size_t)S.capacity * 8, st));
+    if (n_labels > 0) {
+        k_label_pairs_build<<<(unsigned)((n_labels + LP_BUILD_THREADS - 1) / LP_BUILD_THREADS), LP_BUILD_THREADS, 0,
+                              st>>>(n_labels, S.d_l.p, S.d_r.p, S.d_match.p, (uint32_t)n0, (uint32_t)n1, S.tab,
+                                    S.flags.p);
+        SPK_HIP(hipGetLastError());
+    }
+    SPK_TRY(T.stop());
+    unsigned int h_flags[2] = {0u, 0u};
+    SPK_HIP(hipMemcpyAsync(h_flags, S.flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, st));
+    SPK_HIP(hipStreamSynchronize(st));
+    SPK_TRY(T.add());
+    SPK_REQUIRE(!(h_flags[0] & LP_BAD_FLAG), SPK_E_INVALID, w + ": an is_match other than 0 or 1");
+    SPK_REQUIRE(!(h_flags[0] & LP_BAD_ROW), SPK_E_INVALID, w + ": a labelled pair names a row outside its table");
+    SPK_REQUIRE(!(h_flags[0] & LP_BAD_SELF), SPK_E_INVALID, w + ": a labelled pair of a record with itself");
+    SPK_REQUIRE(!(h_flags[0] & LP_BAD_TWICE), SPK_E_INVALID, w + ": a labelled pair given twice");
+    SPK_REQUIRE(h_flags[0] == 0u, SPK_E_STATE, w + ": the pair table is full");
+    S.max_probe = (int)h_flags[1];
+    return SPK_OK;
+}
+
+// ---- scores against a table of labelled pairs, per pair ------------------------------------------------------
+// spk_label_pairs_scores_*: the counting of spk_label_scores_* with the truth state of a pair looked up in the table
+// of spk_label_pairs_histogram instead of gathered from two per-record ids.  The same thresholds, bins, LDS counters
+// and flush (score_lds_init / score_bin / score_lds_flush); the same table, key, hash and bounded walk (lp_key /
+// lp_fmix64 / lp_walk).  A pair that hits label i also raises found[i] to 1 + its index (a 64-bit atomicMax), and
+// a second launch, one thread per label, scores exactly the pair found: a hand-loaded pair set that repeats a
+// labelled pair gives the largest index whatever the arrival order, and no score is written from a race.
+//
+// Pairs per lane and step (4 or 8), and the waves per SIMD the registers are held to, which is also the workgroups
+// per CU the grid is capped at (compile-time switches for tools/ab_label_pair_scores.py's A/B).  The keys, home slots
+// and words of the probe are dead before the tf fold starts, so the union costs no more registers than the fold: 128
+// VGPRs with 8 pairs per lane (4 waves per SIMD), 70 with 4 (7 waves), no scratch in either; held to 8 waves (64
+// VGPRs) the 4-pair form spills 20 bytes and is not offered.  The pass is bound by the latency of its dependent
+// gathers (probe, then value ids, then table entries), so resident waves win over pairs per lane.  cfg2 (46 M
+// pairs), device ms of the call at T = 72 with 10^3 / 10^5 / 10^7 labels: 8 pairs at 3 waves 1.09 / 0.95 / 4.11, at 4
+// waves 0.93 / 0.83 / 3.94; 4 pairs at 4 waves 1.03 / 0.91 / 3.89, at 6 waves 0.86 / 0.76 / 3.71
+// (profiles/ab_label_pair_scores.log).
+#ifndef SPK_LABEL_PAIR_SCORE_PAIRS
+#define SPK_LABEL_PAIR_SCORE_PAIRS 4
+#endif
+#ifndef SPK_LABEL_PAIR_SCORE_WAVES
+#define SPK_LABEL_PAIR_SCORE_WAVES 6
+#endif
+constexpr int LPS_PAIRS = SPK_LABEL_PAIR_SCORE_PAIRS;
+constexpr int LPS_WAVES_PER_SIMD = SPK_LABEL_PAIR_SCORE_WAVES;  // = workgroups per CU: a workgroup puts one wave on each SIMD
+constexpr int LPS_SEL_WG_PER_CU = 8;
+static_assert(LPS_PAIRS == 4 || LPS_PAIRS == 8, "4 or 8 pairs per lane");
+
+struct PairScoreArgs {
+    ScoreArgs S;                // lab0 / lab1 are not read; *S.bad takes the LP_BAD_* bits
+    PairTable T;
+    unsigned long long *found;  // [n_labels], zeroed before the launch: 1 + the largest index of a pair that hit the
+                                // label; or null
+};
+
+__device__ __forceinline__ void score_add_state(uint32_t *cnt, const ScoreArgs &A, const double *th, uint32_t state,
+                                                double s) {
+    atomicAdd(&cnt[state * ((uint32_t)A.T + 2u) + score_bin(s, th, (uint32_t)A.T, A.top)], 1u);
+}
+
+// V consecutive codes of step v, coalesced: 8, 16 or 32 bytes per lane
+template <typename CodeT, int V>
+__device__ __forceinline__ void lps_load_codes(const CodeT *__restrict__ codes, int64_t v, uint32_t (&c)[V]) {
+    constexpr int BYTES = V * (int)sizeof(CodeT);
+    if constexpr (BYTES == 8) {
+        const uint2 w = reinterpret_cast<const uint2 *>(codes)[v];
+        c[0] = w.x & 0xFFFFu, c[1] = w.x >> 16, c[2] = w.y & 0xFFFFu, c[3] = w.y >> 16;
+    } else {
+        constexpr int CW = BYTES / 16;
+        uint4 w[CW];
+#pragma unroll
+        for (int j = 0; j < CW; ++j) w[j] = reinterpret_cast<const uint4 *>(codes)[CW * v + j];
+        const CodeT *e = reinterpret_cast<const CodeT *>(w);
+#pragma unroll
+        for (int j = 0; j < V; ++j) c[j] = (uint32_t)e[j];
+    }
+}
+
+// Every pair of the context against the table, by tf_adjusted_match_prob: k_label_scores_tf's loop with the two label
+// gathers replaced by k_label_pairs_hist's probe.  Per step a lane issues the home-slot loads and the mp gathers of
+// all its pairs together, walks on only where a home slot held another key (lp_walk: bounded by the capacity), and
+// then folds the tf columns as k_label_scores_tf does.  The states of the lane's pairs are packed two bits each.
+template <typename CodeT, int V>
+__global__ __launch_bounds__(LS_THREADS, LPS_WAVES_PER_SIMD) void k_label_pairs_scores_tf(
+    PairScoreArgs B, TfApply F, const CodeT *__restrict__ codes) {
+    extern __shared__ __attribute__((aligned(16))) double s_th[];
+    const ScoreArgs &A = B.S;
+    uint32_t *cnt = score_lds_init(A, s_th);
+    const int lane = threadIdx.x & 63;
+    const int64_t n_vec = A.P / V;
+    const uint4 *lv = reinterpret_cast<const uint4 *>(A.pl);
+    const uint4 *rv = reinterpret_cast<const uint4 *>(A.pr);
+    constexpr int RW = V / 4;  // 16-byte row vectors per side and step
+    for (int64_t v = (int64_t)blockIdx.x * LS_THREADS + threadIdx.x;; v += (int64_t)gridDim.x * LS_THREADS) {
+        const bool in = v < n_vec;
+        if (!__any(in)) break;  // wave-uniform
+        uint32_t l[V], r[V], c[V];
+        unsigned ok = 0;  // bit j: pair j is inside P and names rows and a code in range
+#pragma unroll
+        for (int j = 0; j < V; ++j) l[j] = r[j] = c[j] = 0u;
+        if (in) {
+#pragma unroll
+            for (int k = 0; k < RW; ++k) {
+                const uint4 a = lv[RW * v + k], b = rv[RW * v + k];
+                l[4 * k] = a.x, l[4 * k + 1] = a.y, l[4 * k + 2] = a.z, l[4 * k + 3] = a.w;
+                r[4 * k] = b.x, r[4 * k + 1] = b.y, r[4 * k + 2] = b.z, r[4 * k + 3] = b.w;
+            }
+            lps_load_codes<CodeT, V>(codes, v, c);
+#pragma unroll
+            for (int j = 0; j < V; ++j) ok |= (l[j] < A.n0 && r[j] < A.n1 && c[j] < A.n_pat ? 1u : 0u) << j;
+            if (ok != (1u << V) - 1u) atomicOr(A.bad, LP_BAD_PAIR);
+        }
+        double m[V], a[V], b[V];
+        unsigned states = 0;  // two bits per pair
+        {
+            uint64_t key[V];
+            uint32_t h[V];
+            unsigned long long w[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) {  // all the home slots and the mp gathers first
+                key[j] = lp_key(B.T, l[j], r[j]);
+                h[j] = (uint32_t)lp_fmix64(key[j]) & B.T.mask;
+                w[j] = LP_EMPTY;
+                m[j] = 0.0;
+                if ((ok >> j) & 1u) {
+                    w[j] = B.T.slot[h[j]];
+                    m[j] = A.mpat[c[j]];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                uint32_t at;
+                const uint32_t s = lp_walk(B.T, key[j], h[j], w[j], at);
+                if (s == LP_DAMAGED) {  // the pair is not counted
+                    atomicOr(A.bad, LP_BAD_TABLE);
+                    ok &= ~(1u << j);
+                } else if (at != LP_NO_LABEL && B.found) {
+                    atomicMax(&B.found[at], (unsigned long long)(v * V + j) + 1ull);
+                }
+                states |= (s & 3u) << (2 * j);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) tf_begin(m[j], a[j], b[j]);
+        for (int t = 0; t < F.n; ++t) {
+            const int64_t *__restrict__ i0 = F.ids0[t];
+            const int64_t *__restrict__ i1 = F.ids1[t];
+            const double *__restrict__ tab = F.tab[t];
+            const int64_t tab_n = F.tab_n[t];
+            int64_t ia[V], ib[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                ia[j] = ib[j] = -1;
+                if ((ok >> j) & 1u) {
+                    ia[j] = i0[l[j]];
+                    ib[j] = i1[r[j]];
+                }
+            }
+            double x[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) x[j] = tf_adj(ia[j], ib[j], tab, tab_n);  // -1: no load; an id past the table: 0.5
+#pragma unroll
+            for (int j = 0; j < V; ++j) tf_fold(a[j], b[j], x[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j)
+            if ((ok >> j) & 1u) score_add_state(cnt, A, s_th, (states >> (2 * j)) & 3u, tf_finish(m[j], a[j], b[j]));
+    }
+    // tail (P not a multiple of V): workgroup 0's first wave, one pair per lane
+    if (blockIdx.x == 0 && threadIdx.x < 64) {
+        const int64_t p = n_vec * V + lane;
+        if (p < A.P) {
+            const uint32_t l = (uint32_t)A.pl[p], r = (uint32_t)A.pr[p], c = (uint32_t)codes[p];
+            if (l < A.n0 && r < A.n1 && c < A.n_pat) {
+                const uint64_t key = lp_key(B.T, l, r);
+                const uint32_t h = (uint32_t)lp_fmix64(key) & B.T.mask;
+                uint32_t at;
+                const uint32_t s = lp_walk(B.T, key, h, B.T.slot[h], at);
+                if (s == LP_DAMAGED) {
+                    atomicOr(A.bad, LP_BAD_TABLE);
+                } else {
+                    if (at != LP_NO_LABEL && B.found) atomicMax(&B.found[at], (unsigned long long)p + 1ull);
+                    score_add_state(cnt, A, s_th, s, tf_pair(F, A.mpat[c], (int32_t)l, (int32_t)r, nullptr));
+                }
+            } else {
+                atomicOr(A.bad, LP_BAD_PAIR);
+            }
+        }
+    }
+    score_lds_flush(A, cnt);
+}
+
+// The survivors of a selection against the table: k_label_scores_sel with the same replacement.
+__global__ __launch_bounds__(LS_THREADS) void k_label_pairs_scores_sel(PairScoreArgs B) {
+    extern __shared__ __attribute__((aligned(16))) double s_th[];
+    const ScoreArgs &A = B.S;
+    uint32_t *cnt = score_lds_init(A, s_th);
+    for (int64_t q = (int64_t)blockIdx.x * LS_THREADS + threadIdx.x; q < A.P; q += (int64_t)gridDim.x * LS_THREADS) {
+        const uint32_t l = (uint32_t)A.pl[q], r = (uint32_t)A.pr[q], c = A.code[q];
+        if (l < A.n0 && r < A.n1 && c < A.n_pat) {
+            const uint64_t key = lp_key(B.T, l, r);
+            const uint32_t h = (uint32_t)lp_fmix64(key) & B.T.mask;
+            uint32_t at;
+            const uint32_t s = lp_walk(B.T, key, h, B.T.slot[h], at);
+            if (s == LP_DAMAGED) {
+                atomicOr(A.bad, LP_BAD_TABLE);
+            } else {
+                if (at != LP_NO_LABEL && B.found) atomicMax(&B.found[at], (unsigned long long)q + 1ull);
+                score_add_state(cnt, A, s_th, s, A.per_pair ? A.per_pair[q] : A.mpat[c]);
+            }
+        } else {
+            atomicOr(A.bad, LP_BAD_PAIR);
+        }
+    }
+    score_lds_flush(A, cnt);
+}
+
+// One label per thread, after the counting: the index of the pair found (-1: none) and the score of exactly that
+// pair (NaN: none), by tf_pair over the context's pairs and codes (tf) or from the selection's own scores (codes =
+// the survivors' codes).  found[i] was only raised by pairs that the counting kernel found in range.
+template <typename CodeT>
+__global__ __launch_bounds__(LP_BUILD_THREADS) void k_label_pairs_scores_found(int64_t n, PairScoreArgs B, bool tf,
+                                                                               TfApply F,
+                                                                               const CodeT *__restrict__ codes,
+                                                                               int64_t *__restrict__ out_pair,
+                                                                               double *__restrict__ out_score) {
+    const int64_t i = (int64_t)blockIdx.x * LP_BUILD_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const ScoreArgs &A = B.S;
+    const int64_t q = (int64_t)B.found[i] - 1;
+    double s = NAN;
+    if (q >= 0 && q < A.P) {
+        if (tf) s = tf_pair(F, A.mpat[(uint32_t)codes[q]], A.pl[q], A.pr[q], nullptr);
+        else s = A.per_pair ? A.per_pair[q] : A.mpat[(uint32_t)codes[q]];
+    }
+    out_pair[i] = q < A.P ? q : -1;
+    out_score[i] = s;
+}
+
+// What the spk_label_pairs_scores_* entry points share.  check(): the arguments (SPK_E_INVALID).  stage(): the table
+// of labelled pairs (stage_pair_table: the label faults), the thresholds and the per-label words on the device.
+// count_from(): zeroed counters and words inside the open interval.  finish(): the per-label launch and the read-back.
+struct PairScoreCall {
+    spk_ctx *ctx;
+    const char *what;
+    int T = 0;
+    int64_t n_labels = 0;
+    bool per_label = false;  // out_label_pair or out_label_score is wanted
+    PairTableStage tab;
+    DevBuf<double> thr, d_score;
+    DevBuf<unsigned long long> cnt, found;
+    DevBuf<int64_t> d_pair;
+    StageTimer timer;
+    PairScoreCall(spk_ctx *c, const char *w) : ctx(c), what(w), timer{c} {}
+
+    int check(int64_t n, const int32_t *rows_l, const int32_t *rows_r, const uint8_t *is_match, int n_thresholds,
+              const double *thresholds, const uint64_t *out_counts, const int64_t *out_pair, const double *out_score) {
+        const std::string w(what);
+        SPK_REQUIRE(n >= 0, SPK_E_INVALID, w + ": negative n_labels");
+        SPK_REQUIRE(n == 0 || (rows_l && rows_r && is_match), SPK_E_INVALID, w + ": null rows_l, rows_r or is_match");
+        SPK_REQUIRE(out_counts, SPK_E_INVALID, w + ": null out_counts");
+        SPK_TRY(check_thresholds(what, n_thresholds, thresholds));
+        T = n_thresholds;
+        n_labels = n;
+        per_label = n > 0 && (out_pair || out_score);
+        return SPK_OK;
+    }
+
+    int stage(const int32_t *rows_l, const int32_t *rows_r, const uint8_t *is_match, const double *thresholds,
+              int64_t n0, int64_t n1) {
+        SPK_REQUIRE(n_labels <= LP_MAX_LABELS, SPK_E_LIMIT, std::string(what) + ": more than 2^27 labelled pairs");
+        SPK_REQUIRE((int64_t)score_lds_bytes(T) <= ctx->lds_per_block, SPK_E_LIMIT, std::string(what) + ": LDS");
+        SPK_TRY(thr.alloc((size_t)T + 1));
+        SPK_TRY(cnt.alloc((size_t)3 * (T + 2)));
+        if (per_label) {
+            SPK_TRY(found.alloc((size_t)n_labels));
+            SPK_TRY(d_pair.alloc((size_t)n_labels));
+            SPK_TRY(d_score.alloc((size_t)n_labels));
+        }
+        SPK_TRY(stage_pair_table(ctx, what, n_labels, rows_l, rows_r, is_match, n0, n1, timer, tab));
+        if (T) SPK_HIP(hipMemcpyAsync(thr.p, thresholds, (size_t)T * 8, hipMemcpyHostToDevice, ctx->stream));
+        return SPK_OK;
+    }
+
+    int clear() {  // inside the open interval
+        SPK_HIP(hipMemsetAsync(cnt.p, 0, (size_t)3 * (T + 2) * 8, ctx->stream));
+        if (per_label) SPK_HIP(hipMemsetAsync(found.p, 0, (size_t)n_labels * 8, ctx->stream));
+        return SPK_OK;
+    }
+
+    void fill(PairScoreArgs &B, int64_t P, const int32_t *pl, const int32_t *pr, int64_t n0, int64_t n1) {
+        ScoreArgs &A = B.S;
+        A.P = P;
+        A.pl = pl;
+        A.pr = pr;
+        A.n0 = (uint32_t)n0;
+        A.n1 = (uint32_t)n1;
+        A.n_pat = (uint32_t)ctx->n_patterns;
+        A.T = T;
+        A.top = 0;
+        for (int s = 1; s <= T; s *= 2) A.top = s;
+        A.thr = thr.p;
+        A.gcnt = cnt.p;
+        A.bad = tab.flags.p;
+        B.T = tab.tab;
+        B.found = per_label ? found.p : nullptr;
+    }
+
+    // The per-label launch (tf: by tf_pair over `codes`, the context's; else from the selection's scores and codes).
+    template <typename CodeT>
+    int per_label_launch(const PairScoreArgs &B, bool tf, const TfApply &F, const CodeT *codes) {
+        if (!per_label) return SPK_OK;
+        k_label_pairs_scores_found<CodeT><<<(unsigned)((n_labels + LP_BUILD_THREADS - 1) / LP_BUILD_THREADS),
+                                            LP_BUILD_THREADS, 0, ctx->stream>>>(n_labels, B, tf, F, codes, d_pair.p,
+                                                                                 d_score.p);
+        SPK_HIP(hipGetLastError());
+        return SPK_OK;
+    }
+
+    int finish(int64_t P, uint64_t *out_counts, int64_t *out_pair, double *out_score) {
+        hipStream_t st = ctx->stream;
+        const std::string w(what);
+        unsigned int h_bad = 0u;
+        SPK_TRY(timer.stop());  // the read-backs are no launches
+        SPK_HIP(hipMemcpyAsync(&h_bad, tab.flags.p, sizeof(h_bad), hipMemcpyDeviceToHost, st));
+        SPK_HIP(hipMemcpyAsync(out_counts, cnt.p, (size_t)3 * (T + 2) * 8, hipMemcpyDeviceToHost, st));
+        if (per_label && out_pair)
+            SPK_HIP(hipMemcpyAsync(out_pair, d_pair.p, (size_t)n_labels * 8, hipMemcpyDeviceToHost, st));
+        if (per_label && out_score)
+            SPK_HIP(hipMemcpyAsync(out_score, d_score.p, (size_t)n_labels * 8, hipMemcpyDeviceToHost, st));
+        SPK_HIP(hipStreamSynchronize(st));
+        SPK_TRY(timer.add());
+        SPK_REQUIRE(!(h_bad & LP_BAD_PAIR), SPK_E_STATE,
+                    w + ": a pair names a row outside its table or a code outside the pattern space");
+        SPK_REQUIRE(h_bad == 0u, SPK_E_STATE, w + ": the pair table is damaged");
+        ctx->lpscore_pairs = P;
+        ctx->lpscore_ms = timer.result();
+        ctx->lpscore_capacity = tab.capacity;
+        ctx->lpscore_max_probe = tab.max_probe;
+        return SPK_OK;
+    }
+};
+
+// spk_label_pairs_scores_tf*: the arguments and the state, before anything is staged (scores_tf_begin's rules).
+static int pair_scores_tf_begin(PairScoreCall &C, int64_t n_labels, const int32_t *rows_l, const int32_t *rows_r,
+                                const uint8_t *is_match, const double *m, const double *u, int n_tf_cols,
+                                bool ids_given, const double *const *adj_tables, const int64_t *table_sizes,
+                                int n_thresholds, const double *thresholds, const uint64_t *out_counts,
+                                const int64_t *out_pair, const double *out_score) {
+    spk_ctx *ctx = C.ctx;
+    const std::string w(C.what);
+    SPK_TRY(C.check(n_labels, rows_l, rows_r, is_match, n_thresholds, thresholds, out_counts, out_pair, out_score));
+    SPK_REQUIRE(m && u, SPK_E_INVALID, w + ": m and u are required");
+    SPK_REQUIRE(n_tf_cols >= 1 && n_tf_cols <= 8, SPK_E_INVALID, w + ": 1..8 columns");
+    SPK_REQUIRE(ids_given && adj_tables && table_sizes, SPK_E_INVALID, w + ": null arg");
+    SPK_REQUIRE(ctx->codes_valid, SPK_E_STATE, w + ": no gammas");
+    SPK_TRY(settle_gammas(ctx, nullptr));
+    SPK_REQUIRE(ctx->codes_valid, SPK_E_STATE, w + ": no gammas");
+    const int64_t P = ctx->n_pairs;
+    SPK_REQUIRE(ctx->pairs_valid && ctx->pl.p && ctx->pr.p && ctx->pl.n >= (size_t)P && ctx->pr.n >= (size_t)P,
+                SPK_E_STATE, w + ": no pair rows (a loaded gamma table)");
+    SPK_REQUIRE(ctx->n_patterns >= 1 && ctx->n_patterns <= (int64_t)UINT32_MAX, SPK_E_LIMIT, w + ": pattern space");
+    SPK_REQUIRE(ctx->table[0].n >= 0 && ctx->side_table(1).n >= 0, SPK_E_STATE, w + ": no tables");
+    return SPK_OK;
+}
+
+// The counting itself, once the value ids are staged in G.
+static int pair_scores_tf_run(PairScoreCall &C, TfStage &G, const int32_t *rows_l, const int32_t *rows_r,
+                              const uint8_t *is_match, double lambda, double one_minus, const double *m,
+                              const double *u, const double *const *adj_tables, const int64_t *table_sizes,
+                              const double *thresholds, uint64_t *out_counts, int64_t *out_pair, double *out_score) {
+    spk_ctx *ctx = C.ctx;
+    const int64_t P = ctx->n_pairs, n0 = ctx->table[0].n, n1 = ctx->side_table(1).n;
+    hipStream_t st = ctx->stream;
+    SPK_TRY(tf_stage_tables(ctx, adj_tables, table_sizes, G));
+    DevBuf<double> mpat;  // mp per pattern under the call's parameters: never ctx->mp
+    SPK_TRY(mpat.alloc((size_t)ctx->n_patterns + 1));
+    SPK_TRY(C.stage(rows_l, rows_r, is_match, thresholds, n0, n1));
+    SPK_TRY(C.timer.open());
+    SPK_TRY(pattern_mp_table(ctx, lambda, one_minus, m, u, mpat.p));
+    SPK_TRY(C.clear());
+    PairScoreArgs B{};
+    C.fill(B, P, ctx->pl.p, ctx->pr.p, n0, n1);
+    B.S.mpat = mpat.p;
+    const unsigned g = score_grid(ctx, P, LPS_PAIRS, LPS_WAVES_PER_SIMD);
+    const size_t lds = score_lds_bytes(C.T);
+    if (ctx->code_bytes == 2) {
+        const uint16_t *codes = reinterpret_cast<const uint16_t *>(ctx->codes.p);
+        if (P > 0) k_label_pairs_scores_tf<uint16_t, LPS_PAIRS><<<g, LS_THREADS, lds, st>>>(B, G.T, codes);
+        SPK_HIP(hipGetLastError());
+        SPK_TRY(C.per_label_launch<uint16_t>(B, true, G.T, codes));
+    } else {
+        const uint32_t *codes = reinterpret_cast<const uint32_t *>(ctx->codes.p);
+        if (P > 0) k_label_pairs_scores_tf<uint32_t, LPS_PAIRS><<<g, LS_THREADS, lds, st>>>(B, G.T, codes);
+        SPK_HIP(hipGetLastError());
+        SPK_TRY(C.per_label_launch<uint32_t>(B, true, G.T, codes));
+    }
+    return C.finish(P, out_counts, out_pair, out_score);
 }
 
 }  // namespace spk
@@ -918,56 +1385,23 @@ extern "C" int spk_label_pairs_histogram(spk_ctx *ctx, int64_t n_labels, const i
                 "spk_label_pairs_histogram: more than 2^30 (state, pattern) counters");
     Table &t0 = ctx->table[0], &t1 = ctx->side_table(1);
     SPK_REQUIRE(t0.n >= 0 && t1.n >= 0, SPK_E_STATE, "spk_label_pairs_histogram: no tables");
-    int64_t capacity = 64;
-    while (capacity < 2 * n_labels) capacity *= 2;
     // everything below lives for this call only
-    DevBuf<unsigned long long> slot, hist;
-    DevBuf<uint32_t> index;
-    DevBuf<int32_t> d_l, d_r, code;
-    DevBuf<uint8_t> d_match;
-    DevBuf<unsigned int> flags;  // [0] the bad bits, [1] the longest insert probe
+    PairTableStage S;
+    DevBuf<unsigned long long> hist;
+    DevBuf<int32_t> code;
     DevBuf<double> mpat;
     StageTimer T{ctx};
-    SPK_TRY(slot.alloc((size_t)capacity));
-    SPK_TRY(index.alloc((size_t)capacity));
     SPK_TRY(hist.alloc((size_t)3 * n_pat));
-    SPK_TRY(flags.alloc(2));
     if (out_pattern_mp) SPK_TRY(mpat.alloc((size_t)n_pat));
+    if (out_label_code && n_labels > 0) SPK_TRY(code.alloc((size_t)n_labels));
     hipStream_t st = ctx->stream;
-    PairTable tab{slot.p, index.p, (uint32_t)(capacity - 1), (uint32_t)n_labels, ctx->link_type == SPK_LINK_ONLY};
-    unsigned int h_flags[2] = {0u, 0u};
-    // ---- the table: cleared, then one insert per label; what is wrong with the labels is known before a pair is counted
-    if (n_labels > 0) {
-        SPK_TRY(d_l.alloc((size_t)n_labels));
-        SPK_TRY(d_r.alloc((size_t)n_labels));
-        SPK_TRY(d_match.alloc((size_t)n_labels));
-        if (out_label_code) SPK_TRY(code.alloc((size_t)n_labels));
-        SPK_HIP(hipMemcpyAsync(d_l.p, rows_l, (size_t)n_labels * 4, hipMemcpyHostToDevice, st));
-        SPK_HIP(hipMemcpyAsync(d_r.p, rows_r, (size_t)n_labels * 4, hipMemcpyHostToDevice, st));
-        SPK_HIP(hipMemcpyAsync(d_match.p, is_match, (size_t)n_labels, hipMemcpyHostToDevice, st));
-    }
-    SPK_TRY(T.open());
-    SPK_HIP(hipMemsetAsync(flags.p, 0, 2 * sizeof(unsigned int), st));
-    SPK_HIP(hipMemsetAsync(slot.p, 0xFF, (size_t)capacity * 8, st));
-    if (n_labels > 0) {
-        if (out_label_code) SPK_HIP(hipMemsetAsync(code.p, 0xFF, (size_t)n_labels * 4, st));  // -1
-        k_label_pairs_build<<<(unsigned)((n_labels + LP_BUILD_THREADS - 1) / LP_BUILD_THREADS), LP_BUILD_THREADS, 0,
-                              st>>>(n_labels, d_l.p, d_r.p, d_match.p, (uint32_t)t0.n, (uint32_t)t1.n, tab, flags.p);
-        SPK_HIP(hipGetLastError());
-    }
-    SPK_TRY(T.stop());
-    SPK_HIP(hipMemcpyAsync(h_flags, flags.p, sizeof(h_flags), hipMemcpyDeviceToHost, st));
-    SPK_HIP(hipStreamSynchronize(st));
-    SPK_TRY(T.add());
-    SPK_REQUIRE(!(h_flags[0] & LP_BAD_FLAG), SPK_E_INVALID, "spk_label_pairs_histogram: an is_match other than 0 or 1");
-    SPK_REQUIRE(!(h_flags[0] & LP_BAD_ROW), SPK_E_INVALID,
-                "spk_label_pairs_histogram: a labelled pair names a row outside its table");
-    SPK_REQUIRE(!(h_flags[0] & LP_BAD_SELF), SPK_E_INVALID,
-                "spk_label_pairs_histogram: a labelled pair of a record with itself");
-    SPK_REQUIRE(!(h_flags[0] & LP_BAD_TWICE), SPK_E_INVALID, "spk_label_pairs_histogram: a labelled pair given twice");
-    SPK_REQUIRE(h_flags[0] == 0u, SPK_E_STATE, "spk_label_pairs_histogram: the pair table is full");
+    SPK_TRY(stage_pair_table(ctx, "spk_label_pairs_histogram", n_labels, rows_l, rows_r, is_match, t0.n, t1.n, T, S));
+    const int64_t capacity = S.capacity;
+    unsigned int h_flags[2] = {0u, (unsigned int)S.max_probe};
+    DevBuf<unsigned int> &flags = S.flags;
     // ---- mp per pattern (spk_score's own kernel and arguments) and the counts
     SPK_TRY(T.open());
+    if (code.p) SPK_HIP(hipMemsetAsync(code.p, 0xFF, (size_t)n_labels * 4, st));  // -1
     if (out_pattern_mp) SPK_TRY(pattern_mp_table(ctx, lambda, one_minus, m, u, mpat.p));
     SPK_HIP(hipMemsetAsync(hist.p, 0, (size_t)3 * n_pat * 8, st));
     if (P > 0) {
@@ -975,7 +1409,7 @@ extern "C" int spk_label_pairs_histogram(spk_ctx *ctx, int64_t n_labels, const i
         A.P = P;
         A.pl = ctx->pl.p;
         A.pr = ctx->pr.p;
-        A.T = tab;
+        A.T = S.tab;
         A.n0 = (uint32_t)t0.n;
         A.n1 = (uint32_t)t1.n;
         A.n_pat = (uint32_t)n_pat;
@@ -1012,6 +1446,100 @@ extern "C" int spk_label_pairs_info(spk_ctx *ctx, int64_t *out_pairs, double *ou
     if (out_ms) *out_ms = ctx->lpairs_ms;
     if (out_capacity) *out_capacity = ctx->lpairs_capacity;
     if (out_max_probe) *out_max_probe = ctx->lpairs_max_probe;
+    return SPK_OK;
+}
+
+static void pair_scores_info_reset(spk_ctx *ctx) {
+    ctx->lpscore_pairs = ctx->lpscore_capacity = -1;
+    ctx->lpscore_ms = -1.0;
+    ctx->lpscore_max_probe = -1;
+}
+
+extern "C" int spk_label_pairs_scores_tf(spk_ctx *ctx, int64_t n_labels, const int32_t *rows_l, const int32_t *rows_r,
+                                         const uint8_t *is_match, double lambda, double one_minus, const double *m,
+                                         const double *u, int n_tf_cols, const int64_t *const *ids_side0,
+                                         const int64_t *const *ids_side1, const double *const *adj_tables,
+                                         const int64_t *table_sizes, int n_thresholds, const double *thresholds,
+                                         uint64_t *out_counts, int64_t *out_label_pair, double *out_label_score) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_label_pairs_scores_tf: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    pair_scores_info_reset(ctx);
+    PairScoreCall C(ctx, "spk_label_pairs_scores_tf");
+    SPK_TRY(pair_scores_tf_begin(C, n_labels, rows_l, rows_r, is_match, m, u, n_tf_cols, ids_side0 && ids_side1,
+                                 adj_tables, table_sizes, n_thresholds, thresholds, out_counts, out_label_pair,
+                                 out_label_score));
+    TfStage G;  // the id arrays and tables live until this call returns
+    SPK_TRY(tf_stage_host_ids(ctx, n_tf_cols, ids_side0, ids_side1, G));
+    return pair_scores_tf_run(C, G, rows_l, rows_r, is_match, lambda, one_minus, m, u, adj_tables, table_sizes,
+                              thresholds, out_counts, out_label_pair, out_label_score);
+}
+
+extern "C" int spk_label_pairs_scores_tf_columns(spk_ctx *ctx, int64_t n_labels, const int32_t *rows_l,
+                                                 const int32_t *rows_r, const uint8_t *is_match, double lambda,
+                                                 double one_minus, const double *m, const double *u, int n_tf_cols,
+                                                 const int32_t *cols, const double *const *adj_tables,
+                                                 const int64_t *table_sizes, int n_thresholds, const double *thresholds,
+                                                 uint64_t *out_counts, int64_t *out_label_pair,
+                                                 double *out_label_score) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_label_pairs_scores_tf_columns: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    pair_scores_info_reset(ctx);
+    PairScoreCall C(ctx, "spk_label_pairs_scores_tf_columns");
+    SPK_TRY(pair_scores_tf_begin(C, n_labels, rows_l, rows_r, is_match, m, u, n_tf_cols, cols != nullptr, adj_tables,
+                                 table_sizes, n_thresholds, thresholds, out_counts, out_label_pair, out_label_score));
+    TfStage G;
+    SPK_TRY(tf_stage_column_ids(ctx, n_tf_cols, cols, G));
+    return pair_scores_tf_run(C, G, rows_l, rows_r, is_match, lambda, one_minus, m, u, adj_tables, table_sizes,
+                              thresholds, out_counts, out_label_pair, out_label_score);
+}
+
+extern "C" int spk_label_pairs_scores_selection(spk_ctx *ctx, int64_t n_labels, const int32_t *rows_l,
+                                                const int32_t *rows_r, const uint8_t *is_match, int field,
+                                                int n_thresholds, const double *thresholds, uint64_t *out_counts,
+                                                int64_t *out_label_pair, double *out_label_score) {
+    const char *what = "spk_label_pairs_scores_selection";
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_label_pairs_scores_selection: null ctx");
+    SPK_HIP(hipSetDevice(ctx->device));
+    pair_scores_info_reset(ctx);
+    PairScoreCall C(ctx, what);
+    const std::string w(what);
+    SPK_TRY(C.check(n_labels, rows_l, rows_r, is_match, n_thresholds, thresholds, out_counts, out_label_pair,
+                    out_label_score));
+    SPK_REQUIRE(field == SPK_SEL_MP || field == SPK_SEL_TF_MP, SPK_E_INVALID, w + ": unknown field");
+    const Selection &S = ctx->sel;
+    SPK_REQUIRE(S.valid, SPK_E_STATE, w + ": no selection (run spk_select*)");
+    SPK_REQUIRE(S.current(ctx), SPK_E_STATE, w + ": the pairs or codes changed since spk_select*");
+    SPK_REQUIRE(S.has_rows, SPK_E_STATE, w + ": no pair rows (a loaded gamma table)");
+    SPK_REQUIRE(field != SPK_SEL_MP || S.has_mp, SPK_E_STATE, w + ": spk_select got no m / u");
+    SPK_REQUIRE(field != SPK_SEL_TF_MP || S.has_tf, SPK_E_STATE,
+                w + ": the selection was made without tf tables (spk_select)");
+    SPK_REQUIRE(ctx->n_patterns >= 1 && ctx->n_patterns <= (int64_t)UINT32_MAX, SPK_E_LIMIT, w + ": pattern space");
+    const int64_t n = S.n, n0 = ctx->table[0].n, n1 = ctx->side_table(1).n;
+    SPK_REQUIRE(n0 >= 0 && n1 >= 0, SPK_E_STATE, w + ": no tables");
+    hipStream_t st = ctx->stream;
+    SPK_TRY(C.stage(rows_l, rows_r, is_match, thresholds, n0, n1));
+    SPK_TRY(C.timer.open());
+    SPK_TRY(C.clear());
+    PairScoreArgs B{};
+    C.fill(B, n, S.l.p, S.r.p, n0, n1);
+    B.S.code = S.code.p;
+    B.S.mpat = S.mpat.p;
+    B.S.per_pair = field == SPK_SEL_TF_MP ? S.tf_mp.p : nullptr;
+    if (n > 0) {
+        k_label_pairs_scores_sel<<<score_grid(ctx, n, 1, LPS_SEL_WG_PER_CU), LS_THREADS, score_lds_bytes(C.T), st>>>(B);
+        SPK_HIP(hipGetLastError());
+    }
+    SPK_TRY(C.per_label_launch<uint32_t>(B, false, TfApply{}, S.code.p));
+    return C.finish(n, out_counts, out_label_pair, out_label_score);
+}
+
+extern "C" int spk_label_pairs_scores_info(spk_ctx *ctx, int64_t *out_pairs, double *out_ms, int64_t *out_capacity,
+                                           int *out_max_probe) {
+    SPK_REQUIRE(ctx, SPK_E_INVALID, "spk_label_pairs_scores_info: null ctx");
+    if (out_pairs) *out_pairs = ctx->lpscore_pairs;
+    if (out_ms) *out_ms = ctx->lpscore_ms;
+    if (out_capacity) *out_capacity = ctx->lpscore_capacity;
+    if (out_max_probe) *out_max_probe = ctx->lpscore_max_probe;
     return SPK_OK;
 }
 

@@ -287,6 +287,51 @@ def _score_label_counts(job, counts, totals, t, ids0, ids1):
     return ScoreLabelCounts(counts, t, totals, job.link_type, true_pairs_total(job.link_type, ids0, ids1))
 
 
+def _pair_label_input(job, labels, match_threshold, what):
+    """(labels as pandas, rows_l, rows_r, is_match) of a labels table (labels.pair_label_rows' columns and
+    validation), before the device is touched."""
+    from .labels import pair_label_rows
+    if getattr(job, "passthrough", None) is not None:
+        raise ValueError(f"{what}() needs the records: a job made from a gamma table has pairs without rows")
+    if not isinstance(labels, pd.DataFrame):
+        from .blocking import as_pandas
+        labels = as_pandas(labels)
+    return (labels,) + tuple(pair_label_rows(pair_label_sides(job), labels, match_threshold))
+
+
+def _pair_score_label_counts(job, labels, is_match, counts, pair, score, t, score_name, candidates=None):
+    """PairScoreLabelCounts of one rank's (or the one GPU's) spk_label_pairs_scores_* results.  candidates: for a
+    selection frame, (counts [3, n_patterns], label_code) of spk_label_pairs_histogram over the parent's pairs -- the
+    totals fn and tn are taken against, and which labels blocking produced; None: the counts' own row sums.  On a
+    sharded job the counts and totals are summed over the ranks (exact integers); a labelled pair is a candidate of
+    one rank only, so found / kept are all-reduced with max, and so is the score, with "none / NULL" mapped to -inf
+    for the reduction and restored afterwards; label_pair, an index local to a rank, is then dropped."""
+    from . import distributed as D
+    from .labels import PairScoreLabelCounts
+    totals = None if candidates is None else candidates[0].sum(axis=1)
+    by_blocking = None if candidates is None else (np.asarray(candidates[1]) >= 0)
+    if not (job.reduces_across_ranks() or job.force_reduce):
+        if totals is None:
+            totals = counts.sum(axis=1)
+        return PairScoreLabelCounts(counts, t, totals, job.link_type, labels, is_match, score, score_name,
+                                    label_pair=pair, found_by_blocking=by_blocking)
+    D.allreduce_host_(counts, force=job.force_reduce)
+    if totals is None:
+        totals = counts.sum(axis=1)
+    else:
+        D.allreduce_host_(totals, force=job.force_reduce)
+    found = (np.asarray(pair) >= 0).astype(np.int32)
+    D.allreduce_host_(found, force=job.force_reduce, op="max")
+    if by_blocking is not None:
+        by_blocking = by_blocking.astype(np.int32)
+        D.allreduce_host_(by_blocking, force=job.force_reduce, op="max")
+    score = np.where(np.isnan(score), -np.inf, score)
+    D.allreduce_host_(score, force=job.force_reduce, op="max")
+    score = np.where(np.isneginf(score), np.nan, score)
+    return PairScoreLabelCounts(counts, t, totals, job.link_type, labels, is_match, score, score_name,
+                                found=found, found_by_blocking=by_blocking)
+
+
 class ComparisonFrame(SplinkDataFrame):
     """Candidate pairs (block_using_rules)."""
 
@@ -654,23 +699,50 @@ class FilteredFrame(SplinkDataFrame):
         thresholds: one row per threshold, ascending, the kept pairs with score > threshold predicted (a NULL score
         never); by: the score, the frame's first by default.  fn and tn are taken against the labelled pairs among
         all candidate pairs of the job, so what the filter or the best-match step dropped counts as missed."""
-        from . import _native as N
         job = self.job
         if getattr(job, "passthrough", None) is not None:
             raise ValueError("truth_table() needs the records: a job made from a gamma table has pairs without rows")
-        names = self._score_names()
-        by = names[0] if by is None else by
-        if self._scored_parent() is None or by not in names:
-            raise ValueError(f"truth_table: this frame has no score {by!r}" +
-                             (" (it was filtered from an unscored frame)" if self._scored_parent() is None
-                              else f": by is one of {list(names)}"))
+        by, field = self._score_field(by, "truth_table")
         ids0, ids1 = _label_ids(job, label_column)  # a missing column fails before the device is touched
         t = _score_thresholds([] if thresholds is None else thresholds, "truth_table")
         self._select()
-        field = N.SEL_TF_MP if by == "tf_adjusted_match_prob" else N.SEL_MP
         counts = job.ctx.label_scores_selection(ids0, ids1, field, t)
         totals = job.ctx.label_histogram(ids0, ids1)[0].sum(axis=1)  # the parent's pairs: one pass, no scores
         slc = _score_label_counts(job, counts, totals, t, ids0, ids1)
+        return slc.kept_row() if thresholds is None else slc.truth_table()
+
+    def _score_field(self, by, what):
+        """(the score's column name, its SEL_* field) for `by`, the frame's first score by default."""
+        from . import _native as N
+        names = self._score_names()
+        by = names[0] if by is None else by
+        if self._scored_parent() is None or by not in names:
+            raise ValueError(f"{what}: this frame has no score {by!r}" +
+                             (" (it was filtered from an unscored frame)" if self._scored_parent() is None
+                              else f": by is one of {list(names)}"))
+        return by, (N.SEL_TF_MP if by == "tf_adjusted_match_prob" else N.SEL_MP)
+
+    def label_counts_from_pairs(self, labels, match_threshold=0.5, thresholds=None, by=None):
+        """This frame's pairs against a table of labelled pairs (a clerical-review sample: labels.pair_label_rows'
+        columns), counted on the device (spk_label_pairs_scores_selection): a `PairScoreLabelCounts`, whose
+        labelled_pairs() says of every label whether blocking found the pair, whether this frame kept it and with
+        which score, and whose prediction_errors(threshold) lists the labels the frame gets wrong.  thresholds: as
+        for truth_table (None: none, kept_row() describes the frame as it stands); by: the score, the frame's first
+        by default.  fn and tn are taken against the labelled pairs among all candidate pairs of the job."""
+        job = self.job
+        labels, rows_l, rows_r, is_match = _pair_label_input(job, labels, match_threshold, "label_counts_from_pairs")
+        by, field = self._score_field(by, "label_counts_from_pairs")
+        t = _score_thresholds([] if thresholds is None else thresholds, "label_counts_from_pairs")
+        self._select()
+        counts, pair, score = job.ctx.label_pair_scores_selection(rows_l, rows_r, is_match, field, t)
+        hist, _, code = job.ctx.label_pairs_histogram(rows_l, rows_r, is_match)  # the parent's pairs: no scores
+        return _pair_score_label_counts(job, labels, is_match, counts, pair, score, t, by, candidates=(hist, code))
+
+    def truth_table_from_pairs(self, labels, thresholds=None, match_threshold=0.5, by=None):
+        """truth_table against a table of labelled pairs: thresholds=None gives the one row that describes the frame
+        as it stands, given thresholds one row each; tp, fp, tn, fn over the labelled candidate pairs,
+        recall_of_all_true_pairs over all labelled matches."""
+        slc = self.label_counts_from_pairs(labels, match_threshold, thresholds, by)
         return slc.kept_row() if thresholds is None else slc.truth_table()
 
 
@@ -771,6 +843,13 @@ class SampleFrame(FilteredFrame):
                          "of them would describe the draw, not the linkage (order the filtered frame instead)")
 
     orderBy = sort = limit = _refuse_order
+
+    def _refuse_pair_labels(self, *args, **kwargs):
+        raise ValueError("a sample frame takes no label_counts_from_pairs() or truth_table_from_pairs(): its rows are "
+                         "a random subset, and a table against them would describe the draw, not the linkage (score "
+                         "the filtered frame instead)")
+
+    label_counts_from_pairs = truth_table_from_pairs = _refuse_pair_labels
 
     def _select(self):
         """Make the context's selection this frame's, under the ownership rules of FilteredFrame._select."""

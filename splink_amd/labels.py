@@ -407,6 +407,67 @@ class PairLabelCounts(LabelCounts):
         return out
 
 
+class PairScoreLabelCounts(ScoreLabelCounts):
+    """ScoreLabelCounts of a frame's pairs against a table of labelled pairs (spk_label_pairs_scores_*): the
+    counterpart of PairLabelCounts for tf_adjusted_match_prob and for the pairs a filter or a best-match step kept.
+
+    labels: the labels table; is_match [len(labels)]: its thresholded scores; label_score [len(labels)]: the score
+    (the column `score_name`) of the frame's pair each label names, NaN when the frame has no such pair or its score
+    is NULL; label_pair [len(labels)]: that pair's index in the frame, -1 = none, or None on a sharded job (the index
+    is local to a rank) -- then `found` [len(labels)] says which labels name a pair of the frame.  found_by_blocking
+    [len(labels)] (selection frames; None: the frame holds every candidate pair, so it is `found`): the label names
+    a candidate pair of the job, kept or not.  true_pairs_total is the number of labelled matches, as in
+    PairLabelCounts; truth_table() and kept_row() are ScoreLabelCounts' own."""
+
+    def __init__(self, counts, thresholds, totals, link_type, labels, is_match, label_score, score_name,
+                 label_pair=None, found=None, found_by_blocking=None):
+        self.labels = labels
+        self.is_match = np.ascontiguousarray(is_match).astype(bool)
+        self.label_score = np.ascontiguousarray(label_score, dtype=np.float64)
+        self.score_name = str(score_name)
+        n = len(labels)
+        if (label_pair is None) == (found is None):
+            raise ValueError("PairScoreLabelCounts: give label_pair, or found on a sharded job")
+        self.label_pair = None if label_pair is None else np.ascontiguousarray(label_pair, dtype=np.int64)
+        self.found = self.label_pair >= 0 if found is None else np.ascontiguousarray(found).astype(bool)
+        self.selection = found_by_blocking is not None
+        self.found_by_blocking = (np.ascontiguousarray(found_by_blocking).astype(bool) if self.selection
+                                  else self.found.copy())
+        if not n == len(self.is_match) == len(self.label_score) == len(self.found) == len(self.found_by_blocking):
+            raise ValueError("PairScoreLabelCounts: labels, is_match, label_score, label_pair and found_by_blocking "
+                             "differ in length")
+        if (self.found & ~self.found_by_blocking).any():
+            raise ValueError("PairScoreLabelCounts: a label names a pair of the frame that blocking did not produce")
+        if (~self.found & ~np.isnan(self.label_score)).any():
+            raise ValueError("PairScoreLabelCounts: a score for a label that names no pair of the frame")
+        super().__init__(counts, thresholds, totals, link_type, true_pairs_total=int(self.is_match.sum()))
+        # a pair set may repeat a pair, so more pairs than labels may be counted, never fewer
+        if int(self.counts[MATCH].sum()) < int((self.found & self.is_match).sum()) or \
+                int(self.counts[NON_MATCH].sum()) < int((self.found & ~self.is_match).sum()):
+            raise ValueError("PairScoreLabelCounts: fewer labelled pairs counted than labels found")
+
+    def labelled_pairs(self) -> pd.DataFrame:
+        """The labels table in its own row order plus found_by_blocking, for a filtered or best-match frame `kept`
+        (the frame holds the pair), and the score column (NaN where the frame has no such pair)."""
+        out = self.labels.copy()
+        out["found_by_blocking"] = self.found_by_blocking
+        if self.selection:
+            out["kept"] = self.found
+        out[self.score_name] = self.label_score
+        return out
+
+    def prediction_errors(self, threshold: float) -> pd.DataFrame:
+        """The rows of labelled_pairs() that `score > threshold` gets wrong, with a column `error`: "fp" for a
+        labelled non-match above the threshold, "fn" for a labelled match that is not -- a NULL score is never
+        predicted a match, so a labelled match that is not among the frame's pairs is an "fn"."""
+        pairs = self.labelled_pairs()
+        predicted = self.label_score > float(threshold)
+        fp, fn = predicted & ~self.is_match, ~predicted & self.is_match
+        out = pairs[fp | fn].copy()
+        out["error"] = np.where(fp[fp | fn], "fp", "fn")
+        return out
+
+
 def estimate_from_pair_labels(df_gammas: object, params, settings: dict, spark: object, labels: pd.DataFrame,
                               match_threshold: float = 0.5):
     """estimate_from_labels with the truth taken from a table of labelled pairs (pair_label_rows' columns): one M-step

@@ -155,6 +155,37 @@ class TermFrequencyFrame(SplinkDataFrame):
             counts = job.ctx.label_scores_tf(lab0, lab1, lam, float(1 - df_e.lam), m, u, ids0, ids1, self.tables, t)
         return _score_label_counts(job, counts, None, t, lab0, lab1).truth_table()
 
+    def label_counts_from_pairs(self, labels, match_threshold=0.5, thresholds=None):
+        """Every pair of this frame against a table of labelled pairs (a clerical-review sample:
+        labels.pair_label_rows' columns), by tf_adjusted_match_prob, counted on the device
+        (spk_label_pairs_scores_tf*): a `PairScoreLabelCounts`.  The per-pair part of this frame never runs and no
+        pair leaves the device but the scores of the labelled ones.  thresholds=None: the thresholds of
+        df_e.truth_table_from_pairs(labels, match_threshold=match_threshold), so the two tables line up row for row."""
+        from .frames import _pair_label_input, _pair_score_label_counts, _score_thresholds
+        job, df_e = self.job, self.df_e
+        labels, rows_l, rows_r, is_match = _pair_label_input(job, labels, match_threshold, "label_counts_from_pairs")
+        if thresholds is None:
+            thresholds = df_e.truth_table_from_pairs(labels, None, match_threshold)["threshold"].to_numpy()
+        t = _score_thresholds(thresholds, "label_counts_from_pairs")
+        df_e.gammas.ensure_codes()
+        m, u = job.flat_tables(df_e.level_probs)
+        lam = float(df_e.lam)
+        if self.dev_cols is not None:
+            counts, pair, score = job.ctx.label_pair_scores_tf_columns(rows_l, rows_r, is_match, lam,
+                                                                       float(1 - df_e.lam), m, u, self.dev_cols,
+                                                                       self.tables, t)
+        else:
+            ids0, ids1 = self.host_ids
+            counts, pair, score = job.ctx.label_pair_scores_tf(rows_l, rows_r, is_match, lam, float(1 - df_e.lam), m,
+                                                               u, ids0, ids1, self.tables, t)
+        return _pair_score_label_counts(job, labels, is_match, counts, pair, score, t, "tf_adjusted_match_prob")
+
+    def truth_table_from_pairs(self, labels, thresholds=None, match_threshold=0.5):
+        """The confusion matrix of `tf_adjusted_match_prob > threshold` against a table of labelled pairs, with
+        df_e.truth_table_from_pairs' columns.  Shorthand for
+        label_counts_from_pairs(labels, match_threshold, thresholds).truth_table()."""
+        return self.label_counts_from_pairs(labels, match_threshold, thresholds).truth_table()
+
 
 class TfFilteredFrame(FilteredFrame):
     """`tf.filter(condition)`: toPandas() equals tf.toPandas()[mask].reset_index(drop=True).  A predicate without a
