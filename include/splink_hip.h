@@ -137,6 +137,11 @@ typedef struct {
  * and verified dense ids on the device, one id space for both sides.  Same result as
  * spk_table_set_key with host-computed ids (which stays available for other key expressions). */
 int spk_key_build(spk_ctx *ctx, int rule, int n_terms, const spk_key_term *terms);
+/* Width of the hash behind the dense ids of spk_key_build and spk_table_add_raw_utf8: 1 .. 63 bits, 63 by
+ * default (then the ids are what they were without this call).  A test knob: at a few bits values collide,
+ * which reaches the byte-for-byte verification, the retry under the next of four seeds and the SPK_E_STATE
+ * return after the fourth.  Which values share an id does not depend on the width (the ids' order does). */
+int spk_ingest_set_hash_bits(spk_ctx *ctx, int bits);
 /* Rank for the link predicate from int64 unique ids (raw column, NULL allowed): dense rank, rows
  * [right_from, n) being the 'right' source of link_and_dedupe (-1 = none).  Also sets the NULL-id
  * layout of spk_table_set_rank_null. */

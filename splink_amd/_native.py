@@ -102,6 +102,7 @@ EXPORTS = [
     "spk_pairs_sample", "spk_pairs_sample_info",
     "spk_block_profile", "spk_block_profile_info", "spk_block_profile_set_cut",
     "spk_em_lane_copies",
+    "spk_ingest_set_hash_bits",
 ]
 # spk_rule_profile / spk_block_entry: the per-rule figures and one of a rule's largest blocks (spk_block_profile)
 RULE_PROFILE_DTYPE = np.dtype([("rows_l", "<i8"), ("rows_r", "<i8"), ("blocks", "<i8"), ("candidates", "<i8"),
@@ -326,6 +327,11 @@ class Context:
     def key_build(self, rule, terms):
         t = np.array([tuple(x) for x in terms], dtype=KEY_TERM_DTYPE)
         check(self._lib.spk_key_build(self._h, ctypes.c_int(rule), ctypes.c_int(len(t)), _ptr(t)), "spk_key_build")
+
+    def ingest_set_hash_bits(self, bits: int):
+        """Width (1 .. 63 bits, default 63) of the hash behind key_build's and table_add_raw_utf8's dense ids:
+        tests reach the collision check, the retry under the next seed and the error after four with it."""
+        check(self._lib.spk_ingest_set_hash_bits(self._h, ctypes.c_int(int(bits))), "spk_ingest_set_hash_bits")
 
     def rank_from_raw(self, raw_uid, right_from=-1):
         check(self._lib.spk_rank_from_raw(self._h, ctypes.c_int(raw_uid), ctypes.c_int64(right_from)),

@@ -151,6 +151,9 @@ class _ProgramBuilder:
                 return OperandSpec(kind="num", num=float(node.value), form="num")
             raise ValueError(f"unsupported literal {node.value!r} as a comparison operand")
         if not isinstance(node, Col):
+            if default is not None and isinstance(node, Func) and node.name in ("substr", "substring"):
+                raise ValueError(f"{node.name}() inside ifnull() is not supported as a comparison operand (the other "
+                                 f"order, substr(ifnull(x, 'd'), pos, len), is: there the default is cut too)")
             raise ValueError(f"unsupported comparison operand: {node}")
         name, side = self._column_ref(node)
         form = form_hint or self.schema.form(name)
@@ -303,6 +306,8 @@ class _ProgramBuilder:
                 inner = inner.args[0]
                 if D.is_derived(inner):
                     return D.form_of(self._derived_neutral(inner)[0], self.schema.form)
+                if isinstance(inner, Func):  # ifnull(substr(x, ..), 'd'): operand() rejects the order
+                    return "str"
             if isinstance(inner, Lit):
                 return "str" if isinstance(inner.value, str) else "num"
             name, _ = self._column_ref(inner)

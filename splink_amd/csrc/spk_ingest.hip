@@ -92,8 +92,9 @@ __device__ inline uint64_t hash_bytes(const uint8_t *p, int64_t n, uint64_t seed
     return mix64(h ^ w ^ 0x632BE59BD9B4E019ull);
 }
 
-// keys[i] = 63-bit hash of global row i (rows [0, s0.n) of s0, then s1), ~0 for NULL; idx[i] = i.
-__global__ void k_hash(HashSeg s0, HashSeg s1, uint64_t seed, uint64_t *__restrict__ keys,
+// keys[i] = 63-bit hash of global row i (rows [0, s0.n) of s0, then s1), cut to the low bits of `mask`
+// (spk_ingest_set_hash_bits; all 63 by default), ~0 for NULL; idx[i] = i.
+__global__ void k_hash(HashSeg s0, HashSeg s1, uint64_t seed, uint64_t mask, uint64_t *__restrict__ keys,
                        int32_t *__restrict__ idx) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= s0.n + s1.n) return;
@@ -103,11 +104,11 @@ __global__ void k_hash(HashSeg s0, HashSeg s1, uint64_t seed, uint64_t *__restri
     uint64_t k = ~0ull;
     if (s.valid[row]) {
         if (s.kind == RAW_I64) {
-            k = mix64((uint64_t)s.i64[row] ^ seed) >> 1;
+            k = (mix64((uint64_t)s.i64[row] ^ seed) >> 1) & mask;
         } else {
             int64_t b, e;
             seg_range(s, row, b, e);
-            k = hash_bytes(s.bytes + b, e - b, seed) >> 1;
+            k = (hash_bytes(s.bytes + b, e - b, seed) >> 1) & mask;
         }
     }
     keys[i] = k;
@@ -263,16 +264,17 @@ static int hashed_ids(spk_ctx *ctx, const HashSeg &s0, const HashSeg &s1, DevBuf
     SPK_TRY(w.alloc(n));
     static const uint64_t seeds[4] = {0x243F6A8885A308D3ull, 0x13198A2E03707344ull, 0xA4093822299F31D0ull,
                                       0x082EFA98EC4E6C89ull};
+    const uint64_t mask = ~0ull >> (64 - ctx->ingest_hash_bits);  // 1 .. 63 bits: a key never equals ~0 (NULL)
     for (int attempt = 0; attempt < 4; ++attempt) {
         if (n > 0) {
-            k_hash<<<grid(n), 256, 0, ctx->stream>>>(s0, s1, seeds[attempt], w.k_in.p, w.i_in.p);
+            k_hash<<<grid(n), 256, 0, ctx->stream>>>(s0, s1, seeds[attempt], mask, w.k_in.p, w.i_in.p);
             SPK_HIP(hipGetLastError());
         }
         bool coll = false;
         SPK_TRY(sorted_ids(ctx, n, w, s0, s1, true, nullptr, ids.p, n_ids, &coll));
         if (!coll) return SPK_OK;
     }
-    set_error("device ingest: 64-bit hash collisions under four seeds");
+    set_error("device ingest: " + std::to_string(ctx->ingest_hash_bits) + "-bit hash collisions under four seeds");
     return SPK_E_STATE;
 }
 
@@ -662,6 +664,12 @@ int spk_key_build(spk_ctx *ctx, int rule, int n_terms, const spk_key_term *terms
         rec.push_back(k);
     }
     ctx->rule_terms[rule] = rec;
+    return SPK_OK;
+}
+
+int spk_ingest_set_hash_bits(spk_ctx *ctx, int bits) {
+    SPK_REQUIRE(ctx && bits >= 1 && bits <= 63, SPK_E_INVALID, "spk_ingest_set_hash_bits: 1 .. 63 bits");
+    ctx->ingest_hash_bits = bits;
     return SPK_OK;
 }
 

@@ -571,6 +571,7 @@ struct spk_ctx {
     spk::DevBuf<uint8_t> tf_sort;  // the sort form's keys, sorted keys and sort scratch (scale pass to sum pass)
     std::vector<int64_t> tf_key;
     int tf_mode = 0;  // spk_tf_set_mode: 0 auto (histogram when it fits), 1 always the sort, 2 the sort with 64-bit keys
+    int ingest_hash_bits = 63;  // spk_ingest_set_hash_bits: width of hashed_ids' hash (tests force collisions below 63)
     bool hist_lanes = true;  // k_hist_lanes (lane-private LDS counters) when the pattern space fits
     bool em_fence = true;    // k_em_iter: release fence before each ticket (spk_em_set_lane_histogram 2: none)
 

@@ -9,7 +9,9 @@ with an upper-case letter would not survive into the SQL that either side runs.
 
 Where sqlite and Spark differ the generator stays on common ground, so that sqlite can stand for Spark:
 * no +-Infinity and no NaN as a value (`inf - inf` and NaN ordering differ between Spark, sqlite and IEEE);
-* substr(x, p, n) only with p >= 1 and n >= 0 (position 0 and negative arguments differ);
+* substr(x, p, n) only with p >= 1 and n >= 0 (position 0 and negative arguments differ; those are checked
+  against a port of Spark's substringSQL instead: tests/substr_common.py, tests/test_substr_host.py,
+  tests/test_gpu_substr.py);
 * a string operand is never compared with a numeric one (sqlite's type affinity is not Spark's cast);
 * `is null` is applied to columns (possibly wrapped), not to literals;
 * lower() / trim() are the oracle's Python restatements on both sides (oracle.connect).

@@ -22,7 +22,9 @@ def key_tuples(df, exprs):
         vals = df[col].tolist()
         if sub is not None:
             a, n = sub
-            assert a >= 1
+            # Python slicing is Spark's substr only there (tests/substr_common.py has the whole function; position 0
+            # and negative arguments are pinned by tests/test_substr_host.py and tests/test_gpu_substr.py)
+            assert a >= 1 and n >= 0
             vals = [v if _null(v) else str(v)[a - 1:a - 1 + n] for v in vals]
         cols.append(vals)
     out = []
